@@ -19,6 +19,7 @@ One JSON line on rank 0.  `roofline` is for the dominant kernel symbol (by GPU t
 instrumented step): algorithmic conv FLOPs of its launches / their summed duration, measured with
 events on the launch stream; `cpu_baseline` is the oracle (CPU restatement of the reference step,
 oracle/esrgan_oracle.py) timed on this host's cores on a bounded sample.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see step_outputs).
 """
 import argparse
 import json
@@ -62,6 +63,13 @@ def parse():
     ap.add_argument("--no-parity-mode", "--no-legs", dest="no_parity_mode", action="store_true",
                     help="skip the legs (the other two arithmetic modes of the same step)")
     ap.add_argument("--leg-steps", type=int, default=0, help="timed steps per block of a leg; 0 = --steps (the headline's timing)")
+    ap.add_argument("--no-deterministic", action="store_true",
+                    help="run the step with arrival-order (atomic) reductions instead of the deterministic mode (StepConfig.deterministic): "
+                         "0.3 - 1.1 %% faster in profiles/README.md (r06h, r06i), but results then differ in the last bits from run to run and Adam carries that into the parameters")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (losses, generator output, updated G / EMA / D "
+                         "parameters: a fixed, seeded sample of each large arena) as DIR/<name>.npy, float32 / float64, at most 64 MB; "
+                         "seeded inputs and the deterministic step: the same arguments give the same files on every run")
     return ap.parse_args()
 
 
@@ -394,6 +402,51 @@ def forward_error(dtype, g_kw, c_in, g0=None):
     return float(((y - ref).abs() / (1e-3 * ref.abs().max() + 1e-3 * ref.abs())).max()) * 1e-3
 
 
+DUMP_SAMPLE = 1 << 20       # elements kept of a parameter arena larger than this by --dump-outputs (fixed positions)
+DUMP_OUTPUT = 1 << 22       # the same for the generator output (the flagship batch, 1.6 M elements, is written whole)
+DUMP_LIMIT = 64 << 20       # bytes, all files of one dump together
+
+
+def _whole_or_sample(t, limit):
+    """`t` on the host as float32: whole, or `limit` of its elements (flattened) at positions drawn once from a fixed seed"""
+    n = t.numel()
+    if n <= limit:
+        return t.float().cpu().numpy()
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:limit].sort().values
+    return t.reshape(-1)[idx.to(t.device)].float().cpu().numpy()
+
+
+def step_outputs(ts):
+    """What a caller of the timed step holds after its last step, as float32 / float64 host arrays: the losses of
+    get_current_log(), the generator output (NCHW), and the updated G, EMA-of-G and D parameters - each whole, or a fixed-seed
+    sample where it is larger than DUMP_OUTPUT / DUMP_SAMPLE elements (names ending in _sample) - plus D's spectral-norm u / v
+    buffers.  ts.log() is a collective under data parallelism: every rank calls this."""
+    import numpy as np
+    out = {f"loss_{k}": np.asarray(v, dtype=np.float64) for k, v in ts.log().items()}
+    y = ts.output()
+    out["output" if y.numel() <= DUMP_OUTPUT else "output_sample"] = _whole_or_sample(y, DUMP_OUTPUT)
+    arenas = {"g_params": ts.g_store.data, "d_params": ts.d_store.data}
+    if ts.opt_g.ema is not None:
+        arenas["g_ema_params"] = ts.opt_g.ema
+    for name, a in arenas.items():
+        out[name if a.numel() <= DUMP_SAMPLE else name + "_sample"] = _whole_or_sample(a, DUMP_SAMPLE)
+    sn = ts.d_store.sn_names
+    if sn:
+        out["d_sn_uv"] = torch.cat([t.flatten().float() for t in [ts.d_store.u[k] for k in sn] + [ts.d_store.v[k] for k in sn]]).cpu().numpy()
+    return out
+
+
+def write_outputs(arrays, d):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes > {DUMP_LIMIT}"
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ".npy"), a)
+    trace(f"dumped {len(arrays)} arrays, {total / 2**20:.1f} MiB, to {d}")
+
+
 ERR_DEFINITION = ("max over outputs of |y - ref| / (max|ref| + |ref|): <= 1e-3 is the north-star gate; SSR_RRDBNet(nb=23) "
                   "forward, B=4, vs oracle/esrgan_oracle.py (fp32 CPU)")
 ARITH = {"bf16": "bf16 tensors in HBM; v_mfma_f32_32x32x16_bf16, fp32 accumulate (throughput mode: outside the 1e-3 gate by the "
@@ -414,7 +467,8 @@ def precision_leg(args, dtype, g_kw, d_kw, c_in, c_d, B, lr, gt, steps):
     import gc
     from satlas_super_resolution_amd import flops
     from satlas_super_resolution_amd.train_step import ESRGANTrainStep, StepConfig
-    ts = ESRGANTrainStep(g_kw, d_kw, B, 32, 32, dtype, StepConfig(feed_disc_lr=args.feed_disc_lr), use_graph=not args.no_graph)
+    ts = ESRGANTrainStep(g_kw, d_kw, B, 32, 32, dtype, StepConfig(feed_disc_lr=args.feed_disc_lr, deterministic=not args.no_deterministic),
+                         use_graph=not args.no_graph)
     g0 = flops.generator_random_state(seed=0, **g_kw)
     ts.load_state(g0, flops.discriminator_random_state(c_d, 64, seed=1))
     ts.feed_data(lr, gt)
@@ -438,7 +492,8 @@ def precision_leg(args, dtype, g_kw, d_kw, c_in, c_d, B, lr, gt, steps):
     roof, breakdown = None, None
     if not args.no_roofline:
         def build():
-            tw = ESRGANTrainStep(g_kw, d_kw, B, 32, 32, dtype, StepConfig(feed_disc_lr=args.feed_disc_lr), use_graph=False)
+            tw = ESRGANTrainStep(g_kw, d_kw, B, 32, 32, dtype, StepConfig(feed_disc_lr=args.feed_disc_lr, deterministic=not args.no_deterministic),
+                                 use_graph=False)
             tw.load_state(g0, flops.discriminator_random_state(c_d, 64, seed=1))
             tw.feed_data(lr, gt)
             tw.step()
@@ -490,7 +545,7 @@ def main():
         percep = {"type": "PerceptualLoss", "layer_weights": {"conv1_2": 0.1, "conv2_2": 0.1, "conv3_4": 1, "conv4_4": 1, "conv5_4": 1},
                   "vgg_type": "vgg19", "use_input_norm": True, "perceptual_weight": 1.0, "style_weight": 0, "range_norm": False, "criterion": "l1"}
         vgg_state = P.vgg19_random_state(P.vgg19_specs("conv5_4"), seed=2)
-    ts = ESRGANTrainStep(g_kw, d_kw, B, 32, 32, args.dtype, StepConfig(feed_disc_lr=args.feed_disc_lr, perceptual=percep), dp=ctx,
+    ts = ESRGANTrainStep(g_kw, d_kw, B, 32, 32, args.dtype, StepConfig(feed_disc_lr=args.feed_disc_lr, perceptual=percep, deterministic=not args.no_deterministic), dp=ctx,
                          use_graph=not args.no_graph, vgg_state=vgg_state)
     # random-init weights of the named architecture (reference init distributions), identical on all ranks
     ts.load_state(flops.generator_random_state(seed=0, **g_kw), flops.discriminator_random_state(c_d, 64, seed=1))
@@ -538,6 +593,10 @@ def main():
                    "note": "comm_stream_busy = sum over the step's gradient exchanges of (end - start) on the comm stream: it overlaps the backward "
                            "and the discriminator phases by design; exposed communication = ms_per_step minus the single-GPU step time"}
     dt = float(tmax.item())
+    if args.dump_outputs:      # the state after the last timed step, before any further step runs
+        dumped = step_outputs(ts)
+        if ctx.rank == 0:
+            write_outputs(dumped, args.dump_outputs)
     if dp_diag is not None:
         # host cost of ONE step with an empty queue (inside the timed loop the host runs ahead until the launch queue pushes back: the
         # loop's enqueue time then measures the DEVICE): sync, enqueue one step, read the clock - median of five
@@ -586,7 +645,7 @@ def main():
                                + ("configs[2] (the metric's configuration)" if (args.frames, B) == (8, 32) else
                                   "configs[1]" if (args.frames, B) == (1, 16) else "non-headline") + " shape",
                    "per_gpu_batch": B, "global_batch": B * ctx.world, "parallelism": f"dp{ctx.world}",
-                   "hip_graph": not args.no_graph, "feed_disc_lr": args.feed_disc_lr,
+                   "hip_graph": not args.no_graph, "deterministic": bool(ts.det), "feed_disc_lr": args.feed_disc_lr,
                    "perceptual_vgg19": bool(args.perceptual), "overlap_d": bool(getattr(ts, "overlap_d", False))},
         "headline_mode": args.dtype,
         "step_gflop_per_image": gflop_img,
@@ -602,7 +661,7 @@ def main():
     agg, twin = None, False
     if not args.no_roofline:
         def build():
-            tw = ESRGANTrainStep(g_kw, d_kw, B, 32, 32, args.dtype, StepConfig(feed_disc_lr=args.feed_disc_lr, perceptual=percep), dp=ctx,
+            tw = ESRGANTrainStep(g_kw, d_kw, B, 32, 32, args.dtype, StepConfig(feed_disc_lr=args.feed_disc_lr, perceptual=percep, deterministic=not args.no_deterministic), dp=ctx,
                                  use_graph=False, vgg_state=vgg_state)
             tw.load_state(flops.generator_random_state(seed=0, **g_kw), flops.discriminator_random_state(c_d, 64, seed=1))
             tw.feed_data(lr, gt)

@@ -61,8 +61,8 @@ def _gen_state(c_in, nb, seed=11):
 # EXACT mode's forward criterion; split-bf16 backward) - and fp32x3 at the benchmarked configuration exactly (C_in 24, B = 32: big-tile /
 # register-tiled kernels are picked by the grid size); the fp32 modes run the same kernels
 # for any C_in beyond conv_first (C_in 3 / 96 end to end further down)
-# (bf16 at C_in 3 / 96 differs from C_in 24 in conv_first only: those two run with SSR_RUN_SLOW=1, tools/gpu_round.sh - the suite must
-#  fit the driver's time budget; the odd input widths keep their kernel-level cases in tests/test_gpu_parity.py)
+# (bf16 at C_in 3 / 96 differs from C_in 24 in conv_first only: those two are marked `slow` - run by default, -m "not slow" leaves
+#  them out; the odd input widths also keep their kernel-level cases in tests/test_gpu_parity.py)
 @pytest.mark.parametrize("mode,c_in,B", [("bf16", 24, 32), ("bf16", 24, 16), pytest.param("bf16", 3, 4, marks=pytest.mark.slow),
                                          pytest.param("bf16", 96, 4, marks=pytest.mark.slow), ("fp32", 24, 4), ("fp32h", 24, 32),
                                          pytest.param("fp32x3", 24, 32, marks=pytest.mark.slow)])      # (fp32x3: fp32h's backward IS fp32x3's; its forward keeps the kernel-level and full-size tests)
@@ -244,7 +244,7 @@ def _grad_close(got, ref, what, split=False):
 
 
 # (bf16 at C_in 3 / 96, the fp32x3 repeats around other first layers and the fp32f rows - the modes fp32h superseded as the headline / default -
-#  run with SSR_RUN_SLOW=1, tools/gpu_round.sh: the suite must fit the driver's time budget on a slow host)
+#  are marked `slow`: run by default, -m "not slow" leaves them out where a short suite is wanted)
 @pytest.mark.parametrize("mode,c_in,feed_disc_lr", [("bf16", 24, False), ("bf16", 24, True), pytest.param("bf16", 3, False, marks=pytest.mark.slow),
                                                     pytest.param("bf16", 96, False, marks=pytest.mark.slow)]
                          + [("fp32h", c, f) for c, f in ((3, False), (24, False), (24, True), (96, False))]
