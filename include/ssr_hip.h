@@ -405,6 +405,23 @@ int ssr_relu_maxpool2_fwd(ssr_view f, ssr_view p, int32_t dtype, int32_t N, int3
 int ssr_relu_maxpool2_bwd(ssr_view f, ssr_view gp, ssr_view gf, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C,
                           int32_t accumulate, void* stream);
 
+/* ---- Gram-matrix style term of the perceptual loss (csrc/gram.hip; PerceptualLoss with style_weight > 0, criterion 'l1':
+ *      l_g_style at ssr_esrgan_model.py:154-160) ----
+ * Features f are NHWC [N, HW, C] (HW = H*W pixels, C % 64 == 0); fp32 storage (SSR_F32 / SSR_F32X3) runs exact fp32 MFMA, SSR_BF16
+ * bf16 MFMA, both with fp32 accumulation.  Every result is run-to-run bit-identical (no float atomics outside ssr_gram_l1's
+ * non-deterministic loss sum).
+ * ssr_gram_splits: the pixel splits ssr_gram_fwd uses for this shape; ws must hold splits * N * C * C floats when splits > 1.
+ * ssr_gram_fwd: g[n] = scale * f[n]^T f[n], fp32 [N, C, C], exactly symmetric; the partial matrices of the splits (ws) are added
+ *   in split order.
+ * ssr_gram_l1: loss_out[0] += weight * sum |gx - gt| over n elements (SSR_DETERMINISTIC in dtype: per-block slots as ssr_l1_loss);
+ *   sgn (optional, element type = dtype) = sign(gx - gt), 0 where equal.
+ * ssr_gram_bwd: gf[n] (+)= coef * f[n] sgn[n] ([HW x C] x [C x C] per image; sgn symmetric, element type = dtype). */
+int ssr_gram_splits(int32_t N, int32_t HW, int32_t C);
+int ssr_gram_fwd(ssr_view f, float* g, float* ws, int32_t dtype, int32_t N, int32_t HW, int32_t C, float scale, void* stream);
+int ssr_gram_l1(const float* gx, const float* gt, void* sgn, int32_t dtype, int64_t n, float weight, float* loss_out, void* stream);
+int ssr_gram_bwd(ssr_view f, const void* sgn, ssr_view gf, int32_t dtype, int32_t N, int32_t HW, int32_t C, float coef,
+                 int32_t accumulate, void* stream);
+
 /* SSR_F32X3 weight gradients: split an fp32 buffer (n % 4 == 0 elements) into bf16 planes hi = bf16(x), lo = bf16(x - hi); the
  * bf16 wgrad kernel then accumulates (x_hi, dy_hi) + (x_hi, dy_lo) + (x_lo, dy_hi) into the fp32 gradient. */
 int ssr_split_bf16(const float* x, void* hi, void* lo, int64_t n, void* stream);

@@ -8,7 +8,7 @@
 
 Same registry name and the same `opt` dictionary (YAML) keys.  Instead of autograd over ~41k ATen ops per
 step, optimize_parameters() replays the fused HIP-graph step of train_step.ESRGANTrainStep.
-Scope: L1 + vanilla-GAN (+ VGG19 perceptual) losses, USM-sharpened ground truth, `feed_disc_lr`
+Scope: L1 + vanilla-GAN (+ VGG19 perceptual: feature and Gram-style terms) losses, USM-sharpened ground truth, `feed_disc_lr`
 and `old_hr` discriminator inputs.  Anything this path does not implement raises NotImplementedError naming the
 option (clip / ssim / ldl losses, other optimizers or schedulers, weight decay) — nothing is silently ignored."""
 from __future__ import annotations

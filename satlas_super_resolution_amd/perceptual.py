@@ -1,7 +1,7 @@
 """VGG19 perceptual loss on MI355X: forward of the feature extractor on the generator output and on the target, feature-L1
 losses, and the backward to the generator output — BasicSR's PerceptualLoss / VGGFeatureExtractor as configured by
 /root/reference/ssr/options/esrgan_s2naip_urban.yml:123-137 and called at /root/reference/ssr/models/ssr_esrgan_model.py:153-160
-(`l_g_percep, l_g_style = self.cri_perceptual(self.output, percep_gt)`; style_weight 0 -> no style term).
+(`l_g_percep, l_g_style = self.cri_perceptual(self.output, percep_gt)`).
 
 VGG19 (torchvision `features`, frozen): 16 3x3 convolutions + ReLU, 2x2 max-pool after conv1_2 / conv2_2 / conv3_4 / conv4_4; the
 loss reads the conv outputs BEFORE the ReLU.  The convolutions and their dgrads run on the conv kernels through the C ABI
@@ -9,6 +9,12 @@ loss reads the conv outputs BEFORE the ReLU.  The convolutions and their dgrads 
 pass over the stored pre-ReLU feature (csrc/vgg.hip).  Only dgrads are needed (the extractor's parameters are frozen).
 The gradient w.r.t. the generator output is ADDED to the L1-gradient buffer that the discriminator's input-gradient kernel
 already folds in (train_step._phase_g), so no extra pass over the 128x128 output exists.
+
+Style term (style_weight > 0, criterion 'l1'): per tapped layer the Gram matrices gram(F) = F^T F / (C*H*W) of the output's and the
+target's features (csrc/gram.hip, fp32 [N, C, C]), l_g_style = style_weight * sum_k w_k * mean|gram(Fx) - gram(Ft)|, and its feature
+gradient style_weight * w_k / (N*C^2) * 2/(C*H*W) * Fx sign(D) (D is symmetric) ADDED to the feature-L1 gradient of the layer before
+the dgrad chain.  The target side gets no gradient (gt.detach()).  perceptual_weight 0 with a style term: BasicSR's feature term is
+None, so the feature-L1 launches are skipped and only the style loss exists.
 
 Weights: torchvision's checkpoint layout (`features.{idx}.weight/bias`, e.g. vgg19-dcbb9e9d.pth; BasicSR's `vgg_net.` prefix is
 accepted too).  There is no network access here, so benchmarks and tests use random weights of the same architecture."""
@@ -68,24 +74,35 @@ def load_vgg19_state(path: str) -> Dict[str, torch.Tensor]:
     return {k[len("vgg_net."):] if k.startswith("vgg_net.") else k: v for k, v in sd.items() if "features." in k}
 
 
+def check_perceptual_opt(opt: Dict) -> None:
+    """The loss terms of `train.perceptual_opt` this library runs: criterion 'l1' for the feature and the style (Gram) terms."""
+    if opt.get("type", "PerceptualLoss") != "PerceptualLoss":
+        raise NotImplementedError(f"train.perceptual_opt.type={opt.get('type')!r}")
+    if opt.get("vgg_type", "vgg19") != "vgg19":
+        raise NotImplementedError(f"train.perceptual_opt.vgg_type={opt.get('vgg_type')!r}: only vgg19")
+    if opt.get("criterion", "l1") != "l1":
+        raise NotImplementedError(f"train.perceptual_opt.criterion={opt.get('criterion')!r}: only l1")
+    if float(opt.get("style_weight", 0)) < 0.0:
+        raise NotImplementedError(f"train.perceptual_opt.style_weight={opt.get('style_weight')!r}: BasicSR computes no style term below 0")
+
+
 class PerceptualPlan:
     """Static launch lists for one (B, H, W): `fwd_target` (features of the target, no activations kept), `fwd` (features of
     the generator output, activations kept), `bwd` (loss, feature gradients, dgrads down to the image)."""
 
     def __init__(self, opt: Dict, B: int, H: int, W: int, dtype: int, x_buf: torch.Tensor, tgt_buf: torch.Tensor,
                  grad_buf: torch.Tensor, loss_ptr: int, num_ch: int = 3, state: Optional[Dict[str, torch.Tensor]] = None,
-                 loss_flags: int = 0):
-        if opt.get("type", "PerceptualLoss") != "PerceptualLoss":
-            raise NotImplementedError(f"train.perceptual_opt.type={opt.get('type')!r}")
-        if opt.get("vgg_type", "vgg19") != "vgg19":
-            raise NotImplementedError(f"train.perceptual_opt.vgg_type={opt.get('vgg_type')!r}: only vgg19")
-        if float(opt.get("style_weight", 0)) != 0.0:
-            raise NotImplementedError("train.perceptual_opt.style_weight != 0 (Gram-matrix style loss)")
-        if opt.get("criterion", "l1") != "l1":
-            raise NotImplementedError(f"train.perceptual_opt.criterion={opt.get('criterion')!r}: only l1")
+                 loss_flags: int = 0, style_loss_ptr: int = 0):
+        check_perceptual_opt(opt)
         assert num_ch == 3 and H % 16 == 0 and W % 16 == 0, "VGG19 features need RGB images with H, W divisible by 16"
         self.layer_weights = {str(k): float(v) for k, v in opt["layer_weights"].items()}
         self.pw = float(opt.get("perceptual_weight", 1.0))
+        self.sw = float(opt.get("style_weight", 0.0))
+        self.style = self.sw > 0.0
+        # BasicSR's feature term is None at perceptual_weight 0 - with a style term only (no style term: launched as before)
+        self.feature = self.pw > 0.0 or not self.style
+        if self.style and not style_loss_ptr:
+            raise ValueError("PerceptualPlan: style_weight > 0 needs style_loss_ptr (the l_g_style slot)")
         names = [n for n, *_ in vgg19_layers()]
         for k in self.layer_weights:
             if k not in names:
@@ -169,14 +186,46 @@ class PerceptualPlan:
 
         self.fwd_target = forward(tgt_buf, feats_t)
         self.fwd = forward(x_buf, acts)
+        # ---- style term: Gram matrices of the target's features (fwd_target) and of the output's (fwd), then |D| and sign(D)
+        self.gram_x, self.gram_t, self.gram_s = {}, {}, {}
+        if self.style:
+            splits = {}
+            for name in self.layer_weights:
+                hh, ww = dims[name]
+                cout = acts[name].shape[-1]
+                splits[name] = lib.ssr_gram_splits(B, hh * ww, cout)
+                hip.check(min(splits[name], 0), f"ssr_gram_splits {name}")
+                self.gram_x[name] = torch.zeros(B, cout, cout, dtype=torch.float32, device=dev)
+                self.gram_t[name] = torch.zeros(B, cout, cout, dtype=torch.float32, device=dev)
+                self.gram_s[name] = z(B, cout, cout)            # sign(D) in the feature dtype (+-1 / 0: exact)
+            # one split-partial workspace for every Gram launch (they run in order on one stream)
+            ws_n = max([splits[k] * B * acts[k].shape[-1] ** 2 for k in splits if splits[k] > 1] or [1])
+            self.gram_ws = torch.zeros(ws_n, dtype=torch.float32, device=dev)
+            for name, wgt in self.layer_weights.items():
+                hh, ww = dims[name]
+                cout = acts[name].shape[-1]
+                gscale = 1.0 / (cout * hh * ww)
+                self.fwd_target.add(lib.ssr_gram_fwd, view(feats_t[name]), self.gram_t[name].data_ptr(), self.gram_ws.data_ptr(), dtype, B,
+                                    hh * ww, cout, gscale, what=f"gram target {name}")
+                self.fwd.add(lib.ssr_gram_fwd, view(acts[name]), self.gram_x[name].data_ptr(), self.gram_ws.data_ptr(), dtype, B, hh * ww,
+                             cout, gscale, what=f"gram {name}")
+                # l_g_style += sw * w_k * mean|Gx - Gt|
+                self.fwd.add(lib.ssr_gram_l1, self.gram_x[name].data_ptr(), self.gram_t[name].data_ptr(), self.gram_s[name].data_ptr(),
+                             dtype | loss_flags, B * cout * cout, self.sw * wgt / (B * cout * cout), style_loss_ptr, what=f"gram L1 {name}")
         # ---- backward: losses + feature gradients, then dgrads from the last layer down to the image
         Bk = engine.Launcher()
         for name, wgt in self.layer_weights.items():
             hh, ww = dims[name]
             cout = acts[name].shape[-1]
             # loss += w_k * pw * mean|Fx - Ft| ; g_F = w_k * pw * sign(Fx - Ft) / numel
-            Bk.add(lib.ssr_l1_loss, view(acts[name]), view(feats_t[name]), view(g_acts[name]), dtype | loss_flags, B * hh * ww, cout, wgt * self.pw,
-                   loss_ptr, what=f"feature L1 {name}")
+            if self.feature:
+                Bk.add(lib.ssr_l1_loss, view(acts[name]), view(feats_t[name]), view(g_acts[name]), dtype | loss_flags, B * hh * ww, cout,
+                       wgt * self.pw, loss_ptr, what=f"feature L1 {name}")
+            if self.style:
+                # g_F (+)= sw * w_k / (N C^2) * 2 / (C H W) * Fx sign(D)
+                coef = self.sw * wgt / (B * cout * cout) * 2.0 / (cout * hh * ww)
+                Bk.add(lib.ssr_gram_bwd, view(acts[name]), self.gram_s[name].data_ptr(), view(g_acts[name]), dtype, B, hh * ww, cout, coef,
+                       1 if self.feature else 0, what=f"gram bwd {name}")
         for li in reversed(range(len(layers))):
             name, idx, cin, cout, pooled_before = layers[li]
             hh, ww = dims[name]

@@ -154,7 +154,8 @@ class ESRGANTrainStep:
                 from .perceptual import PerceptualPlan
                 self.p_plan = PerceptualPlan(cfg.perceptual, B, H, W, self.mode, self.fake_in, self.percep_tgt, self.grad_l1,
                                              self.losses.data_ptr() + 4 * 6 * self.loss_stride, num_ch=cout, state=vgg_state,
-                                             loss_flags=self.loss_dt & hip.DETERMINISTIC)
+                                             loss_flags=self.loss_dt & hip.DETERMINISTIC,
+                                             style_loss_ptr=self.losses.data_ptr() + 4 * 7 * self.loss_stride)   # l_g_style: slot 7
                 self.p_plan.pack()
             self.opt_g = AdamState(self.g_store, cfg.lr_g, cfg.betas, cfg.eps, cfg.ema_decay)
             self.opt_d = AdamState(self.d_store, cfg.lr_d, cfg.betas_d or cfg.betas, cfg.eps, 0.0)
@@ -447,8 +448,10 @@ class ESRGANTrainStep:
         scal = self.losses if not self.det else self.losses.view(8, self.loss_stride).double().cpu().sum(1).float().to(self.losses.device)
         vals = self.dp.reduce_scalars(scal).tolist()      # det: the per-block slots added in index order on the host
         out = OrderedDict((k, vals[i]) for i, k in enumerate(LOSS_KEYS))
-        if self.p_plan is not None:
+        if self.p_plan is not None and self.p_plan.feature:
             out["l_g_percep"] = vals[6]
+        if self.p_plan is not None and self.p_plan.style:      # ssr_esrgan_model.py:157-160
+            out["l_g_style"] = vals[7]
         return out
 
     def output(self) -> torch.Tensor:
