@@ -15,11 +15,14 @@ A "step" = one full optimize_parameters(): G fwd+bwd+Adam+EMA, 3 D forwards (+3 
 iterations), D dgrad-only bwd + 2 full D bwd, Adam — nothing skipped.  Inputs are synthetic random
 S2/NAIP tensors already resident in HBM; weights are random-init of the named architecture.
 
-One JSON line on rank 0.  `roofline` is for the dominant kernel symbol (by GPU time inside one
-instrumented step): algorithmic conv FLOPs of its launches / their summed duration, measured with
-events on the launch stream; `cpu_baseline` is the oracle (CPU restatement of the reference step,
-oracle/esrgan_oracle.py) timed on this host's cores on a bounded sample.
-`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see step_outputs).
+One JSON line on rank 0.  A plain run does only what the headline needs: set up, warm up, time the K steps,
+write the outputs (`--dump-outputs DIR`: what the last timed step computed as DIR/<name>.npy, see step_outputs) and
+print the line.  `--full` adds everything else the benchmark measures, in the same process after the timed steps:
+further timed blocks (`ms_per_step_blocks`), the host cost of one step under data parallelism, `roofline` for the
+dominant kernel symbol (by GPU time inside one instrumented step: algorithmic conv FLOPs of its launches / their
+summed duration, measured with events on the launch stream), the other arithmetic modes as `legs` with their error
+against the CPU oracle, and `cpu_baseline`: the oracle (CPU restatement of the reference step, oracle/esrgan_oracle.py)
+timed on this host's cores on a bounded sample.
 """
 import argparse
 import json
@@ -45,7 +48,7 @@ def parse():
                     help="arithmetic mode of the headline line.  Default fp32h (round 6): the fastest mode inside EVERY gate of the reference "
                          "(outputs and parameter gradients at 1e-3; the reference computes in fp32) - fp16-split forward, split-bf16 backward; "
                          "fp32x3 (outputs only), bf16 (throughput mode, outside the gate), fp32f and exact fp32 are reported as `legs` of the "
-                         "same run, timed the same way")
+                         "same run, timed the same way (--full)")
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch (configs[2]: 32; configs[1]: 16)")
     ap.add_argument("--frames", type=int, default=8, help="Sentinel-2 frames (x3 RGB channels); configs[2]: 8, configs[1]: 1")
     ap.add_argument("--feed-disc-lr", action="store_true")
@@ -54,6 +57,10 @@ def parse():
                          "no network here) — NOT part of the headline metric's FLOP model (SURVEY.md 8d), reported as its own workload")
     ap.add_argument("--blocks", type=int, default=23)
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: further timed blocks, the roofline and "
+                         "per-kernel times of an instrumented step, the other arithmetic modes (legs) with their error against the CPU "
+                         "oracle, and the CPU baseline; the --no-* / --cpu-* / --blocks-timed / --leg-steps options below shape these parts")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=4)
@@ -597,7 +604,8 @@ def main():
         dumped = step_outputs(ts)
         if ctx.rank == 0:
             write_outputs(dumped, args.dump_outputs)
-    if dp_diag is not None:
+    # everything below the dump that runs the device again is --full: a plain run only reads the losses and prints the line
+    if dp_diag is not None and args.full:
         # host cost of ONE step with an empty queue (inside the timed loop the host runs ahead until the launch queue pushes back: the
         # loop's enqueue time then measures the DEVICE): sync, enqueue one step, read the clock - median of five
         one = []
@@ -617,7 +625,7 @@ def main():
     # beside the contract's single timed region: further blocks of the same K steps, median reported (boxes differ by a few %
     # and a 0.3 s region sees clock ramps)
     blocks = []
-    for _ in range(max(0, args.blocks_timed)):
+    for _ in range(max(0, args.blocks_timed) if args.full else 0):
         ctx.barrier()
         torch.cuda.synchronize()
         tb = time.perf_counter()
@@ -652,14 +660,15 @@ def main():
         "step_tflops": value * gflop_img / 1e3,
         "frac_of_mfma_peak_whole_step": value * gflop_img / 1e3 / (PEAK_TFLOPS[args.dtype] * ctx.world),
         "losses_finite": finite,
-        "ms_per_step_blocks": [round(b, 4) for b in blocks],
-        "ms_per_step_median_of_blocks": (sorted(blocks)[len(blocks) // 2] if blocks else None),
     }
+    if args.full:
+        out["ms_per_step_blocks"] = [round(b, 4) for b in blocks]
+        out["ms_per_step_median_of_blocks"] = sorted(blocks)[len(blocks) // 2] if blocks else None
     if dp_diag is not None:
         out["dp"] = dp_diag
     # the instrumented step contains the gradient exchanges: every rank runs it (collectives must match), rank 0 reports
     agg, twin = None, False
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         def build():
             tw = ESRGANTrainStep(g_kw, d_kw, B, 32, 32, args.dtype, StepConfig(feed_disc_lr=args.feed_disc_lr, perceptual=percep, deterministic=not args.no_deterministic), dp=ctx,
                                  use_graph=False, vgg_state=vgg_state)
@@ -671,7 +680,8 @@ def main():
         agg = instrumented_step(ts_r, args)
         if twin:
             del ts_r
-    trace("instrumented step done")
+    if agg is not None:
+        trace("instrumented step done")
     if ctx.rank == 0 and agg is not None:
         dom, roof0 = roofline_of(agg, args.dtype)
         roof0["measured_on"] = ("unsplit twin of the step (full-batch launches; the step itself runs the generator as two half-batch chains that share the chip)"
@@ -715,7 +725,7 @@ def main():
     if ctx.rank == 0:
         out["arithmetic"] = ARITH[args.dtype]
         out["gate"] = GATE[args.dtype]
-    if ctx.world == 1 and not args.no_parity_mode and args.blocks == 23 and not args.perceptual:
+    if args.full and ctx.world == 1 and not args.no_parity_mode and args.blocks == 23 and not args.perceptual:
         del ts
         import gc
         gc.collect()
@@ -748,7 +758,7 @@ def main():
             out["value_all_gates"] = {"mode": best, "value": full[best]["value"], "unit": "images/s", "ms_per_step": full[best]["ms_per_step"],
                                       "note": "fastest arithmetic mode whose outputs AND parameter gradients are inside the 1e-3 gate unconditionally"
                                               + (" = the headline mode" if best == args.dtype else "; the headline `value` is the mode --dtype names (see gate)")}
-    if ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
+    if args.full and ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, c_in, c_d)
     # the process group goes first: whatever the backend writes while it shuts down, the JSON line stays the LAST line of stdout
     if ctx.active:

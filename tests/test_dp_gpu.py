@@ -114,7 +114,7 @@ def test_dp_shared_gpu_matches_full_batch_oracle(tmp_path, world):
 @pytest.mark.gpu
 @pytest.mark.parametrize("world", [2, 4])
 def test_bench_n_ranks_on_one_gpu_prints_one_json_line(world):
-    """`bench.py --gpus N` as the driver launches it (torch.distributed.run, one process per rank), with all ranks on
+    """`bench.py --gpus N --full` as the driver launches it (torch.distributed.run, one process per rank), with all ranks on
     cuda:0 and gloo standing in for RCCL: every rank must take part in every collective — the timed steps, the max-over-
     ranks reduction AND the instrumented roofline step — and rank 0 alone prints the JSON line."""
     import json
@@ -124,7 +124,7 @@ def test_bench_n_ranks_on_one_gpu_prints_one_json_line(world):
     env = dict(os.environ, SSR_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "2",
-           "--batch", "2", "--blocks", "1", "--no-cpu-baseline", "--blocks-timed", "1"]
+           "--batch", "2", "--blocks", "1", "--full", "--no-cpu-baseline", "--blocks-timed", "1"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

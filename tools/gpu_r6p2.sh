@@ -5,4 +5,4 @@ for r in 1 2; do
     echo -n "$v  "; env $v python bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-roofline --no-legs 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(round(d['value'],1), round(d['ms_per_step'],3))"
   done
 done
-SSR_X3_BIGTILE2=2 python bench.py --no-cpu-baseline --no-legs --blocks-timed 1 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(json.dumps(d['kernel_time_breakdown_ms']))"
+SSR_X3_BIGTILE2=2 python bench.py --full --no-cpu-baseline --no-legs --blocks-timed 1 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(json.dumps(d['kernel_time_breakdown_ms']))"

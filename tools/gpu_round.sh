@@ -1,5 +1,5 @@
 #!/bin/bash
-# One GPU-box visit: the whole -m gpu suite, HBM-traffic PMC passes (the headline mode - HEAD_DTYPE, default fp32h - + the bf16 / fp32 legs), the default bench
+# One GPU-box visit: the whole -m gpu suite, HBM-traffic PMC passes (the headline mode - HEAD_DTYPE, default fp32h - + the bf16 / fp32 legs), the --full bench
 # line (which then carries roofline.traffic for this very build), rocprofv3 kernel stats of the headline mode (overlapped and serial),
 # SQ/GRBM counters, and the other BASELINE.json configurations.
 #   gpurun --timeout 2400 -- 'bash tools/gpu_round.sh r05z'
@@ -41,7 +41,7 @@ if [ "${SKIP_LEG_TRAFFIC:-0}" != "1" ]; then  # the parity legs' dominant kernel
   done
 fi
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-python bench.py ${BENCH_ARGS:-} > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "bench rc=$?"; tail -1 $O/${TAG}_bench.json | cut -c1-1200
+python bench.py --full ${BENCH_ARGS:-} > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "bench rc=$?"; tail -1 $O/${TAG}_bench.json | cut -c1-1200
 if [ "${SKIP_PROF:-0}" != "1" ]; then
   (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -o k -- python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --blocks-timed 0 --no-legs > /tmp/prof_$TAG.log 2>&1)
   F=$(find /tmp/prof_$TAG -name '*kernel_stats.csv' | head -1); [ -n "$F" ] && cp $F $O/${TAG}_kernel_stats.csv && head -8 $F | cut -c1-160
@@ -57,7 +57,7 @@ if [ "${SKIP_DP:-0}" != "1" ]; then           # the data-parallel branch over RC
   : > $O/${TAG}_dp_world1.jsonl
   for OG in 0 1; do for ALGO in allreduce rsag; do
     SSR_DP_FORCE=1 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=$((29500 + OG * 2 + ${#ALGO})) SSR_DP_ONE_GRAPH=$OG SSR_DP_ALGO=$ALGO \
-      python bench.py --no-cpu-baseline --no-legs --no-roofline --blocks-timed 2 2>/dev/null | tail -1 >> $O/${TAG}_dp_world1.jsonl
+      python bench.py --full --no-cpu-baseline --no-legs --no-roofline --blocks-timed 2 2>/dev/null | tail -1 >> $O/${TAG}_dp_world1.jsonl
   done; done
   python -c "
 import json
@@ -67,9 +67,9 @@ fi
 if [ "${SKIP_CONFIGS:-0}" != "1" ]; then      # the other BASELINE.json configurations on this build, one JSON line each
   : > $O/${TAG}_bench_configs.jsonl
   for ARGS in "--frames 1 --batch 16" "--frames 32 --batch 16" "--feed-disc-lr" "--perceptual" "--dtype fp32x3" "--dtype fp32x3 --frames 1 --batch 16" "--dtype bf16" "--dtype bf16 --frames 1 --batch 16" "--dtype bf16 --frames 32 --batch 16" "--dtype fp32f" "--dtype fp32"; do
-    SSR_VGG19_RANDOM=1 python bench.py $ARGS --no-cpu-baseline --no-legs 2>/dev/null | tail -1 >> $O/${TAG}_bench_configs.jsonl
+    SSR_VGG19_RANDOM=1 python bench.py $ARGS --full --no-cpu-baseline --no-legs 2>/dev/null | tail -1 >> $O/${TAG}_bench_configs.jsonl
   done
-  SSR_DETERMINISTIC=1 python bench.py --no-cpu-baseline --no-legs 2>/dev/null | tail -1 | python -c "
+  SSR_DETERMINISTIC=1 python bench.py --full --no-cpu-baseline --no-legs 2>/dev/null | tail -1 | python -c "
 import sys, json; d = json.loads(sys.stdin.read()); d['config']['deterministic'] = True; print(json.dumps(d))" >> $O/${TAG}_bench_configs.jsonl
   python -c "
 import json

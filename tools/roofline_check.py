@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Recompute bench.py's roofline fraction from the committed rocprofv3 summary, no decoder ring:
+"""Recompute the roofline fraction of a `bench.py --full` line from the committed rocprofv3 summary, no decoder ring:
 
     python tools/roofline_check.py profiles/r06x_bench.json profiles/r06x_kernel_stats_serial.csv [steps_profiled] > profiles/r06x_roofline_check.txt
 
