@@ -378,6 +378,17 @@ int ssr_adam_step(const ssr_adam_args* a, void* stream);
 /* y = a*x + b*y over n fp32 elements (grad averaging / accumulation helpers) */
 int ssr_axpby_f32(float a, const float* x, float b, float* y, int64_t n, void* stream);
 
+/* ---- non-finite guard of the optimizer step (csrc/finite.hip) ----
+ * ssr_nonfinite_scan: *flag = 1 if any element of the n_ranges (1..SSR_SCAN_MAX_RANGES) fp32 ranges srcs[k][0, ns[k]) is NaN or +-Inf
+ *   (a bit test on the exponent).  The flag is only ever set, never cleared: the caller starts it at 0.  srcs / ns are host arrays;
+ *   every pointer 4-byte aligned, ns[k] >= 0 (0: nothing to scan).  SSR_EINVAL without a launch otherwise.
+ * ssr_adam_step_guarded: reads *flag on the device.  0: exactly ssr_adam_step (same arithmetic, *step += 1).  Non-zero: param, exp_avg,
+ *   exp_avg_sq and *step are left as they are, the EMA (if any) still gets ema = ema*decay + p*(1-decay) from the unchanged p, and
+ *   *skipped += 1.  *flag is 0 afterwards either way.  No host synchronisation: a step with both launches is capturable. */
+#define SSR_SCAN_MAX_RANGES 8
+int ssr_nonfinite_scan(const float* const* srcs, const int64_t* ns, int32_t n_ranges, int32_t* flag, void* stream);
+int ssr_adam_step_guarded(const ssr_adam_args* a, int32_t* flag, int32_t* skipped, void* stream);
+
 /* ---- image quantisation and validation metrics (csrc/metrics.hip) ----
  * ssr_quantize_u8: fp32 NCHW -> uint8 NHWC, clamp(0,1) * 255 then mode 0: round half to even (basicsr tensor2img as called at
  *   /root/reference/ssr/models/ssr_esrgan_model.py:302-305), mode 1: truncate (astype(uint8) at /root/reference/ssr/infer_grid.py:60-64,
@@ -389,6 +400,10 @@ int ssr_axpby_f32(float a, const float* x, float b, float* y, int64_t n, void* s
  * ssr_metric_ssim_sums: out[c] = sum over the valid region of the SSIM map of channel c (11x11 Gaussian window, sigma 1.5, fp64;
  *   basicsr calculate_ssim); the caller divides by (H-2*crop-10)*(W-2*crop-10). */
 int ssr_quantize_u8(const float* src_nchw, uint8_t* dst_nhwc, int32_t N, int32_t C, int32_t H, int32_t W, int32_t mode, void* stream);
+/* ssr_quantize_u8 that also adds the number of NaN / +-Inf samples of src into the device counter *nonfinite in the same pass (one
+ * atomic per wave; the caller zeroes the counter).  The bytes it writes are ssr_quantize_u8's. */
+int ssr_quantize_u8_checked(const float* src_nchw, uint8_t* dst_nhwc, int32_t N, int32_t C, int32_t H, int32_t W, int32_t mode,
+                            int32_t* nonfinite, void* stream);
 int ssr_metric_shift_sums(const uint8_t* a, const uint8_t* b, int32_t H, int32_t W, int32_t C, int32_t crop, int32_t max_offset,
                           int64_t* out, void* stream);
 int ssr_metric_ssim_sums(const uint8_t* a, const uint8_t* b, int32_t H, int32_t W, int32_t C, int32_t crop, double* out, void* stream);

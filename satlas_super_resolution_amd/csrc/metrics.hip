@@ -12,9 +12,13 @@
 
 namespace {
 
+// COUNT (ssr_quantize_u8_checked): also add the number of NaN / +-Inf samples (exponent bits all ones) into *nonfinite, one atomic
+// per wave that saw any
+template <bool COUNT>
 __global__ __launch_bounds__(256) void quantize_u8_kernel(const float* __restrict__ src, uint8_t* __restrict__ dst, int N, int C,
-                                                          int H, int W, int mode) {
+                                                          int H, int W, int mode, int32_t* __restrict__ nonfinite) {
     const long total = (long)N * H * W * C;
+    int bad = 0;
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const int c = (int)(e % C);
         long q = e / C;
@@ -22,8 +26,14 @@ __global__ __launch_bounds__(256) void quantize_u8_kernel(const float* __restric
         const int y = (int)(q % H);
         const int n = (int)(q / H);
         float v = src[(((long)n * C + c) * H + y) * W + x];
+        if constexpr (COUNT) bad += (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
         v = fminf(fmaxf(v, 0.f), 1.f) * 255.0f;            // clamp(0,1) then * 255 in fp32 (NaN -> 0 via fmaxf)
         dst[e] = (uint8_t)(mode == 0 ? rintf(v) : v);       // np.round = half-to-even | astype(uint8) = truncation
+    }
+    if constexpr (COUNT) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) bad += __shfl_down(bad, o, 64);
+        if ((threadIdx.x & 63) == 0 && bad) atomicAdd(nonfinite, bad);
     }
 }
 
@@ -113,7 +123,18 @@ extern "C" int ssr_quantize_u8(const float* src, uint8_t* dst, int32_t N, int32_
     const long total = (long)N * C * H * W;
     long g = (total + 255) / 256;
     if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(quantize_u8_kernel, dim3((int)g), dim3(256), 0, ST(stream), src, dst, N, C, H, W, mode);
+    hipLaunchKernelGGL(quantize_u8_kernel<false>, dim3((int)g), dim3(256), 0, ST(stream), src, dst, N, C, H, W, mode, nullptr);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_quantize_u8_checked(const float* src, uint8_t* dst, int32_t N, int32_t C, int32_t H, int32_t W, int32_t mode,
+                                       int32_t* nonfinite, void* stream) {
+    if (!src || !dst || !nonfinite || N <= 0 || C <= 0 || H <= 0 || W <= 0 || (mode != 0 && mode != 1)) return SSR_EINVAL;
+    const long total = (long)N * C * H * W;
+    long g = (total + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(quantize_u8_kernel<true>, dim3((int)g), dim3(256), 0, ST(stream), src, dst, N, C, H, W, mode, nonfinite);
     SSR_LAUNCH_CHECK();
     return SSR_OK;
 }

@@ -2,6 +2,7 @@
 // bilinear/nearest x2 (backward), spectral norm, losses, fused Adam+EMA.  All are coalesced over the
 // channel (fastest NHWC) axis; reductions are wave-shuffle (64 lanes) -> LDS -> one atomic per block.
 #include "common.h"
+#include "adam.h"
 #include <cstdlib>
 
 namespace {
@@ -698,26 +699,7 @@ __global__ __launch_bounds__(256) void bce_loss_kernel(ssr_view x, ssr_view grad
 // ------------------------------------------------------------------------------------------------
 // Adam (torch.optim.Adam single-tensor math) + EMA, one launch per flat arena
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void adam_kernel(const ssr_adam_args a) {
-    const int t = a.step[0] + 1;
-    const float lr = a.lr[0];
-    const float bc1 = 1.f - powf(a.beta1, (float)t);
-    const float bc2 = 1.f - powf(a.beta2, (float)t);
-    const float step_size = lr / bc1;
-    const float bc2_sqrt = sqrtf(bc2);
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < a.n; e += (long)gridDim.x * blockDim.x) {
-        const float g = a.grad[e] * a.grad_scale;
-        float m = a.exp_avg[e], v = a.exp_avg_sq[e];
-        m = m + (g - m) * (1.f - a.beta1);                 // exp_avg.lerp_(grad, 1 - beta1)
-        v = v * a.beta2 + (1.f - a.beta2) * g * g;         // mul_(beta2).addcmul_(g, g, 1 - beta2)
-        const float denom = sqrtf(v) / bc2_sqrt + a.eps;
-        const float p = a.param[e] - step_size * (m / denom);
-        a.exp_avg[e] = m;
-        a.exp_avg_sq[e] = v;
-        a.param[e] = p;
-        if (a.ema) a.ema[e] = a.ema[e] * a.ema_decay + p * (1.f - a.ema_decay);
-    }
-}
+__global__ __launch_bounds__(256) void adam_kernel(const ssr_adam_args a) { adam_update(a); }   // csrc/adam.h
 __global__ void bump_kernel(int32_t* step) { step[0] += 1; }
 
 __global__ __launch_bounds__(256) void axpby_kernel(float a, const float* __restrict__ x, float b,

@@ -125,8 +125,10 @@ ABI_SYMBOLS = [
     "ssr_spectral_norm_bwd", "ssr_usm_sharp", "ssr_l1_loss", "ssr_bce_logits_loss", "ssr_adam_step", "ssr_axpby_f32",
     "ssr_quantize_u8", "ssr_metric_shift_sums", "ssr_metric_ssim_sums", "ssr_split_bf16", "ssr_split_bf16_multi", "ssr_channel_affine", "ssr_relu_maxpool2_fwd", "ssr_relu_maxpool2_bwd",
     "ssr_gram_splits", "ssr_gram_fwd", "ssr_gram_l1", "ssr_gram_bwd",
+    "ssr_nonfinite_scan", "ssr_adam_step_guarded", "ssr_quantize_u8_checked",
     "ssr_device_info", "ssr_abi_version",
 ]
+SCAN_MAX_RANGES = 8           # SSR_SCAN_MAX_RANGES: ranges per ssr_nonfinite_scan call
 
 _lib: Optional[C.CDLL] = None
 
@@ -193,6 +195,9 @@ def lib() -> C.CDLL:
     l.ssr_gram_fwd.argtypes = [View, vp, vp, i32, i32, i32, i32, f32, vp]
     l.ssr_gram_l1.argtypes = [vp, vp, vp, i32, i64, f32, vp, vp]
     l.ssr_gram_bwd.argtypes = [View, vp, View, i32, i32, i32, i32, f32, i32, vp]
+    l.ssr_nonfinite_scan.argtypes = [C.POINTER(vp), C.POINTER(i64), i32, vp, vp]
+    l.ssr_adam_step_guarded.argtypes = [C.POINTER(AdamArgs), vp, vp, vp]
+    l.ssr_quantize_u8_checked.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
     l.ssr_device_info.argtypes = [C.c_char_p, i32]
     l.ssr_abi_version.argtypes = []
     for s in ABI_SYMBOLS:

@@ -165,19 +165,22 @@ def run_infer_grid(opt: Dict, model: Optional[Callable[[torch.Tensor], torch.Ten
                     firsts.append(np.array(first))
             return firsts, dst
 
+        compute_dtype = getattr(model, "compute_dtype", None)
+
         def launch(sel):
-            """enqueue upload, formatting, generator, truncating uint8 and the download of one batch; nothing waits here"""
+            """enqueue upload, formatting, generator, truncating uint8 and the download of one batch; nothing waits here.  The count of
+            non-finite outputs (ssr_quantize_u8_checked) sits behind the image in the same device buffer and comes down with it."""
             with torch.no_grad():
                 y = model(frames_to_input(sel.to(device, non_blocking=True)))
                 if not on_gpu:
-                    return quantize_output(y), None
-                from .metrics import tensor2img_u8
-                yq = tensor2img_u8(y.detach(), truncate=True)
-                yh = torch.empty(yq.shape, dtype=torch.uint8, pin_memory=True)
-                yh.copy_(yq, non_blocking=True)
+                    return quantize_output(y, compute_dtype), None
+                from .metrics import quantize_u8_checked
+                buf, shape = quantize_u8_checked(y.detach(), truncate=True)
+                bh = torch.empty(buf.shape, dtype=torch.uint8, pin_memory=True)
+                bh.copy_(buf, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record()
-                return yh, ev
+                return (bh, shape), ev
 
         # software pipeline over the batches: the files of batches g + 1 and g + 2 are being decoded while the device runs batch g and
         # this thread picks the frames of batch g + 1; batch g's chunks go to the encoders (through an output block) as soon as its
@@ -201,6 +204,11 @@ def run_infer_grid(opt: Dict, model: Optional[Callable[[torch.Tensor], torch.Ten
             yh, ev = pending
             if ev is not None:
                 ev.synchronize()
+                from .metrics import nonfinite_error, split_checked
+                yh, bad = split_checked(*yh)
+                if bad:       # before any PNG of the batch is encoded
+                    names = sorted({pngs[i].split("/")[-2] for i in idxs})
+                    raise nonfinite_error(bad, compute_dtype, f" in the batch of tile(s) {', '.join(names)}")
                 yh = yh.numpy()
             t3 = _time.perf_counter()
             ob = g % NOUT

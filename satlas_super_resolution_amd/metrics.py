@@ -12,8 +12,16 @@ import torch
 from . import hip
 
 
-def tensor2img_u8(x: torch.Tensor, truncate: bool = False) -> torch.Tensor:
-    """float32 NCHW on the device -> uint8 NHWC on the device.  truncate=True is the astype(uint8) of infer_grid.py:60-64."""
+def tensor2img_u8(x: torch.Tensor, truncate: bool = False, check_finite: bool = False, compute_dtype=None) -> torch.Tensor:
+    """float32 NCHW on the device -> uint8 NHWC on the device.  truncate=True is the astype(uint8) of infer_grid.py:60-64.
+    check_finite=True: count NaN / +-Inf samples in the same pass and raise FloatingPointError (naming `compute_dtype`) if there
+    are any, instead of returning the pixels they were clamped to (one read of the counter: a device sync)."""
+    if check_finite:
+        buf, shape = quantize_u8_checked(x, truncate)
+        img, bad = split_checked(buf, shape)
+        if bad:
+            raise nonfinite_error(bad, compute_dtype)
+        return img
     x = x.contiguous().float()
     assert x.is_cuda and x.dim() == 4
     n, c, h, w = x.shape
@@ -21,6 +29,37 @@ def tensor2img_u8(x: torch.Tensor, truncate: bool = False) -> torch.Tensor:
     hip.check(hip.lib().ssr_quantize_u8(x.data_ptr(), out.data_ptr(), n, c, h, w, 1 if truncate else 0, hip.stream_ptr()),
               "ssr_quantize_u8")
     return out
+
+
+def quantize_u8_checked(x: torch.Tensor, truncate: bool = False):
+    """ssr_quantize_u8_checked: -> (one flat uint8 device buffer holding the NHWC image and, at the next 4-byte boundary, the int32
+    count of non-finite input samples; the image shape).  One copy of the buffer brings both to the host (split_checked)."""
+    x = x.contiguous().float()
+    assert x.is_cuda and x.dim() == 4
+    n, c, h, w = x.shape
+    off = -(-n * h * w * c // 4) * 4
+    buf = torch.empty(off + 4, dtype=torch.uint8, device=x.device)
+    cnt = buf[off:].view(torch.int32)
+    cnt.zero_()
+    hip.check(hip.lib().ssr_quantize_u8_checked(x.data_ptr(), buf.data_ptr(), n, c, h, w, 1 if truncate else 0, cnt.data_ptr(),
+                                                 hip.stream_ptr()), "ssr_quantize_u8_checked")
+    return buf, (n, h, w, c)
+
+
+def split_checked(buf: torch.Tensor, shape):
+    """a buffer of quantize_u8_checked (on the device or copied to the host) -> (uint8 image view [N, H, W, C], non-finite count)"""
+    nb = math.prod(shape)
+    off = -(-nb // 4) * 4
+    return buf[:nb].view(shape), int(buf[off:off + 4].view(torch.int32)[0])
+
+
+def nonfinite_error(count: int, compute_dtype=None, where: str = "") -> FloatingPointError:
+    """what inference / validation raise instead of writing pixels derived from NaN / Inf"""
+    msg = f"{count} non-finite output sample(s){where}" + (f" in compute_dtype {compute_dtype}" if compute_dtype is not None else "")
+    if compute_dtype == "fp32h":
+        msg += (": fp32h runs the forward convolutions on fp16-split operands (|activation| < 65504, |weight| < 64); "
+                "set `compute_dtype: fp32f` (exact fp32 forward, same gates) for this model")
+    return FloatingPointError(msg)
 
 
 def _pair(a, b):

@@ -120,7 +120,7 @@ class SSRESRGANModel:
         carry = None
         if old is not None:     # a ragged last batch / another tile size: carry every piece of state over, then free the old step
             carry = dict(g=old.g_store.state_dict(), d=old.d_store.state_dict(),
-                         opt=[(o.exp_avg.clone(), o.exp_avg_sq.clone(), o.step.clone()) for o in (old.opt_g, old.opt_d)],
+                         opt=[(o.exp_avg.clone(), o.exp_avg_sq.clone(), o.step.clone(), o.skipped.clone()) for o in (old.opt_g, old.opt_d)],
                          ema=None if old.opt_g.ema is None else old.opt_g.ema.clone(), it=old.iter)
             del old
             import gc
@@ -131,8 +131,8 @@ class SSRESRGANModel:
             self._init_params()
         else:
             self.ts.load_state(carry["g"], carry["d"], reset_ema=False)
-            for o, (m, v, s) in zip((self.ts.opt_g, self.ts.opt_d), carry["opt"]):
-                o.exp_avg.copy_(m); o.exp_avg_sq.copy_(v); o.step.copy_(s)
+            for o, (m, v, s, k) in zip((self.ts.opt_g, self.ts.opt_d), carry["opt"]):
+                o.exp_avg.copy_(m); o.exp_avg_sq.copy_(v); o.step.copy_(s); o.skipped.copy_(k)
             if carry["ema"] is not None:
                 self.ts.opt_g.ema.copy_(carry["ema"])
             self.ts.iter = carry["it"]
@@ -205,9 +205,17 @@ class SSRESRGANModel:
         # the fp16-split forward of mode fp32h has fp16's range (include/ssr_hip.h, SSR_F32H): an activation beyond 65504 turns into NaN outputs.
         # The losses are read from the device here anyway: say what to do instead of logging NaN silently
         if self.compute_dtype == "fp32h" and any(isinstance(v, float) and not math.isfinite(v) for v in self.log_dict.values()):
+            kept = (" Updates with non-finite gradients are skipped on the device: weights, Adam moments and step counts were left unchanged "
+                    f"(skipped so far: {self.nonfinite_skips}).") if self.ts.nonfinite_guard else ""
             raise FloatingPointError("non-finite loss in compute_dtype fp32h: its forward convolutions run on fp16-split operands (|activation| < 65504, "
-                                     "|weight| < 64); set `compute_dtype: fp32f` (exact fp32 forward, same gates) for this model")
+                                     "|weight| < 64); set `compute_dtype: fp32f` (exact fp32 forward, same gates) for this model." + kept)
         return self.log_dict
+
+    @property
+    def nonfinite_skips(self) -> dict:
+        """updates skipped by the non-finite guard so far, per network (ESRGANTrainStep.nonfinite_skips; one device read)"""
+        g, d = self.ts.nonfinite_skips() if self.ts is not None else (0, 0)
+        return {"net_g": g, "net_d": d}
 
     def update_learning_rate(self, current_iter: int, warmup_iter: int = -1):
         """BasicSR BaseModel.update_learning_rate: the schedulers are stepped once per call from the second call on
@@ -369,7 +377,8 @@ class SSRESRGANModel:
             for idx, val_data in enumerate(dataloader):
                 self.feed_data(val_data)
                 self.test()
-                sr = M.tensor2img_u8(self.output)                 # [B,H,W,3] uint8 RGB on the device (tensor2img: clamp, *255, round)
+                # [B,H,W,3] uint8 RGB on the device (tensor2img: clamp, *255, round); raises instead of scoring NaN-derived pixels
+                sr = M.tensor2img_u8(self.output, check_finite=True, compute_dtype=self.compute_dtype)
                 gt = M.tensor2img_u8(self.gt) if self.gt is not None else None
                 if save_img:
                     vis = self.opt.get("path", {}).get("visualization", "experiments/visualization")

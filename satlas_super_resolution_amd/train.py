@@ -47,6 +47,7 @@ def train(opt: Dict, max_iters: Optional[int] = None, resume_state: Optional[Dic
         log(f"Resuming training from epoch: {epoch}, iter: {current_iter}.")
     logger_opt = opt.get("logger", {})
     t0, seen = time.time(), 0
+    last_skips = {"net_g": 0, "net_d": 0}
     while current_iter < total_iters:
         if hasattr(loader.sampler, "set_epoch"):
             loader.sampler.set_epoch(epoch)
@@ -59,6 +60,10 @@ def train(opt: Dict, max_iters: Optional[int] = None, resume_state: Optional[Dic
             model.optimize_parameters(current_iter)
             seen += batch["lr"].shape[0]
             if current_iter % int(logger_opt.get("print_freq", 100)) == 0:
+                skips = model.nonfinite_skips           # updates the device-side guard skipped (non-finite gradients)
+                if rank == 0 and skips != last_skips:
+                    log(f"iter {current_iter}: non-finite gradients, updates skipped so far (weights left unchanged): {skips}")
+                last_skips = skips
                 # get_current_log() reduces the loss scalars over the ranks (a collective): EVERY rank calls it, as the
                 # reference's loop does (ssr/train.py:111-117 -> reduce_loss_dict); only rank 0 prints
                 cur_log = model.get_current_log()

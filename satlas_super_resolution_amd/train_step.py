@@ -46,9 +46,13 @@ LOSS_KEYS = ("l_g_pix", "l_g_gan", "l_d_real", "out_d_real", "l_d_fake", "out_d_
 
 
 class AdamState:
-    """torch.optim.Adam state over a ParamStore's flat arena (+ optional EMA arena)."""
+    """torch.optim.Adam state over a ParamStore's flat arena (+ optional EMA arena).
 
-    def __init__(self, store: engine.ParamStore, lr: float, betas, eps: float, ema_decay: float = 0.0):
+    guard (SSR_NONFINITE_GUARD, default on): update() first scans the gradient arena for NaN / +-Inf into the device word `flag`
+    (ssr_nonfinite_scan), then runs the guarded Adam, which skips the update of a flagged step on the device - parameters, moments and
+    `step` stay, the EMA still moves toward the unchanged parameters - counts it in `skipped` and clears the flag.  No host sync."""
+
+    def __init__(self, store: engine.ParamStore, lr: float, betas, eps: float, ema_decay: float = 0.0, guard: bool = True):
         dev = store.device
         self.store = store
         self.exp_avg = torch.zeros_like(store.data)
@@ -60,13 +64,24 @@ class AdamState:
                              self.exp_avg_sq.data_ptr(), self.ema.data_ptr() if self.ema is not None else None,
                              store.numel, self.lr.data_ptr(), self.step.data_ptr(), betas[0], betas[1], eps,
                              ema_decay, 1.0)
+        self.guard = guard
+        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)       # set by the scan, cleared by the guarded Adam's tail
+        self.skipped = torch.zeros(1, dtype=torch.int32, device=dev)    # updates skipped so far
+        self._scan_src = (C.c_void_p * 1)(store.grad.data_ptr())
+        self._scan_n = (C.c_int64 * 1)(store.numel)
 
     def set_lr(self, lr: float):
         self.lr.fill_(lr)
 
     def update(self, grad_scale: float = 1.0):
         self.args.grad_scale = grad_scale
-        hip.check(hip.lib().ssr_adam_step(C.byref(self.args), hip.stream_ptr()), "ssr_adam_step")
+        L, st = hip.lib(), hip.stream_ptr()
+        if not self.guard:
+            hip.check(L.ssr_adam_step(C.byref(self.args), st), "ssr_adam_step")
+            return
+        hip.check(L.ssr_nonfinite_scan(self._scan_src, self._scan_n, 1, self.flag.data_ptr(), st), "ssr_nonfinite_scan")
+        hip.check(L.ssr_adam_step_guarded(C.byref(self.args), self.flag.data_ptr(), self.skipped.data_ptr(), st),
+                  "ssr_adam_step_guarded")
 
 
 class ESRGANTrainStep:
@@ -157,8 +172,13 @@ class ESRGANTrainStep:
                                              loss_flags=self.loss_dt & hip.DETERMINISTIC,
                                              style_loss_ptr=self.losses.data_ptr() + 4 * 7 * self.loss_stride)   # l_g_style: slot 7
                 self.p_plan.pack()
-            self.opt_g = AdamState(self.g_store, cfg.lr_g, cfg.betas, cfg.eps, cfg.ema_decay)
-            self.opt_d = AdamState(self.d_store, cfg.lr_d, cfg.betas_d or cfg.betas, cfg.eps, 0.0)
+            # SSR_NONFINITE_GUARD=0: the unguarded ssr_adam_step, as before the guard (same-call A/B timing; the reference applies a
+            # non-finite update).  Otherwise each network's Adam skips a step whose gradient arena holds a NaN / Inf (AdamState).  It
+            # runs inside update(), i.e. after every writer of the arena in every path, and under data parallelism after the
+            # exchange: NaN / Inf survives the sum, so every rank sees the same flag without a collective of its own
+            self.nonfinite_guard = os.environ.get("SSR_NONFINITE_GUARD", "1") != "0"
+            self.opt_g = AdamState(self.g_store, cfg.lr_g, cfg.betas, cfg.eps, cfg.ema_decay, guard=self.nonfinite_guard)
+            self.opt_d = AdamState(self.d_store, cfg.lr_d, cfg.betas_d or cfg.betas, cfg.eps, 0.0, guard=self.nonfinite_guard)
         self._graphs: Dict[str, torch.cuda.CUDAGraph] = {}
         self._warm = set()
         self._side = None
@@ -457,3 +477,8 @@ class ESRGANTrainStep:
     def output(self) -> torch.Tensor:
         """self.output (NCHW fp32) of the last generator forward."""
         return self.g_plan.read_output()
+
+    def nonfinite_skips(self) -> Tuple[int, int]:
+        """(G, D): the updates the non-finite guard has skipped so far (read from the device here, only when called)."""
+        g, d = torch.cat([self.opt_g.skipped, self.opt_d.skipped]).tolist()
+        return int(g), int(d)

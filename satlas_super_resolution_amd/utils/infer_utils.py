@@ -47,14 +47,24 @@ def frames_to_input(sel_u8: torch.Tensor) -> torch.Tensor:
     return sel_u8.permute(0, 1, 4, 2, 3).reshape(b, n * 3, 32, 32).float() / 255
 
 
-def quantize_output(output: torch.Tensor) -> np.ndarray:
+def quantize_output(output: torch.Tensor, compute_dtype=None) -> np.ndarray:
     """infer_grid.py:60-64 / infer.py:58-60: clamp(0,1) -> *255 -> astype(uint8) (truncation), NCHW -> uint8 [N,H,W,C] on
-    the host.  Device tensors are quantised on the device (ssr_quantize_u8, csrc/metrics.hip) and only bytes cross PCIe."""
+    the host.  Device tensors are quantised on the device (ssr_quantize_u8_checked, csrc/metrics.hip) and only bytes cross PCIe.
+    A NaN / Inf output raises FloatingPointError (naming `compute_dtype`) instead of turning into black or saturated pixels; on the
+    device the count comes back with the image's own copy."""
+    from ..metrics import nonfinite_error
     if output.is_cuda:
-        from ..metrics import tensor2img_u8
-        return tensor2img_u8(output.detach(), truncate=True).cpu().numpy()
-    out = torch.clamp(output, 0, 1).detach().float().numpy()
-    return np.transpose(out * 255, (0, 2, 3, 1)).astype(np.uint8)
+        from ..metrics import quantize_u8_checked, split_checked
+        buf, shape = quantize_u8_checked(output.detach(), truncate=True)
+        img, bad = split_checked(buf.cpu(), shape)
+        if bad:
+            raise nonfinite_error(bad, compute_dtype)
+        return img.numpy()
+    out = output.detach().float().numpy()
+    bad = int(out.size - np.isfinite(out).sum())
+    if bad:
+        raise nonfinite_error(bad, compute_dtype)
+    return np.transpose(np.clip(out, 0, 1) * 255, (0, 2, 3, 1)).astype(np.uint8)
 
 
 def stitch_arrays(chunks: Dict, img_size: int, grid_size: int = 16, sentinel2: bool = False) -> np.ndarray:
@@ -94,7 +104,7 @@ def infer_chunks(model: Callable[[torch.Tensor], torch.Tensor], inputs: Sequence
         x = torch.cat([inputs[i] for i in idx], 0)
         if device is not None:
             x = x.to(device)
-        y = quantize_output(model(x))
+        y = quantize_output(model(x), getattr(model, "compute_dtype", None))
         for k, i in enumerate(idx):
             out[i] = y[k]
     return out
