@@ -408,6 +408,29 @@ int ssr_metric_shift_sums(const uint8_t* a, const uint8_t* b, int32_t H, int32_t
                           int64_t* out, void* stream);
 int ssr_metric_ssim_sums(const uint8_t* a, const uint8_t* b, int32_t H, int32_t W, int32_t C, int32_t crop, double* out, void* stream);
 
+/* ---- scene inference: a whole Sentinel-2 image stack in, one super-resolved mosaic out (csrc/scene.hip) ----
+ * A scene is uint8 [T][H][W][3] in device memory, H and W multiples of 32 (SSR_EUNSUP otherwise); chunk (i, j) of the
+ * gh x gw = H/32 x W/32 grid has id i*gw + j.  Scene, mosaic and view base pointers are 16-byte aligned.  Chunk and frame ids are
+ * DEVICE arrays, so one generator plan (and its captured forward graph) serves every batch of a scene; an item whose chunk id (or one
+ * of whose frame ids) lies outside the scene is skipped: nothing is read or written for it.
+ * ssr_scene_zero_scan: has_zero[(i*gw + j)*T + t] = 1 if any of the 3072 bytes of frame t of chunk (i, j) is 0, else 0: the validity
+ *   test `[0, 0, 0] in ts` of format_s2naip_data (ssr/utils/infer_utils.py:12-20), which on an ndarray means "any sample equals 0".
+ * ssr_scene_gather: the generator's NHWC input for a batch of B chunks (dst: [B, 32, 32, cs] of `dtype` storage, SSR_F32 / SSR_F32X3
+ *   or SSR_BF16): channel k*3 + c of pixel (y, x) of item b = scene[frame_ids[b*n + k]][32 i + y][32 j + x][c] / 255 with (i, j) =
+ *   chunk_ids[b] - the frame-major stacking, `.float() / 255` (as ATen divides by a host scalar on the device: x * fp32(1/255)) and layout change of infer_utils.py:33-38 followed by
+ *   ssr_nchw_to_nhwc's rounding to the storage type, bit for bit.  Channels 3n .. cs of the view are not written.  n > T, n > 512 or
+ *   an unknown dtype: SSR_EUNSUP.
+ * ssr_scene_scatter_u8: the generator's NHWC output (src: [B, 128, 128, cs], C <= 8 channels used) -> mosaic uint8 [Ho][Wo][C]
+ *   (Ho, Wo multiples of 128): item b lands at rows 128 i .., columns 128 j .. (stitch, infer_utils.py:41-60) after
+ *   ssr_quantize_u8's mode-1 arithmetic: clamp(0, 1) * 255, truncated (infer_grid.py:60-64).  The number of NaN / +-Inf samples among
+ *   the C channels is added to the device counter *nonfinite (one atomic per wave that saw any; the caller zeroes it), as
+ *   ssr_quantize_u8_checked does. */
+int ssr_scene_zero_scan(const uint8_t* scene, int32_t T, int32_t H, int32_t W, uint8_t* has_zero, void* stream);
+int ssr_scene_gather(const uint8_t* scene, int32_t T, int32_t H, int32_t W, const int32_t* chunk_ids, const int32_t* frame_ids,
+                     int32_t B, int32_t n, ssr_view dst, int32_t dtype, void* stream);
+int ssr_scene_scatter_u8(ssr_view src, int32_t dtype, const int32_t* chunk_ids, int32_t B, int32_t C, uint8_t* mosaic, int32_t Ho,
+                         int32_t Wo, int32_t* nonfinite, void* stream);
+
 /* ---- VGG19 perceptual loss glue (csrc/vgg.hip; the convolutions run through ssr_conv2d with SSR_ACT_RELU / m_relu) ----
  * ssr_channel_affine: y[p, c] (+)= x[p, c] * scale[c] + shift[c] for c < C <= 8 (host float arrays, copied into the launch):
  *   the input normalisation (x - mean) / std of the feature extractor and, with accumulate = 1, its adjoint.

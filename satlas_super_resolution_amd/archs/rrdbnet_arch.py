@@ -66,6 +66,23 @@ class SSR_RRDBNet(HipNet):
                                                     need_input_grad=training, **self.kwargs)
         return self._plans[key]
 
+    def plan_for_inference(self, B, H, W):
+        """The frozen-forward plan of this shape with the weights packed, for callers that fill `plan.xin` (NHWC, the plan's storage
+        type) and consume `plan.out` ([B, 4H, 4W, rup(num_out_ch, 8)]) on the device themselves - no NCHW staging tensors:
+
+            plan = net.plan_for_inference(B, 32, 32); <write plan.xin>; net.run_forward(plan); <read plan.out>
+
+        It is the plan forward() uses under no_grad for the same shape (one set of buffers, one captured graph with
+        freeze_packed()).  Scale 4 only: the other scales unshuffle the input on the way into `xin`."""
+        if self.scale != 4:
+            raise NotImplementedError(f"plan_for_inference: scale = {self.scale} (pixel-unshuffled input); only scale 4 generators "
+                                      "take their input as it lies in plan.xin")
+        self.store()
+        plan = self.plan(B, H, W, training=False)
+        assert plan.unshuffle == 1
+        self.pack_if_stale()
+        return plan
+
     def forward(self, x):
         if not torch.is_grad_enabled():      # inference: no autograd node (and no marshalling of 702 parameters through Function.apply)
             return _generator_forward(self, False, x)[1]

@@ -1,0 +1,209 @@
+// Scene inference glue: a whole Sentinel-2 image stack stays on the device between its upload and the download of the
+// super-resolved mosaic (satlas_super_resolution_amd/infer_scene.py).  Byte work around the generator, HBM-bound, a few tens of MB
+// per 512 x 512 tile next to 9.4 TFLOP of convolutions.
+//
+//   ssr_scene_zero_scan    per (chunk, frame): does the 32 x 32 x 3 block hold a zero sample (`[0, 0, 0] in ts`,
+//                          ssr/utils/infer_utils.py:17 of the reference)
+//   ssr_scene_gather       the chosen frames of a batch of chunks -> the generator plan's NHWC input, / 255 (infer_utils.py:33-38)
+//   ssr_scene_scatter_u8   the plan's NHWC output -> truncating uint8 (infer_grid.py:60-64) at the chunks' places in the mosaic
+//                          (infer_utils.py:41-60), counting non-finite samples
+//
+// A scene is uint8 [T][H][W][3], H and W multiples of 32: a chunk row is 96 contiguous bytes (6 x 16) and a row of a
+// super-resolved chunk 128 * C bytes of the mosaic, both 16-byte aligned when the base pointers are - the global accesses on the
+// byte side are uint4.  Chunk and frame ids come from device arrays; an id outside the scene makes its item a no-op (nothing is
+// read or written for it).
+#include "common.h"
+
+namespace {
+
+constexpr int CH = 32;             // low-resolution chunk edge
+constexpr int ROW16 = CH * 3 / 16; // uint4 per chunk row of the scene
+constexpr int SR = 128;            // super-resolved chunk edge (scale 4)
+constexpr int SROWS = 8;           // mosaic rows per scatter block
+constexpr int MAX_C = 8;           // output channels ssr_scene_scatter_u8 accepts
+constexpr float INV255 = 1.0f / 255.0f;
+
+__device__ __forceinline__ bool has_zero_byte(uint32_t v) { return ((v - 0x01010101u) & ~v & 0x80808080u) != 0; }
+
+// one wave per (chunk, frame): 192 uint4 = 3 per lane
+__global__ __launch_bounds__(256) void scene_zero_scan_kernel(const uint8_t* __restrict__ scene, int T, int H, int W,
+                                                              uint8_t* __restrict__ has_zero) {
+    const int gw = W / CH, n_chunks = (H / CH) * gw;
+    const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (long)n_chunks * T) return;                       // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const int chunk = (int)(item / T), t = (int)(item - (long)chunk * T);
+    const int ci = chunk / gw, cj = chunk - ci * gw;
+    const uint8_t* base = scene + (((long)t * H + (long)ci * CH) * W + (long)cj * CH) * 3;
+    bool z = false;
+#pragma unroll
+    for (int k = 0; k < CH * ROW16 / 64; ++k) {
+        const int e = lane + 64 * k, row = e / ROW16, q = e - row * ROW16;
+        const uint4 v = *reinterpret_cast<const uint4*>(base + (long)row * W * 3 + 16 * q);
+        z |= has_zero_byte(v.x) | has_zero_byte(v.y) | has_zero_byte(v.z) | has_zero_byte(v.w);
+    }
+    const bool any = __any(z);
+    if (lane == 0) has_zero[item] = any ? 1 : 0;
+}
+
+template <typename T, int V> struct Pack;
+template <typename T> struct Pack<T, 1> { T v[1]; };
+template <> struct alignas(16) Pack<float, 4> { float v[4]; };
+template <> struct alignas(16) Pack<__bf16, 8> { __bf16 v[8]; };
+
+// one block per (batch item, chunk row): the n chosen frames' rows go through LDS (n * 96 bytes), then V consecutive channels of a
+// pixel per thread and store (V = 16 bytes when 3 n is a multiple of it, else single elements).  Consecutive threads write
+// consecutive addresses inside a pixel and on to the next one (contiguous when the view has no pad).
+template <typename T, int V>
+__global__ __launch_bounds__(256) void scene_gather_kernel(const uint8_t* __restrict__ scene, int T_, int H, int W,
+                                                           const int32_t* __restrict__ chunk_ids,
+                                                           const int32_t* __restrict__ frame_ids, int n, ssr_view dst) {
+    extern __shared__ uint4 rows[];                               // [n][ROW16]
+    const int b = blockIdx.x / CH, y = blockIdx.x - b * CH;
+    const int gw = W / CH, chunk = chunk_ids[b];
+    if (chunk < 0 || chunk >= (H / CH) * gw) return;              // block-uniform
+    const int ci = chunk / gw, cj = chunk - ci * gw;
+    for (int k = 0; k < n; ++k) {                                 // block-uniform: before any barrier
+        const int f = frame_ids[b * n + k];
+        if (f < 0 || f >= T_) return;
+    }
+    for (int e = threadIdx.x; e < n * ROW16; e += 256) {
+        const int k = e / ROW16, q = e - k * ROW16;
+        const long t = frame_ids[b * n + k];
+        rows[e] = *reinterpret_cast<const uint4*>(scene + ((t * H + (long)ci * CH + y) * W + (long)cj * CH) * 3 + 16 * q);
+    }
+    __syncthreads();
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(rows);
+    const int C = 3 * n, groups = C / V;
+    T* __restrict__ d = reinterpret_cast<T*>(dst.p);
+    const long pix0 = ((long)b * CH + y) * CH;
+    for (int e = threadIdx.x; e < CH * groups; e += 256) {
+        const int x = e / groups, c0 = (e - x * groups) * V;
+        Pack<T, V> o;
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+            const int c = c0 + u, k = c / 3;
+            // `.float() / 255` of frames_to_input ON THE DEVICE: ATen's division of a tensor by a host scalar multiplies by the
+            // reciprocal rounded to fp32 (x * (1.0f / 255.0f); 126 of the 256 byte values differ from x / 255.0f in the last bit),
+            // then the storage type's rounding (ssr_nchw_to_nhwc)
+            o.v[u] = from_f32<T>((float)bytes[k * (CH * 3) + x * 3 + (c - 3 * k)] * INV255);
+        }
+        *reinterpret_cast<Pack<T, V>*>(d + (pix0 + x) * dst.cs + dst.coff + c0) = o;
+    }
+}
+
+template <typename T> __device__ __forceinline__ void load_pixel(const T* p, int C, float (&v)[MAX_C]);
+template <> __device__ __forceinline__ void load_pixel<float>(const float* p, int C, float (&v)[MAX_C]) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(p);          // a pixel of the view starts on 32 bytes (cs, coff % 8 == 0)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = a[u];
+    if (C > 4) {
+        const f32x4 b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[4 + u] = b[u];
+    }
+}
+template <> __device__ __forceinline__ void load_pixel<__bf16>(const __bf16* p, int C, float (&v)[MAX_C]) {
+    const bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = (float)a[u];
+}
+
+// one block per (batch item, SROWS rows of its 128 x 128 output): pixels are read whole (the first 8 channels of the view in one
+// or two 16-byte loads), quantised into an LDS image of the rows, and leave as uint4 stores into the mosaic
+template <typename T>
+__global__ __launch_bounds__(256) void scene_scatter_u8_kernel(ssr_view src, const int32_t* __restrict__ chunk_ids, int C,
+                                                               uint8_t* __restrict__ mosaic, int Ho, int Wo,
+                                                               int32_t* __restrict__ nonfinite) {
+    __shared__ uint4 img[SROWS * SR * MAX_C / 16];
+    uint8_t* bytes = reinterpret_cast<uint8_t*>(img);
+    const int b = blockIdx.x / (SR / SROWS), y0 = (blockIdx.x - b * (SR / SROWS)) * SROWS;
+    const int gw = Wo / SR, chunk = chunk_ids[b];
+    if (chunk < 0 || chunk >= (Ho / SR) * gw) return;             // block-uniform
+    const int ci = chunk / gw, cj = chunk - ci * gw;
+    const T* __restrict__ s = reinterpret_cast<const T*>(src.p);
+    int bad = 0;
+#pragma unroll
+    for (int it = 0; it < SROWS * SR / 256; ++it) {
+        const int e = threadIdx.x + 256 * it, r = e / SR, x = e - r * SR;
+        float v[MAX_C];
+        load_pixel<T>(s + (((long)b * SR + y0 + r) * SR + x) * src.cs + src.coff, C, v);
+#pragma unroll
+        for (int c = 0; c < MAX_C; ++c) {
+            if (c < C) {
+                bad += (__float_as_uint(v[c]) & 0x7f800000u) == 0x7f800000u;
+                // ssr_quantize_u8 mode 1: clamp(0, 1) then * 255 in fp32 (NaN -> 0 via fmaxf), truncation
+                bytes[(r * SR + x) * C + c] = (uint8_t)(fminf(fmaxf(v[c], 0.f), 1.f) * 255.0f);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_down(bad, o, 64);
+    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(nonfinite, bad);
+    __syncthreads();
+    const int row16 = SR * C / 16;                                // uint4 per chunk row of the mosaic
+    for (int e = threadIdx.x; e < SROWS * row16; e += 256) {
+        const int r = e / row16, q = e - r * row16;
+        *reinterpret_cast<uint4*>(mosaic + (((long)ci * SR + y0 + r) * Wo + (long)cj * SR) * C + 16 * q) = img[e];
+    }
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+#define ST(s) reinterpret_cast<hipStream_t>(s)
+
+extern "C" int ssr_scene_zero_scan(const uint8_t* scene, int32_t T, int32_t H, int32_t W, uint8_t* has_zero, void* stream) {
+    if (!scene || !has_zero || T <= 0 || H <= 0 || W <= 0 || !aligned16(scene)) return SSR_EINVAL;
+    if (H % CH || W % CH) return SSR_EUNSUP;
+    const long items = (long)(H / CH) * (W / CH) * T;
+    if (items > (1l << 30)) return SSR_EINVAL;
+    hipLaunchKernelGGL(scene_zero_scan_kernel, dim3((int)((items + 3) / 4)), dim3(256), 0, ST(stream), scene, T, H, W, has_zero);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_gather(const uint8_t* scene, int32_t T, int32_t H, int32_t W, const int32_t* chunk_ids,
+                                const int32_t* frame_ids, int32_t B, int32_t n, ssr_view dst, int32_t dtype, void* stream) {
+    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
+    if (!scene || !chunk_ids || !frame_ids || !dst.p || T <= 0 || H <= 0 || W <= 0 || B <= 0 || n <= 0) return SSR_EINVAL;
+    if (!aligned16(scene) || !aligned16(dst.p) || dst.cs % 8 || dst.coff % 8 || dst.coff < 0 || dst.coff + 3 * n > dst.cs ||
+        B > (1 << 20))
+        return SSR_EINVAL;
+    if (H % CH || W % CH || n > T || n > 512 || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
+    const dim3 grid(B * CH), block(256);
+    const size_t lds = (size_t)n * CH * 3;
+    const int C = 3 * n;
+    if (dtype == SSR_F32) {
+        if (C % 4 == 0)
+            hipLaunchKernelGGL((scene_gather_kernel<float, 4>), grid, block, lds, ST(stream), scene, T, H, W, chunk_ids, frame_ids, n, dst);
+        else
+            hipLaunchKernelGGL((scene_gather_kernel<float, 1>), grid, block, lds, ST(stream), scene, T, H, W, chunk_ids, frame_ids, n, dst);
+    } else {
+        if (C % 8 == 0)
+            hipLaunchKernelGGL((scene_gather_kernel<__bf16, 8>), grid, block, lds, ST(stream), scene, T, H, W, chunk_ids, frame_ids, n, dst);
+        else
+            hipLaunchKernelGGL((scene_gather_kernel<__bf16, 1>), grid, block, lds, ST(stream), scene, T, H, W, chunk_ids, frame_ids, n, dst);
+    }
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_scatter_u8(ssr_view src, int32_t dtype, const int32_t* chunk_ids, int32_t B, int32_t C, uint8_t* mosaic,
+                                    int32_t Ho, int32_t Wo, int32_t* nonfinite, void* stream) {
+    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
+    if (!src.p || !chunk_ids || !mosaic || !nonfinite || B <= 0 || C <= 0 || Ho <= 0 || Wo <= 0) return SSR_EINVAL;
+    // whole pixels are read: the 8 channels from coff on must lie inside the buffer's pixel
+    if (!aligned16(src.p) || !aligned16(mosaic) || src.cs % 8 || src.coff % 8 || src.coff < 0 || src.coff + MAX_C > src.cs ||
+        C > MAX_C || B > (1 << 20))
+        return SSR_EINVAL;
+    if (Ho % SR || Wo % SR || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
+    const dim3 grid(B * (SR / SROWS)), block(256);
+    if (dtype == SSR_F32)
+        hipLaunchKernelGGL(scene_scatter_u8_kernel<float>, grid, block, 0, ST(stream), src, chunk_ids, C, mosaic, Ho, Wo, nonfinite);
+    else
+        hipLaunchKernelGGL(scene_scatter_u8_kernel<__bf16>, grid, block, 0, ST(stream), src, chunk_ids, C, mosaic, Ho, Wo, nonfinite);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}

@@ -126,6 +126,7 @@ ABI_SYMBOLS = [
     "ssr_quantize_u8", "ssr_metric_shift_sums", "ssr_metric_ssim_sums", "ssr_split_bf16", "ssr_split_bf16_multi", "ssr_channel_affine", "ssr_relu_maxpool2_fwd", "ssr_relu_maxpool2_bwd",
     "ssr_gram_splits", "ssr_gram_fwd", "ssr_gram_l1", "ssr_gram_bwd",
     "ssr_nonfinite_scan", "ssr_adam_step_guarded", "ssr_quantize_u8_checked",
+    "ssr_scene_zero_scan", "ssr_scene_gather", "ssr_scene_scatter_u8",
     "ssr_device_info", "ssr_abi_version",
 ]
 SCAN_MAX_RANGES = 8           # SSR_SCAN_MAX_RANGES: ranges per ssr_nonfinite_scan call
@@ -198,6 +199,9 @@ def lib() -> C.CDLL:
     l.ssr_nonfinite_scan.argtypes = [C.POINTER(vp), C.POINTER(i64), i32, vp, vp]
     l.ssr_adam_step_guarded.argtypes = [C.POINTER(AdamArgs), vp, vp, vp]
     l.ssr_quantize_u8_checked.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
+    l.ssr_scene_zero_scan.argtypes = [vp, i32, i32, i32, vp, vp]
+    l.ssr_scene_gather.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, View, i32, vp]
+    l.ssr_scene_scatter_u8.argtypes = [View, i32, vp, i32, i32, vp, i32, i32, vp, vp]
     l.ssr_device_info.argtypes = [C.c_char_p, i32]
     l.ssr_abi_version.argtypes = []
     for s in ABI_SYMBOLS:

@@ -1,0 +1,334 @@
+"""Scene inference: one Sentinel-2 image stack in, one super-resolved image out, everything between the upload and the download on
+the device.
+
+    python -m satlas_super_resolution_amd.infer_scene -opt infer_scene.yml
+    python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m satlas_super_resolution_amd.infer_scene -opt ...
+
+`infer_grid` keeps the reference's file layout (256 chunk PNGs in, 256 chunk PNGs and two mosaics out, per tile); this driver takes
+the image itself: `{data_dir}/NAME.png` of shape [T*H, W, 3] (the T frames stacked on the rows, the chunk files' convention at full
+size) or `{data_dir}/NAME.npy` of shape [T, H, W, 3], H and W multiples of 32, and writes `{save_path}/NAME/stitched_sr.png`
+([4H, 4W, 3]) and `{save_path}/NAME/stitched_s2.png` (frame 0) - the mosaics `infer_grid` writes for the same pixels.  Every 32 x 32
+chunk is super-resolved on its own, as the reference does (ssr/infer_grid.py:46-85), so the result is the reference's mosaic.
+
+On the device (csrc/scene.hip): the "does this frame hold a zero" test of format_s2naip_data for every (chunk, frame), the cut into
+chunks + `/ 255` + NHWC straight into the generator plan's input, the generator (a replayed graph), the truncating uint8 + stitch
+straight from the plan's output into the mosaic, and the count of non-finite outputs.  On the host: which frames each chunk uses
+(`select_scene_frames`: 256 tiny draws that keep the reference's `random` stream), one PNG decode and two encodes per scene, in the
+`png_io` worker processes while the device runs another scene.
+
+Option keys: `data_dir`, `save_path`, `n_lr_images`, `network_g`, `path.*`, `compute_dtype` (default fp32h), `batch` (chunks per
+generator launch, default 64), `io_workers` as `infer_grid`; `scene_hw: [H, W]` for PNG scenes that are not square."""
+from __future__ import annotations
+
+import argparse
+import os
+import random
+import time
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+CHUNK = 32            # low-resolution chunk edge (format_s2naip_data)
+SCALE = 4
+
+
+# ------------------------------------------------------------------------------------------------ host side
+def select_scene_frames(has_zero: np.ndarray, n: int) -> np.ndarray:
+    """Which frames of every chunk go to the network: has_zero bool [chunks, T] (does frame t of the chunk hold a zero sample) ->
+    int32 [chunks, n].  `utils.infer_utils.select_frames`' rule per chunk - clean frames are preferred, frames that hold zeros top
+    the list up, fewer than n frames in total make `random.sample` raise ValueError - with the `random` module consumed once per
+    chunk in ROW-MAJOR chunk order: a seeded run picks what format_s2naip_data would pick called on the chunks in that order."""
+    has_zero = np.asarray(has_zero).astype(bool)
+    assert has_zero.ndim == 2, has_zero.shape
+    out = np.empty((has_zero.shape[0], n), np.int32)
+    for k, hz in enumerate(has_zero):
+        clean, dirty = np.flatnonzero(~hz).tolist(), np.flatnonzero(hz).tolist()
+        if len(clean) >= n:
+            out[k] = random.sample(clean, n)
+        else:
+            out[k] = clean + random.sample(dirty, n - len(clean))
+    return out
+
+
+def check_scene_size(H: int, W: int) -> None:
+    if H <= 0 or W <= 0 or H % CHUNK or W % CHUNK:
+        raise ValueError(f"scene of {H} x {W} pixels: height and width must be multiples of {CHUNK}")
+
+
+def parse_scene(arr: np.ndarray, scene_hw: Optional[Sequence[int]] = None) -> np.ndarray:
+    """A scene file's array -> uint8 [T, H, W, 3].  [T, H, W, 3] (.npy) is taken as it is; [T*H, W, 3] (.png: the frames stacked on
+    the rows) is cut with H = scene_hw[0] (and W checked against scene_hw[1]) or, without scene_hw, as square frames H = W."""
+    arr = np.asarray(arr)
+    if arr.dtype != np.uint8 or arr.ndim not in (3, 4) or arr.shape[-1] != 3:
+        raise ValueError(f"a scene is a uint8 array [T, H, W, 3] or [T*H, W, 3], not {arr.dtype} {tuple(arr.shape)}")
+    if arr.ndim == 3:
+        rows, W = arr.shape[:2]
+        H = W
+        if scene_hw is not None:
+            H = int(scene_hw[0])
+            if int(scene_hw[1]) != W:
+                raise ValueError(f"scene image of {rows} x {W} pixels: scene_hw {list(scene_hw)} expects width {int(scene_hw[1])}")
+        if H <= 0 or rows % H or rows == 0:
+            raise ValueError(f"scene image of {rows} x {W} pixels: {rows} rows are not a whole number of frames of height {H}"
+                             + ("" if scene_hw is not None else " (square frames are assumed: set scene_hw: [H, W])"))
+        arr = arr.reshape(rows // H, H, W, 3)
+    check_scene_size(arr.shape[1], arr.shape[2])
+    return arr
+
+
+def list_scenes(data_dir: str) -> List[Tuple[str, str]]:
+    """[(NAME, path)] of the scene files of data_dir (NAME.png / NAME.npy), sorted by NAME"""
+    found = {}
+    for f in os.listdir(data_dir):
+        name, ext = os.path.splitext(f)
+        if ext.lower() in (".png", ".npy") and os.path.isfile(os.path.join(data_dir, f)):
+            if name in found:
+                raise ValueError(f"{data_dir}: scene {name!r} exists as both {os.path.basename(found[name])} and {f}")
+            found[name] = os.path.join(data_dir, f)
+    return sorted(found.items())
+
+
+def scenes_of_rank(scenes: Sequence, rank: int, world: int) -> List:
+    """rank r takes scenes r, r + world, ... of the sorted list (no collective, no barrier: every scene is one rank's own)"""
+    return list(scenes[rank::world])
+
+
+def _png_shape(path: str) -> Tuple[int, int, int]:
+    from PIL import Image
+    with Image.open(path) as im:          # header only: nothing is decoded here
+        w, h = im.size
+    return (h, w, 3)
+
+
+# ------------------------------------------------------------------------------------------------ device side
+def _ptr(t: torch.Tensor) -> int:
+    return t.data_ptr()
+
+
+def scene_zero_scan(scene: torch.Tensor) -> torch.Tensor:
+    """uint8 [T, H, W, 3] on the device -> uint8 [gh*gw, T] on the device: 1 where frame t of the chunk holds a zero sample"""
+    from . import hip
+    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
+    T, H, W = scene.shape[:3]
+    check_scene_size(H, W)
+    out = torch.empty((H // CHUNK) * (W // CHUNK), T, dtype=torch.uint8, device=scene.device)
+    hip.check(hip.lib().ssr_scene_zero_scan(_ptr(scene), T, H, W, _ptr(out), hip.stream_ptr()), "ssr_scene_zero_scan")
+    return out
+
+
+def scene_gather(scene: torch.Tensor, chunk_ids: torch.Tensor, frame_ids: torch.Tensor, dst: torch.Tensor, dtype: Optional[int] = None):
+    """the chosen frames (int32 [B, n], device) of the chunks chunk_ids (int32 [B], device) -> dst, an NHWC generator input
+    [B, 32, 32, >= 3n] of fp32 or bf16 storage (GeneratorPlan.xin); pad channels are left as they are"""
+    from . import hip
+    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
+    assert chunk_ids.dtype == torch.int32 and frame_ids.dtype == torch.int32 and chunk_ids.is_cuda and frame_ids.is_cuda
+    assert chunk_ids.is_contiguous() and frame_ids.is_contiguous()
+    T, H, W = scene.shape[:3]
+    check_scene_size(H, W)
+    B, n = frame_ids.shape
+    assert chunk_ids.shape == (B,) and tuple(dst.shape[:3]) == (B, CHUNK, CHUNK) and dst.shape[3] >= 3 * n, (chunk_ids.shape, dst.shape)
+    if dtype is None:
+        dtype = hip.dtype_code(dst.dtype)
+    hip.check(hip.lib().ssr_scene_gather(_ptr(scene), T, H, W, _ptr(chunk_ids), _ptr(frame_ids), B, n, hip.view(dst), dtype,
+                                         hip.stream_ptr()), "ssr_scene_gather")
+
+
+def scene_scatter_u8(src: torch.Tensor, chunk_ids: torch.Tensor, C: int, mosaic: torch.Tensor, nonfinite: torch.Tensor,
+                     dtype: Optional[int] = None):
+    """src, an NHWC generator output [B, 128, 128, >= C] (GeneratorPlan.out) -> truncating uint8 at the places of the chunks
+    chunk_ids in mosaic (uint8 [Ho, Wo, C], device); adds the number of non-finite samples to the int32 device counter"""
+    from . import hip
+    B = chunk_ids.shape[0]
+    assert chunk_ids.dtype == torch.int32 and chunk_ids.is_cuda and chunk_ids.is_contiguous()
+    assert tuple(src.shape[:3]) == (B, SCALE * CHUNK, SCALE * CHUNK) and src.shape[3] >= C, src.shape
+    assert mosaic.is_cuda and mosaic.dtype == torch.uint8 and mosaic.is_contiguous() and mosaic.dim() == 3 and mosaic.shape[2] == C
+    assert nonfinite.dtype == torch.int32 and nonfinite.is_cuda
+    if dtype is None:
+        dtype = hip.dtype_code(src.dtype)
+    hip.check(hip.lib().ssr_scene_scatter_u8(hip.view(src), dtype, _ptr(chunk_ids), B, C, _ptr(mosaic), mosaic.shape[0],
+                                             mosaic.shape[1], _ptr(nonfinite), hip.stream_ptr()), "ssr_scene_scatter_u8")
+
+
+class _Pending:
+    """a scene whose launches are queued: the pinned host buffer its mosaic and counter are being copied to, and the event behind
+    that copy"""
+
+    def __init__(self, host, event, shape, compute_dtype, chunks):
+        self.host, self.event, self.shape, self.compute_dtype, self.chunks = host, event, shape, compute_dtype, chunks
+
+    def result(self, where: str = "") -> np.ndarray:
+        """waits for the download; raises FloatingPointError if an output sample was NaN / Inf (before any pixel is handed out)"""
+        from .metrics import nonfinite_error, split_checked
+        self.event.synchronize()
+        img, bad = split_checked(self.host, self.shape)
+        if bad:
+            raise nonfinite_error(bad, self.compute_dtype, where)
+        return img.numpy()
+
+
+def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[torch.Tensor] = None) -> _Pending:
+    """upload, zero scan, frame choice (the one host round trip: chunks x T flags down, chunks x n ids up), then every batch of
+    chunks through gather -> generator -> scatter and the download of mosaic + counter; returns without waiting for them"""
+    if getattr(model, "scale", SCALE) != SCALE:
+        raise NotImplementedError(f"scene inference runs scale {SCALE} generators only (scale = {model.scale})")
+    n, batch = int(n_lr_images), int(batch)
+    if batch < 1:
+        raise ValueError(f"batch = {batch}")
+    dev = next(model.parameters()).device
+    if isinstance(frames, torch.Tensor):
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError(f"a scene is a uint8 array [T, H, W, 3], not {frames.dtype} {tuple(frames.shape)}")
+        check_scene_size(frames.shape[1], frames.shape[2])
+        scene = frames.to(dev, non_blocking=True).contiguous()
+    else:
+        arr = np.asarray(frames)
+        if arr.ndim != 4:
+            raise ValueError(f"a scene is a uint8 array [T, H, W, 3], not {arr.dtype} {tuple(arr.shape)}")
+        arr = parse_scene(arr)
+        arr = np.ascontiguousarray(arr) if arr.flags.writeable else np.array(arr)      # (a read-only mapping of a .npy file: copy)
+        scene = torch.from_numpy(arr).to(dev, non_blocking=True)
+    T, H, W = scene.shape[:3]
+    C_in, C_out = model.kwargs["num_in_ch"], model.kwargs["num_out_ch"]
+    if C_in != 3 * n:
+        raise ValueError(f"n_lr_images = {n} gives {3 * n} input channels, the generator takes {C_in}")
+    gw, n_chunks = W // CHUNK, (H // CHUNK) * (W // CHUNK)
+    has_zero = scene_zero_scan(scene).cpu().numpy()
+    frame_ids = torch.from_numpy(select_scene_frames(has_zero, n)).to(dev, non_blocking=True)
+    chunk_ids = torch.arange(n_chunks, dtype=torch.int32, device=dev)
+    Ho, Wo = SCALE * H, SCALE * W
+    nb = Ho * Wo * C_out
+    off = -(-nb // 16) * 16
+    buf = torch.empty(off + 4, dtype=torch.uint8, device=dev)       # the mosaic and, behind it, the counter: one download
+    counter = buf[off:].view(torch.int32)
+    counter.zero_()
+    mosaic = buf[:nb].view(Ho, Wo, C_out)
+    with torch.no_grad():
+        for c0 in range(0, n_chunks, batch):
+            ids = chunk_ids[c0:c0 + batch]
+            plan = model.plan_for_inference(ids.shape[0], CHUNK, CHUNK)
+            scene_gather(scene, ids, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
+            model.run_forward(plan)
+            scene_scatter_u8(plan.out, ids, C_out, mosaic, counter, plan.dt)
+    if host is None or host.numel() != buf.numel():
+        host = torch.empty(buf.shape, dtype=torch.uint8, pin_memory=True)
+    host.copy_(buf, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record()
+    return _Pending(host, ev, (Ho, Wo, C_out), getattr(model, "compute_dtype", None), n_chunks)
+
+
+def super_resolve_scene(model, frames, n_lr_images: int, batch: int = 64) -> np.ndarray:
+    """frames: uint8 [T, H, W, 3] (numpy array or CUDA tensor), H and W multiples of 32 (ValueError otherwise) -> uint8
+    [4H, 4W, 3]: every 32 x 32 chunk super-resolved on its own from `n_lr_images` of its frames (select_scene_frames) and placed
+    at rows 128 i, columns 128 j.  Raises FloatingPointError (metrics.nonfinite_error) if any output sample is NaN / Inf."""
+    return _enqueue_scene(model, frames, n_lr_images, batch).result()
+
+
+# ------------------------------------------------------------------------------------------------ driver
+def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device=None) -> Dict:
+    from . import png_io
+    from .infer_grid import load_generator
+    data_dir, save_path, n_lr_images = opt["data_dir"], opt["save_path"], int(opt["n_lr_images"])
+    batch, scene_hw = int(opt.get("batch", 64)), opt.get("scene_hw")
+    if device is None:
+        device = torch.device("cuda")
+    if model is None:
+        model = load_generator(opt, device)
+    scenes = list_scenes(data_dir)
+    if rank == 0:
+        print("Running inference on ", len(scenes), " scenes.")
+    mine = scenes_of_rank(scenes, rank, world)
+    # worker budget as infer_grid's: the cores this process may really use, shared by the ranks of the node, one left to the driver
+    workers = int(opt.get("io_workers", max(1, min(16, png_io.host_cores() // max(1, world) - 1))))
+    t_start = time.perf_counter()
+    chunks = 0
+    import contextlib
+    with contextlib.ExitStack() as stack:
+        open_blocks: List = []
+        stack.callback(lambda: [b.close() for b in list(open_blocks)])      # registered first: runs after the last task has ended
+        pool = stack.enter_context(png_io.shared_pool(workers))
+        sdir = None
+
+        def block(nbytes, tag):
+            nonlocal sdir
+            if sdir is None:
+                sdir = png_io.shm_dir(4 * nbytes)
+            blk = png_io.ShmBlock(nbytes, sdir, f"r{rank}_{tag}")
+            open_blocks.append(blk)
+            return blk
+
+        def release(blk):
+            blk.close()
+            if blk in open_blocks:
+                open_blocks.remove(blk)
+
+        def start_read(k):
+            """scene k's pixels on their way to host memory: a PNG is decoded by a worker into a one-shot block, a .npy is mapped"""
+            name, path = mine[k]
+            if path.lower().endswith(".npy"):
+                return name, None, None, np.load(path, mmap_mode="r")
+            shape = _png_shape(path)
+            blk = block(int(np.prod(shape)), "scene")
+            return name, blk, pool.submit("read_into", [path], blk.path, blk.nbytes, [0], blk.nbytes, True), shape
+
+        def finish_read(rd) -> Tuple[str, object, np.ndarray]:
+            name, blk, fut, what = rd
+            if blk is None:
+                return name, None, parse_scene(np.asarray(what), scene_hw)
+            got = fut.result()[0]
+            arr = got if isinstance(got, np.ndarray) else blk.buf[:int(np.prod(got))].reshape(got)
+            return name, blk, parse_scene(arr, scene_hw)
+
+        def submit_save(arr: np.ndarray, path: str):
+            """one image to an encoder through a block of its own (closed and unlinked as soon as the file is written)"""
+            blk = block(arr.nbytes, "mosaic")
+            blk.buf[:] = arr.reshape(-1)
+            f = pool.submit("save_from", blk.path, blk.nbytes, [(0, tuple(arr.shape), path)], True)
+            f.add_done_callback(lambda _f, b=blk: release(b))
+            return f
+
+        # software pipeline over the scenes: scene k + 1 is being decoded and scene k - 1 encoded while the device runs scene k
+        saves = []
+        stack.callback(lambda: [f.exception() for f in saves])     # runs first, also on an error: earlier scenes' files are whole
+        hosts = [None, None]
+        reading = start_read(0) if mine else None
+        prev = None                                   # (name, first frame, pending) of the scene the device is running
+        for k in range(len(mine) + 1):
+            cur = None
+            if k < len(mine):
+                name, blk, frames = finish_read(reading)
+                reading = start_read(k + 1) if k + 1 < len(mine) else None
+                pending = _enqueue_scene(model, frames, n_lr_images, batch, hosts[k & 1])
+                hosts[k & 1] = pending.host
+                cur = (name, np.array(frames[0]), pending)          # (the upload has been waited for: the flags came back)
+                del frames
+                if blk is not None:
+                    release(blk)
+            if prev is not None:
+                pname, first, ppend = prev
+                sr = ppend.result(f" in scene {pname}")             # raises before any file of the scene is written
+                saves.append(submit_save(sr, os.path.join(save_path, pname, "stitched_sr.png")))
+                saves.append(submit_save(first, os.path.join(save_path, pname, "stitched_s2.png")))
+                chunks += ppend.chunks
+            prev = cur
+        for f in saves:
+            f.result()
+    return {"scenes": len(mine), "chunks": chunks, "seconds": round(time.perf_counter() - t_start, 3), "io_workers": workers}
+
+
+def main():
+    import yaml
+    parser = argparse.ArgumentParser()
+    parser.add_argument("-opt", type=str, help="Path to the options file.")
+    args = parser.parse_args()
+    with open(args.opt) as f:
+        opt = yaml.safe_load(f)
+    from .dp import init_distributed
+    ctx = init_distributed()
+    res = run_infer_scene(opt, rank=ctx.rank, world=ctx.world)
+    print(f"rank {ctx.rank}: {res}")
+
+
+if __name__ == "__main__":
+    main()

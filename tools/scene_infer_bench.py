@@ -1,0 +1,128 @@
+"""Whole-tile inference end to end on ONE GPU, the two drivers side by side on the same pixels:
+
+  (a) infer_grid.run_infer_grid on the reference's chunk-file tree (256 PNGs of [8*32, 32, 3] per 512 x 512 tile in, 256 chunk
+      PNGs + two mosaics out) - the tree tools/infer_e2e_bench.py generates;
+  (b) infer_scene.run_infer_scene on one PNG of [8*512, 512, 3] per tile (two mosaics out), and once more on .npy scenes;
+  then the generator alone (inputs resident in HBM) as tools/infer_e2e_bench.py times it.
+
+One process, SSR_RRDBNet(24, 3, 4, 64, 23, 32) with random weights, n_lr_images 8, batch 64, `tiles` tiles per repetition (default 8:
+two tiles are a window of a tenth of a second, too short to time); after a warm-up of both paths (a) and (b) alternate three times.
+
+    python tools/scene_infer_bench.py [mode] [tiles] > profiles/scene_infer/bench.json
+    rocprofv3 --kernel-trace --stats ... -- python tools/scene_infer_bench.py fp32h 8 --scene-only      (warm-up + one run of (b))
+"""
+import json
+import os
+import shutil
+import statistics
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    scene_only = "--scene-only" in sys.argv
+    mode = args[0] if len(args) > 0 else "fp32h"
+    n_tiles = int(args[1]) if len(args) > 1 else 8
+    from PIL import Image
+    from satlas_super_resolution_amd import png_io
+    from satlas_super_resolution_amd.archs.rrdbnet_arch import SSR_RRDBNet
+    from satlas_super_resolution_amd.infer_grid import run_infer_grid
+    from satlas_super_resolution_amd.infer_scene import run_infer_scene
+    tmp = tempfile.mkdtemp(prefix="scene_bench_")
+    try:
+        rng = np.random.RandomState(0)
+        yy, xx = np.mgrid[0:256, 0:32]
+        for d in ("in", "scenes_png", "scenes_npy"):
+            os.makedirs(os.path.join(tmp, d))
+        for t in range(n_tiles):
+            d = os.path.join(tmp, "in", f"tile{t}")
+            os.makedirs(d)
+            scene = np.empty((8, 512, 512, 3), np.uint8)
+            for i in range(16):
+                for j in range(16):      # smooth field + noise: PNG sizes like real imagery rather than incompressible noise
+                    img = 110 + 60 * np.sin((yy + 7 * i) / 19.0)[..., None] * np.cos((xx + 5 * j) / 11.0)[..., None] + rng.randint(-12, 13, (256, 32, 3))
+                    img = np.clip(img, 1, 255).astype(np.uint8)
+                    if not scene_only:
+                        Image.fromarray(img).save(os.path.join(d, f"{i}_{j}.png"))
+                    scene[:, 32 * i:32 * (i + 1), 32 * j:32 * (j + 1)] = img.reshape(8, 32, 32, 3)
+            Image.fromarray(scene.reshape(8 * 512, 512, 3)).save(os.path.join(tmp, "scenes_png", f"tile{t}.png"))
+            if not scene_only:
+                np.save(os.path.join(tmp, "scenes_npy", f"tile{t}.npy"), scene)
+        net = SSR_RRDBNet(24, 3, 4, 64, 23, 32, compute_dtype=mode).cuda().eval().freeze_packed()
+        base = {"n_lr_images": 8, "batch": 64}
+        runs = [0]
+
+        def grid():
+            runs[0] += 1
+            opt = dict(base, data_dir=os.path.join(tmp, "in") + "/", save_path=os.path.join(tmp, f"out_grid{runs[0]}") + "/")
+            t0 = time.perf_counter()
+            res = run_infer_grid(opt, model=net)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            assert (res["chunks"], res["tiles_stitched"]) == (256 * n_tiles, n_tiles), res
+            shutil.rmtree(opt["save_path"], ignore_errors=True)
+            return dt / n_tiles
+
+        def scene(kind):
+            runs[0] += 1
+            opt = dict(base, data_dir=os.path.join(tmp, "scenes_" + kind) + "/", save_path=os.path.join(tmp, f"out_scene{runs[0]}") + "/")
+            t0 = time.perf_counter()
+            res = run_infer_scene(opt, model=net)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            assert (res["scenes"], res["chunks"]) == (n_tiles, 256 * n_tiles), res
+            assert len(os.listdir(opt["save_path"])) == n_tiles
+            shutil.rmtree(opt["save_path"], ignore_errors=True)
+            return dt / n_tiles
+
+        n_workers = max(1, min(16, png_io.host_cores() - 1))
+        with png_io.shared_pool(n_workers) as pool:      # the workers stay up for every later driver call of this process
+            [f.result() for f in [pool.submit("read_many", []) for _ in range(2 * n_workers)]]
+        if scene_only:
+            scene("png")
+            print(json.dumps({"scene_png_seconds_per_tile": scene("png")}))
+            return
+        grid()                                            # warm-up of both paths: plans, graph capture, first touch, page cache
+        scene("png")
+        scene("npy")
+        a, b = [], []
+        for _ in range(3):
+            a.append(grid())
+            b.append(scene("png"))
+        c = scene("npy")
+        x = torch.rand(64, 24, 32, 32, device="cuda")
+        with torch.no_grad():
+            for _ in range(2):
+                net(x)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(8):
+                net(x)
+            torch.cuda.synchronize()
+            t_model = (time.perf_counter() - t0) / 8
+        med = statistics.median
+        rec = {"workload": "whole 512 x 512 Sentinel-2 tiles (16 x 16 chunks of 8 frames), SSR_RRDBNet(nf=64, nb=23, gc=32), random weights, "
+                           "n_lr_images 8, batch 64, one GPU, one process; per-tile wall time of a driver call over all tiles",
+               "device": torch.cuda.get_device_name(0), "compute_dtype": mode, "tiles_per_repetition": n_tiles, "host_cores": png_io.host_cores(),
+               "io_workers": n_workers,
+               "chunk_files_infer_grid": {"files_per_tile": "256 chunk PNGs in, 256 chunk PNGs + 2 mosaics out",
+                                          "seconds_per_tile": a, "median": med(a), "spread": max(a) - min(a), "tiles_per_s": 1 / med(a)},
+               "scene_png_infer_scene": {"files_per_tile": "1 PNG [8*512, 512, 3] in, 2 mosaics out",
+                                         "seconds_per_tile": b, "median": med(b), "spread": max(b) - min(b), "tiles_per_s": 1 / med(b)},
+               "scene_npy_infer_scene": {"files_per_tile": "1 .npy [8, 512, 512, 3] in, 2 mosaics out", "seconds_per_tile": [c], "tiles_per_s": 1 / c},
+               "generator_only": {"ms_per_64_chunks": 1e3 * t_model, "seconds_per_tile": 4 * t_model, "tiles_per_s": 64 / t_model / 256},
+               "scene_over_chunk_files": med(b) / med(a),
+               "accepted": med(b) <= med(a) + (max(a) - min(a))}
+        print(json.dumps(rec))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
