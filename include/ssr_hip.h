@@ -431,6 +431,33 @@ int ssr_scene_gather(const uint8_t* scene, int32_t T, int32_t H, int32_t W, cons
 int ssr_scene_scatter_u8(ssr_view src, int32_t dtype, const int32_t* chunk_ids, int32_t B, int32_t C, uint8_t* mosaic, int32_t Ho,
                          int32_t Wo, int32_t* nonfinite, void* stream);
 
+/* ---- scene inference, overlapping chunks blended in the output (csrc/scene.hip; additive: the ABI version stays 3) ----
+ * H and W are ANY values >= 32 (SSR_EUNSUP below that).  The place of chunk b is origins[2b], origins[2b + 1] = (y0, x0), the
+ * low-resolution pixel of its first sample (a DEVICE array of int32 pairs); an item whose origin lies outside
+ * [0, H - 32] x [0, W - 32] (or one of whose frame ids lies outside [0, T)) is skipped: nothing is read or written for it.  The scene
+ * pointer needs no alignment: nothing outside the rows of a chunk is read.
+ * ssr_scene_zero_scan_at: has_zero[b*T + t] = 1 if any of the 3072 bytes of frame t of the window at origin b is 0, else 0.
+ * ssr_scene_gather_at: ssr_scene_gather with the chunk at the origin: the same x * fp32(1/255) and storage rounding, the same
+ *   conditions on dst, n and dtype.
+ * ssr_scene_blend_add: the generator's NHWC output (src: [B, 128, 128, cs], C <= 8 channels used, coff + C <= cs) is added into
+ *   acc, uint32 [Ho][Wo][C] (Ho = 4H, Wo = 4W, 16-byte aligned, zeroed by the caller): for sample v of pixel (r, col) of item b
+ *     f = (uint32) (fminf(fmaxf(v, 0), 1) * 65535.0f)         fp32 multiply, truncation; NaN -> 0
+ *     acc[4 y0 + r][4 x0 + col][c] += f * window[r] * window[col]
+ *   with window a DEVICE array int32[128] (weights <= 64, so one term stays below 2^28).  The adds are integer atomics: items of one
+ *   launch, and launches, may overlap, and the sums do not depend on the order of arrival.  The number of NaN / +-Inf samples among
+ *   the C channels is added to *nonfinite as ssr_scene_scatter_u8 does.  Ho or Wo below 128 or no multiple of 4: SSR_EUNSUP.
+ * ssr_scene_blend_finish: mosaic[y][x][c] = (uint8) ((uint64) acc[y][x][c] * 255 / ((uint64) Sy[y] * Sx[x] * 65535)), truncating as
+ *   the reference's quantiser does; Sy int32 [Ho] and Sx int32 [Wo] (device) are the sums of the window weights of the chunks that
+ *   cover the row / column (a zero sum gives 0).  mosaic is uint8 [Ho][Wo][C], 4-byte aligned. */
+int ssr_scene_zero_scan_at(const uint8_t* scene, int32_t T, int32_t H, int32_t W, const int32_t* origins, int32_t n_chunks,
+                           uint8_t* has_zero, void* stream);
+int ssr_scene_gather_at(const uint8_t* scene, int32_t T, int32_t H, int32_t W, const int32_t* origins, const int32_t* frame_ids,
+                        int32_t B, int32_t n, ssr_view dst, int32_t dtype, void* stream);
+int ssr_scene_blend_add(ssr_view src, int32_t dtype, const int32_t* origins, int32_t B, int32_t C, const int32_t* window,
+                        uint32_t* acc, int32_t Ho, int32_t Wo, int32_t* nonfinite, void* stream);
+int ssr_scene_blend_finish(const uint32_t* acc, const int32_t* Sy, const int32_t* Sx, int32_t C, uint8_t* mosaic, int32_t Ho,
+                           int32_t Wo, void* stream);
+
 /* ---- VGG19 perceptual loss glue (csrc/vgg.hip; the convolutions run through ssr_conv2d with SSR_ACT_RELU / m_relu) ----
  * ssr_channel_affine: y[p, c] (+)= x[p, c] * scale[c] + shift[c] for c < C <= 8 (host float arrays, copied into the launch):
  *   the input normalisation (x - mean) / std of the feature extractor and, with accumulate = 1, its adjoint.

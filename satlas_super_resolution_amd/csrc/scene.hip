@@ -12,6 +12,18 @@
 // super-resolved chunk 128 * C bytes of the mosaic, both 16-byte aligned when the base pointers are - the global accesses on the
 // byte side are uint4.  Chunk and frame ids come from device arrays; an id outside the scene makes its item a no-op (nothing is
 // read or written for it).
+//
+// Overlap-and-blend for scenes of ANY size >= 32 x 32 (super_resolve_scene_blended): chunks sit at arbitrary (y0, x0), given as a
+// device array of int32 pairs, overlap, and are cross-faded in the output in integer arithmetic.
+//
+//   ssr_scene_zero_scan_at   the zero test over the 32 x 32 windows at the origins
+//   ssr_scene_gather_at      ssr_scene_gather at the origins
+//   ssr_scene_blend_add      the plan's NHWC output -> 16-bit fixed point, times the window weight of its place in the chunk,
+//                            added (integer atomics: any arrival order gives the same words) into a uint32 accumulator
+//   ssr_scene_blend_finish   accumulator / weight sums -> the truncating uint8 mosaic
+//
+// Here a chunk row of the scene starts at any byte (W * 3 may be odd) and a mosaic row is only 4-byte aligned: rows are read as the
+// aligned words that lie inside them plus single bytes at the two ends, the mosaic is stored in aligned 4-byte units.
 #include "common.h"
 
 namespace {
@@ -150,6 +162,142 @@ __global__ __launch_bounds__(256) void scene_scatter_u8_kernel(ssr_view src, con
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---- chunks at arbitrary places (the overlap-and-blend path) ----
+constexpr int ROWB = CH * 3;       // bytes per chunk row of the scene
+constexpr int ROWW = ROWB / 4 + 1; // aligned 4-byte words that cover a chunk row starting at any byte
+
+// Word i (< ROWW) of the aligned words covering the ROWB bytes at `a` (any alignment): one word load where the word lies inside
+// the row, single byte loads at its two ends (nothing outside [a, a + ROWB) is read); bytes outside the row come back as 0xff.
+// Row byte j sits at byte (a & 3) + j of the words.
+__device__ __forceinline__ uint32_t row_word(const uint8_t* a, int i) {
+    const int sh = (int)(reinterpret_cast<uintptr_t>(a) & 3);
+    const int j0 = 4 * i - sh;                                    // row byte index of the word's first byte
+    if (j0 >= 0 && j0 + 4 <= ROWB) return *reinterpret_cast<const uint32_t*>(a + j0);
+    uint32_t v = 0xffffffffu;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int j = j0 + u;
+        if (j >= 0 && j < ROWB) v = (v & ~(0xffu << (8 * u))) | ((uint32_t)a[j] << (8 * u));
+    }
+    return v;
+}
+
+__device__ __forceinline__ bool origin_ok(int y0, int x0, int H, int W) { return y0 >= 0 && x0 >= 0 && y0 <= H - CH && x0 <= W - CH; }
+
+// one wave per (chunk, frame): CH rows x ROWW words, 0xff outside the rows
+__global__ __launch_bounds__(256) void scene_zero_scan_at_kernel(const uint8_t* __restrict__ scene, int T, int H, int W,
+                                                                 const int32_t* __restrict__ origins, int n_chunks,
+                                                                 uint8_t* __restrict__ has_zero) {
+    const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (long)n_chunks * T) return;                       // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const int chunk = (int)(item / T), t = (int)(item - (long)chunk * T);
+    const int y0 = origins[2 * chunk], x0 = origins[2 * chunk + 1];
+    if (!origin_ok(y0, x0, H, W)) return;                         // wave-uniform
+    const uint8_t* base = scene + (((long)t * H + y0) * W + x0) * 3;
+    bool z = false;
+    for (int e = lane; e < CH * ROWW; e += 64) {
+        const int row = e / ROWW, i = e - row * ROWW;
+        z |= has_zero_byte(row_word(base + (long)row * W * 3, i));
+    }
+    const bool any = __any(z);
+    if (lane == 0) has_zero[item] = any ? 1 : 0;
+}
+
+// scene_gather_kernel at an arbitrary origin: the rows go through LDS as their covering aligned words (n x ROWW words, and the n
+// byte offsets of the rows inside them), the conversion and the stores are the same
+template <typename T, int V>
+__global__ __launch_bounds__(256) void scene_gather_at_kernel(const uint8_t* __restrict__ scene, int T_, int H, int W,
+                                                              const int32_t* __restrict__ origins,
+                                                              const int32_t* __restrict__ frame_ids, int n, ssr_view dst) {
+    extern __shared__ uint32_t roww[];                            // [n][ROWW] words, then [n] byte offsets
+    uint32_t* shift = roww + n * ROWW;
+    const int b = blockIdx.x / CH, y = blockIdx.x - b * CH;
+    const int y0 = origins[2 * b], x0 = origins[2 * b + 1];
+    if (!origin_ok(y0, x0, H, W)) return;                         // block-uniform
+    for (int k = 0; k < n; ++k) {                                 // block-uniform: before any barrier
+        const int f = frame_ids[b * n + k];
+        if (f < 0 || f >= T_) return;
+    }
+    for (int e = threadIdx.x; e < n * ROWW; e += 256) {
+        const int k = e / ROWW, i = e - k * ROWW;
+        const long t = frame_ids[b * n + k];
+        const uint8_t* a = scene + ((t * H + y0 + y) * W + x0) * 3;
+        roww[e] = row_word(a, i);
+        if (i == 0) shift[k] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
+    }
+    __syncthreads();
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(roww);
+    const int C = 3 * n, groups = C / V;
+    T* __restrict__ d = reinterpret_cast<T*>(dst.p);
+    const long pix0 = ((long)b * CH + y) * CH;
+    for (int e = threadIdx.x; e < CH * groups; e += 256) {
+        const int x = e / groups, c0 = (e - x * groups) * V;
+        Pack<T, V> o;
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+            const int c = c0 + u, k = c / 3;
+            // x * (1.0f / 255.0f), then the storage type's rounding: scene_gather_kernel's arithmetic
+            o.v[u] = from_f32<T>((float)bytes[k * (4 * ROWW) + shift[k] + x * 3 + (c - 3 * k)] * INV255);
+        }
+        *reinterpret_cast<Pack<T, V>*>(d + (pix0 + x) * dst.cs + dst.coff + c0) = o;
+    }
+}
+
+// one wave per (batch item, row of its 128 x 128 output): the row's 128 C fixed-point samples, weighted, are added to 128 C
+// consecutive words of the accumulator - wave-instructions of 256 contiguous bytes.  Integer adds: the sums do not depend on the
+// order in which overlapping chunks arrive.
+template <typename T>
+__global__ __launch_bounds__(256) void scene_blend_add_kernel(ssr_view src, const int32_t* __restrict__ origins, int B, int C,
+                                                              const int32_t* __restrict__ window, uint32_t* __restrict__ acc,
+                                                              int Ho, int Wo, int32_t* __restrict__ nonfinite) {
+    const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (long)B * SR) return;                             // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const int b = (int)(item / SR), r = (int)(item - (long)b * SR);
+    const int y0 = origins[2 * b], x0 = origins[2 * b + 1];
+    if (!origin_ok(y0, x0, Ho / 4, Wo / 4)) return;               // wave-uniform
+    const T* __restrict__ s = reinterpret_cast<const T*>(src.p) + ((long)b * SR + r) * SR * src.cs + src.coff;
+    uint32_t* __restrict__ a = acc + (((long)4 * y0 + r) * Wo + (long)4 * x0) * C;
+    const uint32_t wr = (uint32_t)window[r];
+    int bad = 0;
+    for (int e = lane; e < SR * C; e += 64) {
+        const int x = e / C, c = e - x * C;
+        const float v = to_f32(s[(long)x * src.cs + c]);
+        bad += (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
+        // clamp(0, 1) (NaN -> 0 via fmaxf) * 65535 in fp32, truncated: 16 fractional bits of the sample
+        const uint32_t f = (uint32_t)(fminf(fmaxf(v, 0.f), 1.f) * 65535.0f);
+        atomicAdd(a + e, f * wr * (uint32_t)window[x]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_down(bad, o, 64);
+    if (lane == 0 && bad) atomicAdd(nonfinite, bad);
+}
+
+// one thread per aligned 4-byte unit of the mosaic (a row is Wo C bytes, Wo a multiple of 4)
+__global__ __launch_bounds__(256) void scene_blend_finish_kernel(const uint32_t* __restrict__ acc, const int32_t* __restrict__ Sy,
+                                                                 const int32_t* __restrict__ Sx, int C, uint32_t* __restrict__ mosaic,
+                                                                 int Ho, int Wo) {
+    const long roww_ = (long)Wo * C / 4;
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= roww_ * Ho) return;
+    const int y = (int)(q / roww_);
+    const int j0 = (int)(q - (long)y * roww_) * 4;                // first byte of the unit inside its row
+    const uint64_t sy = (uint64_t)Sy[y] * 65535u;
+    const u32x4 a4 = *reinterpret_cast<const u32x4*>(acc + 4 * q);   // the unit's 4 samples: 16 aligned bytes
+    uint32_t out = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int x = (j0 + u) / C;
+        const uint64_t den = sy * (uint64_t)Sx[x];
+        const uint64_t num = (uint64_t)a4[u] * 255u;
+        out |= (uint32_t)(den ? (num / den) & 0xff : 0) << (8 * u);
+    }
+    mosaic[q] = out;
+}
+
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
 }  // namespace
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
@@ -204,6 +352,71 @@ extern "C" int ssr_scene_scatter_u8(ssr_view src, int32_t dtype, const int32_t* 
         hipLaunchKernelGGL(scene_scatter_u8_kernel<float>, grid, block, 0, ST(stream), src, chunk_ids, C, mosaic, Ho, Wo, nonfinite);
     else
         hipLaunchKernelGGL(scene_scatter_u8_kernel<__bf16>, grid, block, 0, ST(stream), src, chunk_ids, C, mosaic, Ho, Wo, nonfinite);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_zero_scan_at(const uint8_t* scene, int32_t T, int32_t H, int32_t W, const int32_t* origins, int32_t n_chunks,
+                                      uint8_t* has_zero, void* stream) {
+    if (!scene || !origins || !has_zero || T <= 0 || H <= 0 || W <= 0 || n_chunks <= 0) return SSR_EINVAL;
+    if (H < CH || W < CH) return SSR_EUNSUP;
+    const long items = (long)n_chunks * T;
+    if (items > (1l << 30)) return SSR_EINVAL;
+    hipLaunchKernelGGL(scene_zero_scan_at_kernel, dim3((int)((items + 3) / 4)), dim3(256), 0, ST(stream), scene, T, H, W, origins,
+                       n_chunks, has_zero);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_gather_at(const uint8_t* scene, int32_t T, int32_t H, int32_t W, const int32_t* origins,
+                                   const int32_t* frame_ids, int32_t B, int32_t n, ssr_view dst, int32_t dtype, void* stream) {
+    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
+    if (!scene || !origins || !frame_ids || !dst.p || T <= 0 || H <= 0 || W <= 0 || B <= 0 || n <= 0) return SSR_EINVAL;
+    if (!aligned16(dst.p) || dst.cs % 8 || dst.coff % 8 || dst.coff < 0 || dst.coff + 3 * n > dst.cs || B > (1 << 20))
+        return SSR_EINVAL;
+    if (H < CH || W < CH || n > T || n > 512 || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
+    const dim3 grid(B * CH), block(256);
+    const size_t lds = (size_t)n * (ROWW + 1) * 4;
+    const int C = 3 * n;
+    if (dtype == SSR_F32) {
+        if (C % 4 == 0)
+            hipLaunchKernelGGL((scene_gather_at_kernel<float, 4>), grid, block, lds, ST(stream), scene, T, H, W, origins, frame_ids, n, dst);
+        else
+            hipLaunchKernelGGL((scene_gather_at_kernel<float, 1>), grid, block, lds, ST(stream), scene, T, H, W, origins, frame_ids, n, dst);
+    } else {
+        if (C % 8 == 0)
+            hipLaunchKernelGGL((scene_gather_at_kernel<__bf16, 8>), grid, block, lds, ST(stream), scene, T, H, W, origins, frame_ids, n, dst);
+        else
+            hipLaunchKernelGGL((scene_gather_at_kernel<__bf16, 1>), grid, block, lds, ST(stream), scene, T, H, W, origins, frame_ids, n, dst);
+    }
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_blend_add(ssr_view src, int32_t dtype, const int32_t* origins, int32_t B, int32_t C, const int32_t* window,
+                                   uint32_t* acc, int32_t Ho, int32_t Wo, int32_t* nonfinite, void* stream) {
+    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
+    if (!src.p || !origins || !window || !acc || !nonfinite || B <= 0 || C <= 0 || Ho <= 0 || Wo <= 0) return SSR_EINVAL;
+    if (!aligned4(src.p) || !aligned16(acc) || src.coff < 0 || src.coff + C > src.cs || C > MAX_C || B > (1 << 20)) return SSR_EINVAL;
+    if (Ho % 4 || Wo % 4 || Ho < SR || Wo < SR || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
+    const dim3 grid(B * (SR / 4)), block(256);
+    if (dtype == SSR_F32)
+        hipLaunchKernelGGL(scene_blend_add_kernel<float>, grid, block, 0, ST(stream), src, origins, B, C, window, acc, Ho, Wo, nonfinite);
+    else
+        hipLaunchKernelGGL(scene_blend_add_kernel<__bf16>, grid, block, 0, ST(stream), src, origins, B, C, window, acc, Ho, Wo, nonfinite);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_blend_finish(const uint32_t* acc, const int32_t* Sy, const int32_t* Sx, int32_t C, uint8_t* mosaic, int32_t Ho,
+                                      int32_t Wo, void* stream) {
+    if (!acc || !Sy || !Sx || !mosaic || C <= 0 || Ho <= 0 || Wo <= 0) return SSR_EINVAL;
+    if (!aligned16(acc) || !aligned4(mosaic) || C > MAX_C) return SSR_EINVAL;
+    if (Ho % 4 || Wo % 4 || Ho < SR || Wo < SR) return SSR_EUNSUP;
+    const long units = (long)Ho * Wo * C / 4, blocks = (units + 255) / 256;
+    if (blocks > 0x7fffffffl) return SSR_EUNSUP;
+    hipLaunchKernelGGL(scene_blend_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), acc, Sy, Sx, C,
+                       reinterpret_cast<uint32_t*>(mosaic), Ho, Wo);
     SSR_LAUNCH_CHECK();
     return SSR_OK;
 }

@@ -17,7 +17,12 @@ straight from the plan's output into the mosaic, and the count of non-finite out
 `png_io` worker processes while the device runs another scene.
 
 Option keys: `data_dir`, `save_path`, `n_lr_images`, `network_g`, `path.*`, `compute_dtype` (default fp32h), `batch` (chunks per
-generator launch, default 64), `io_workers` as `infer_grid`; `scene_hw: [H, W]` for PNG scenes that are not square."""
+generator launch, default 64), `io_workers` as `infer_grid`; `scene_hw: [H, W]` for PNG scenes that are not square.
+
+`overlap: K` (0 .. 16; absent: the path above, unchanged) takes scenes of ANY height and width >= 32 instead: chunks overlap their
+neighbours by K pixels, the last chunk of a row or column ends at the scene's edge, and the super-resolved chunks are cross-faded
+where they overlap (`super_resolve_scene_blended`), which removes the 128-pixel grid that chunks super-resolved alone leave in the
+mosaic.  The blend is integer arithmetic on the device, so runs stay bit-identical."""
 from __future__ import annotations
 
 import argparse
@@ -51,14 +56,62 @@ def select_scene_frames(has_zero: np.ndarray, n: int) -> np.ndarray:
     return out
 
 
-def check_scene_size(H: int, W: int) -> None:
-    if H <= 0 or W <= 0 or H % CHUNK or W % CHUNK:
+def check_scene_size(H: int, W: int, any_size: bool = False) -> None:
+    if any_size:
+        if H < CHUNK or W < CHUNK:
+            raise ValueError(f"scene of {H} x {W} pixels: height and width must be at least {CHUNK}")
+    elif H <= 0 or W <= 0 or H % CHUNK or W % CHUNK:
         raise ValueError(f"scene of {H} x {W} pixels: height and width must be multiples of {CHUNK}")
 
 
-def parse_scene(arr: np.ndarray, scene_hw: Optional[Sequence[int]] = None) -> np.ndarray:
+MAX_OVERLAP = CHUNK // 2
+SR_CHUNK = SCALE * CHUNK
+
+
+def scene_chunk_origins(L: int, overlap: int) -> List[int]:
+    """Where the 32-pixel chunks of the blended path start along an axis of L low-resolution pixels: 0, s, 2s, ... with the stride
+    s = 32 - overlap for as long as origin + 32 < L, then L - 32 (the last chunk ends at the scene's edge and overlaps its
+    neighbour by whatever is left).  0 <= overlap <= 16 and L >= 32, ValueError otherwise."""
+    L, ov = int(L), int(overlap)
+    if ov != overlap or not 0 <= ov <= MAX_OVERLAP:
+        raise ValueError(f"overlap = {overlap}: an integer from 0 to {MAX_OVERLAP}")
+    if L < CHUNK:
+        raise ValueError(f"a scene axis of {L} pixels is shorter than a chunk ({CHUNK})")
+    out, o = [], 0
+    while o + CHUNK < L:
+        out.append(o)
+        o += CHUNK - ov
+    return out + [L - CHUNK]
+
+
+def scene_chunk_grid(H: int, W: int, overlap: int) -> np.ndarray:
+    """int32 [chunks, 2]: (y0, x0) of every chunk, the cross product of the row and the column origins in row-major order"""
+    ys, xs = scene_chunk_origins(H, overlap), scene_chunk_origins(W, overlap)
+    return np.array([(y, x) for y in ys for x in xs], np.int32).reshape(-1, 2)
+
+
+def blend_window(overlap: int) -> np.ndarray:
+    """int32 [128]: the weight of row (or column) r of a super-resolved chunk, w[r] = min(r + 1, 128 - r, R), R = max(1, 4 overlap);
+    a sample's weight is w[r] * w[c].  Where two chunks overlap by `overlap` pixels the two ramps add up to R + 1: a linear
+    cross-fade.  Nothing is special at a scene edge: the division by the sum of the weights makes a lone chunk's sample itself."""
+    scene_chunk_origins(CHUNK, overlap)             # (the range check)
+    r = np.arange(SR_CHUNK)
+    return np.minimum(np.minimum(r + 1, SR_CHUNK - r), max(1, SCALE * int(overlap))).astype(np.int32)
+
+
+def blend_weight_sums(L: int, overlap: int) -> np.ndarray:
+    """int32 [4 L]: for every output row (column) the sum of `blend_window` over the chunks that cover it (>= 1, <= 125)"""
+    w = blend_window(overlap)
+    S = np.zeros(SCALE * int(L), np.int32)
+    for o in scene_chunk_origins(L, overlap):
+        S[SCALE * o:SCALE * o + SR_CHUNK] += w
+    return S
+
+
+def parse_scene(arr: np.ndarray, scene_hw: Optional[Sequence[int]] = None, any_size: bool = False) -> np.ndarray:
     """A scene file's array -> uint8 [T, H, W, 3].  [T, H, W, 3] (.npy) is taken as it is; [T*H, W, 3] (.png: the frames stacked on
-    the rows) is cut with H = scene_hw[0] (and W checked against scene_hw[1]) or, without scene_hw, as square frames H = W."""
+    the rows) is cut with H = scene_hw[0] (and W checked against scene_hw[1]) or, without scene_hw, as square frames H = W.  H and W
+    are multiples of 32, or with any_size (the blended path) anything from 32 up."""
     arr = np.asarray(arr)
     if arr.dtype != np.uint8 or arr.ndim not in (3, 4) or arr.shape[-1] != 3:
         raise ValueError(f"a scene is a uint8 array [T, H, W, 3] or [T*H, W, 3], not {arr.dtype} {tuple(arr.shape)}")
@@ -73,7 +126,7 @@ def parse_scene(arr: np.ndarray, scene_hw: Optional[Sequence[int]] = None) -> np
             raise ValueError(f"scene image of {rows} x {W} pixels: {rows} rows are not a whole number of frames of height {H}"
                              + ("" if scene_hw is not None else " (square frames are assumed: set scene_hw: [H, W])"))
         arr = arr.reshape(rows // H, H, W, 3)
-    check_scene_size(arr.shape[1], arr.shape[2])
+    check_scene_size(arr.shape[1], arr.shape[2], any_size)
     return arr
 
 
@@ -150,6 +203,75 @@ def scene_scatter_u8(src: torch.Tensor, chunk_ids: torch.Tensor, C: int, mosaic:
                                              mosaic.shape[1], _ptr(nonfinite), hip.stream_ptr()), "ssr_scene_scatter_u8")
 
 
+def _check_origins(origins: torch.Tensor):
+    assert origins.is_cuda and origins.dtype == torch.int32 and origins.is_contiguous() and origins.dim() == 2 and origins.shape[1] == 2, \
+        (origins.dtype, origins.shape)
+
+
+def scene_zero_scan_at(scene: torch.Tensor, origins: torch.Tensor) -> torch.Tensor:
+    """uint8 [T, H, W, 3] (H, W >= 32) and int32 [chunks, 2] origins (y0, x0), both on the device -> uint8 [chunks, T] on the device:
+    1 where frame t of the 32 x 32 window at the origin holds a zero sample; rows of origins outside the scene are not written"""
+    from . import hip
+    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
+    _check_origins(origins)
+    T, H, W = scene.shape[:3]
+    check_scene_size(H, W, True)
+    out = torch.zeros(origins.shape[0], T, dtype=torch.uint8, device=scene.device)
+    hip.check(hip.lib().ssr_scene_zero_scan_at(_ptr(scene), T, H, W, _ptr(origins), origins.shape[0], _ptr(out), hip.stream_ptr()),
+              "ssr_scene_zero_scan_at")
+    return out
+
+
+def scene_gather_at(scene: torch.Tensor, origins: torch.Tensor, frame_ids: torch.Tensor, dst: torch.Tensor, dtype: Optional[int] = None):
+    """`scene_gather` for chunks at the origins (int32 [B, 2], device) of a scene of any size >= 32 x 32"""
+    from . import hip
+    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
+    _check_origins(origins)
+    assert frame_ids.dtype == torch.int32 and frame_ids.is_cuda and frame_ids.is_contiguous()
+    T, H, W = scene.shape[:3]
+    check_scene_size(H, W, True)
+    B, n = frame_ids.shape
+    assert origins.shape[0] == B and tuple(dst.shape[:3]) == (B, CHUNK, CHUNK) and dst.shape[3] >= 3 * n, (origins.shape, dst.shape)
+    if dtype is None:
+        dtype = hip.dtype_code(dst.dtype)
+    hip.check(hip.lib().ssr_scene_gather_at(_ptr(scene), T, H, W, _ptr(origins), _ptr(frame_ids), B, n, hip.view(dst), dtype,
+                                            hip.stream_ptr()), "ssr_scene_gather_at")
+
+
+def _check_acc(acc: torch.Tensor, C: int):
+    assert acc.is_cuda and acc.dtype == torch.int32 and acc.is_contiguous() and acc.dim() == 3 and acc.shape[2] == C, (acc.dtype, acc.shape)
+
+
+def scene_blend_add(src: torch.Tensor, origins: torch.Tensor, C: int, window: torch.Tensor, acc: torch.Tensor,
+                    nonfinite: torch.Tensor, dtype: Optional[int] = None):
+    """src, an NHWC generator output [B, 128, 128, >= C], in 16-bit fixed point times the window weights (int32 [128], device) is
+    added to acc (int32 storage [Ho, Wo, C] on the device, read as uint32) at 4 x the origins; adds the number of non-finite
+    samples to the int32 device counter"""
+    from . import hip
+    B = origins.shape[0]
+    _check_origins(origins)
+    _check_acc(acc, C)
+    assert tuple(src.shape[:3]) == (B, SR_CHUNK, SR_CHUNK) and src.shape[3] >= C, src.shape
+    assert window.is_cuda and window.dtype == torch.int32 and window.is_contiguous() and tuple(window.shape) == (SR_CHUNK,)
+    assert nonfinite.dtype == torch.int32 and nonfinite.is_cuda
+    if dtype is None:
+        dtype = hip.dtype_code(src.dtype)
+    hip.check(hip.lib().ssr_scene_blend_add(hip.view(src), dtype, _ptr(origins), B, C, _ptr(window), _ptr(acc), acc.shape[0],
+                                            acc.shape[1], _ptr(nonfinite), hip.stream_ptr()), "ssr_scene_blend_add")
+
+
+def scene_blend_finish(acc: torch.Tensor, Sy: torch.Tensor, Sx: torch.Tensor, mosaic: torch.Tensor):
+    """acc [Ho, Wo, C] over the weight sums Sy (int32 [Ho]) and Sx (int32 [Wo]) -> mosaic, uint8 [Ho, Wo, C], truncating"""
+    from . import hip
+    Ho, Wo, C = acc.shape
+    _check_acc(acc, C)
+    assert mosaic.is_cuda and mosaic.dtype == torch.uint8 and mosaic.is_contiguous() and tuple(mosaic.shape) == (Ho, Wo, C)
+    for S, L in ((Sy, Ho), (Sx, Wo)):
+        assert S.is_cuda and S.dtype == torch.int32 and S.is_contiguous() and tuple(S.shape) == (L,)
+    hip.check(hip.lib().ssr_scene_blend_finish(_ptr(acc), _ptr(Sy), _ptr(Sx), C, _ptr(mosaic), Ho, Wo, hip.stream_ptr()),
+              "ssr_scene_blend_finish")
+
+
 class _Pending:
     """a scene whose launches are queued: the pinned host buffer its mosaic and counter are being copied to, and the event behind
     that copy"""
@@ -167,6 +289,27 @@ class _Pending:
         return img.numpy()
 
 
+def _upload_scene(model, frames, n: int, any_size: bool = False) -> Tuple[torch.Tensor, int]:
+    """the checks of the scene and of the generator's channels, the upload: (uint8 [T, H, W, 3] on the model's device, num_out_ch)"""
+    dev = next(model.parameters()).device
+    if isinstance(frames, torch.Tensor):
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError(f"a scene is a uint8 array [T, H, W, 3], not {frames.dtype} {tuple(frames.shape)}")
+        check_scene_size(frames.shape[1], frames.shape[2], any_size)
+        scene = frames.to(dev, non_blocking=True).contiguous()
+    else:
+        arr = np.asarray(frames)
+        if arr.ndim != 4:
+            raise ValueError(f"a scene is a uint8 array [T, H, W, 3], not {arr.dtype} {tuple(arr.shape)}")
+        arr = parse_scene(arr, any_size=any_size)
+        arr = np.ascontiguousarray(arr) if arr.flags.writeable else np.array(arr)      # (a read-only mapping of a .npy file: copy)
+        scene = torch.from_numpy(arr).to(dev, non_blocking=True)
+    C_in, C_out = model.kwargs["num_in_ch"], model.kwargs["num_out_ch"]
+    if C_in != 3 * n:
+        raise ValueError(f"n_lr_images = {n} gives {3 * n} input channels, the generator takes {C_in}")
+    return scene, C_out
+
+
 def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[torch.Tensor] = None) -> _Pending:
     """upload, zero scan, frame choice (the one host round trip: chunks x T flags down, chunks x n ids up), then every batch of
     chunks through gather -> generator -> scatter and the download of mosaic + counter; returns without waiting for them"""
@@ -175,23 +318,9 @@ def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[t
     n, batch = int(n_lr_images), int(batch)
     if batch < 1:
         raise ValueError(f"batch = {batch}")
-    dev = next(model.parameters()).device
-    if isinstance(frames, torch.Tensor):
-        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
-            raise ValueError(f"a scene is a uint8 array [T, H, W, 3], not {frames.dtype} {tuple(frames.shape)}")
-        check_scene_size(frames.shape[1], frames.shape[2])
-        scene = frames.to(dev, non_blocking=True).contiguous()
-    else:
-        arr = np.asarray(frames)
-        if arr.ndim != 4:
-            raise ValueError(f"a scene is a uint8 array [T, H, W, 3], not {arr.dtype} {tuple(arr.shape)}")
-        arr = parse_scene(arr)
-        arr = np.ascontiguousarray(arr) if arr.flags.writeable else np.array(arr)      # (a read-only mapping of a .npy file: copy)
-        scene = torch.from_numpy(arr).to(dev, non_blocking=True)
+    scene, C_out = _upload_scene(model, frames, n)
+    dev = scene.device
     T, H, W = scene.shape[:3]
-    C_in, C_out = model.kwargs["num_in_ch"], model.kwargs["num_out_ch"]
-    if C_in != 3 * n:
-        raise ValueError(f"n_lr_images = {n} gives {3 * n} input channels, the generator takes {C_in}")
     gw, n_chunks = W // CHUNK, (H // CHUNK) * (W // CHUNK)
     has_zero = scene_zero_scan(scene).cpu().numpy()
     frame_ids = torch.from_numpy(select_scene_frames(has_zero, n)).to(dev, non_blocking=True)
@@ -218,6 +347,65 @@ def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[t
     return _Pending(host, ev, (Ho, Wo, C_out), getattr(model, "compute_dtype", None), n_chunks)
 
 
+def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch: int, host: Optional[torch.Tensor] = None) -> _Pending:
+    """`_enqueue_scene` for a scene of any size >= 32 x 32 cut into chunks that overlap: upload, zero scan at the origins, frame
+    choice (the one host round trip), a zeroed accumulator, every batch of chunks through gather -> generator -> blend-add, the
+    division by the weight sums and the download of mosaic + counter"""
+    if getattr(model, "scale", SCALE) != SCALE:
+        raise NotImplementedError(f"scene inference runs scale {SCALE} generators only (scale = {model.scale})")
+    n, batch = int(n_lr_images), int(batch)
+    if batch < 1:
+        raise ValueError(f"batch = {batch}")
+    window = blend_window(overlap)                  # (refuses a bad overlap before anything is uploaded)
+    scene, C_out = _upload_scene(model, frames, n, any_size=True)
+    dev = scene.device
+    T, H, W = scene.shape[:3]
+    grid = scene_chunk_grid(H, W, overlap)
+    n_chunks = grid.shape[0]
+    origins = torch.from_numpy(grid).to(dev, non_blocking=True)
+    window = torch.from_numpy(window).to(dev, non_blocking=True)
+    Sy = torch.from_numpy(blend_weight_sums(H, overlap)).to(dev, non_blocking=True)
+    Sx = torch.from_numpy(blend_weight_sums(W, overlap)).to(dev, non_blocking=True)
+    has_zero = scene_zero_scan_at(scene, origins).cpu().numpy()
+    frame_ids = torch.from_numpy(select_scene_frames(has_zero, n)).to(dev, non_blocking=True)
+    Ho, Wo = SCALE * H, SCALE * W
+    nb = Ho * Wo * C_out
+    off = -(-nb // 16) * 16
+    buf = torch.empty(off + 4, dtype=torch.uint8, device=dev)       # the mosaic and, behind it, the counter: one download
+    counter = buf[off:].view(torch.int32)
+    counter.zero_()
+    mosaic = buf[:nb].view(Ho, Wo, C_out)
+    acc = torch.zeros(Ho, Wo, C_out, dtype=torch.int32, device=dev)  # 4 bytes per output sample, this scene's own
+    with torch.no_grad():
+        for c0 in range(0, n_chunks, batch):
+            org = origins[c0:c0 + batch]
+            plan = model.plan_for_inference(org.shape[0], CHUNK, CHUNK)
+            scene_gather_at(scene, org, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
+            model.run_forward(plan)
+            scene_blend_add(plan.out, org, C_out, window, acc, counter, plan.dt)
+        scene_blend_finish(acc, Sy, Sx, mosaic)
+    del acc
+    if host is None or host.numel() != buf.numel():
+        host = torch.empty(buf.shape, dtype=torch.uint8, pin_memory=True)
+    host.copy_(buf, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record()
+    return _Pending(host, ev, (Ho, Wo, C_out), getattr(model, "compute_dtype", None), n_chunks)
+
+
+def super_resolve_scene_blended(model, frames, n_lr_images: int, overlap: int = 8, batch: int = 64) -> np.ndarray:
+    """frames: uint8 [T, H, W, 3] (numpy array or CUDA tensor), H and W ANY values >= 32 -> uint8 [4H, 4W, 3].  The scene is cut into
+    32 x 32 chunks that overlap their neighbours by `overlap` pixels (0 .. 16; `scene_chunk_origins`: the last chunk of an axis ends
+    at the scene's edge), every chunk is super-resolved from `n_lr_images` of its frames (select_scene_frames over the chunks in
+    row-major order) and the outputs are cross-faded where they overlap (`blend_window`), in integer arithmetic on the device: the
+    bytes do not depend on the batch size or the order of the chunks.
+    The accumulator holds 4 bytes per output sample (48 H W bytes: 50 MB for 512 x 512, 23 GB for a whole 10980 x 10980
+    acquisition) and is allocated per scene, next to the scene itself and the 12 H W bytes of the mosaic.
+    Refusals as `super_resolve_scene`: scale 4 generators only, n_lr_images against the generator's channels, FloatingPointError
+    (metrics.nonfinite_error) if any output sample is NaN / Inf."""
+    return _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch).result()
+
+
 def super_resolve_scene(model, frames, n_lr_images: int, batch: int = 64) -> np.ndarray:
     """frames: uint8 [T, H, W, 3] (numpy array or CUDA tensor), H and W multiples of 32 (ValueError otherwise) -> uint8
     [4H, 4W, 3]: every 32 x 32 chunk super-resolved on its own from `n_lr_images` of its frames (select_scene_frames) and placed
@@ -231,6 +419,10 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
     from .infer_grid import load_generator
     data_dir, save_path, n_lr_images = opt["data_dir"], opt["save_path"], int(opt["n_lr_images"])
     batch, scene_hw = int(opt.get("batch", 64)), opt.get("scene_hw")
+    overlap = opt.get("overlap")                    # absent: every chunk on its own (the reference's mosaic); 0 .. 16: blended
+    blended = overlap is not None
+    if blended:
+        scene_chunk_origins(CHUNK, overlap)
     if device is None:
         device = torch.device("cuda")
     if model is None:
@@ -275,10 +467,10 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
         def finish_read(rd) -> Tuple[str, object, np.ndarray]:
             name, blk, fut, what = rd
             if blk is None:
-                return name, None, parse_scene(np.asarray(what), scene_hw)
+                return name, None, parse_scene(np.asarray(what), scene_hw, blended)
             got = fut.result()[0]
             arr = got if isinstance(got, np.ndarray) else blk.buf[:int(np.prod(got))].reshape(got)
-            return name, blk, parse_scene(arr, scene_hw)
+            return name, blk, parse_scene(arr, scene_hw, blended)
 
         def submit_save(arr: np.ndarray, path: str):
             """one image to an encoder through a block of its own (closed and unlinked as soon as the file is written)"""
@@ -299,7 +491,10 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
             if k < len(mine):
                 name, blk, frames = finish_read(reading)
                 reading = start_read(k + 1) if k + 1 < len(mine) else None
-                pending = _enqueue_scene(model, frames, n_lr_images, batch, hosts[k & 1])
+                if blended:
+                    pending = _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, hosts[k & 1])
+                else:
+                    pending = _enqueue_scene(model, frames, n_lr_images, batch, hosts[k & 1])
                 hosts[k & 1] = pending.host
                 cur = (name, np.array(frames[0]), pending)          # (the upload has been waited for: the flags came back)
                 del frames

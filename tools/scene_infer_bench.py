@@ -10,6 +10,14 @@ two tiles are a window of a tenth of a second, too short to time); after a warm-
 
     python tools/scene_infer_bench.py [mode] [tiles] > profiles/scene_infer/bench.json
     rocprofv3 --kernel-trace --stats ... -- python tools/scene_infer_bench.py fp32h 8 --scene-only      (warm-up + one run of (b))
+
+`--overlap K` runs another leg INSTEAD: one 512 x 512 scene of 8 frames through `super_resolve_scene` (256 chunks, each alone) and
+through `super_resolve_scene_blended(overlap=K)` (chunks overlapping by K pixels, cross-faded on the device), alternating three times
+after a warm-up of both, upload to download, no files; then a 500 x 731 scene, which only the blended path takes.  The generator
+dominates, so the expected ratio of the two is the ratio of the chunk counts.  `--blend-only` (with `--overlap K`): the warm-up and
+one blended run of the 512 x 512 scene, for a kernel trace.
+
+    python tools/scene_infer_bench.py fp32h --overlap 8 > profiles/scene_blend/bench.json
 """
 import json
 import os
@@ -24,7 +32,62 @@ import numpy as np
 import torch
 
 
+def _scene(rng, T, H, W):
+    """smooth field + noise, no black samples"""
+    yy, xx = np.mgrid[0:H, 0:W]
+    base = 110 + 60 * np.sin(yy / 19.0)[None, :, :, None] * np.cos(xx / 11.0)[None, :, :, None]
+    return np.clip(base + rng.randint(-12, 13, (T, H, W, 3)), 1, 255).astype(np.uint8)
+
+
+def blend_leg(mode, overlap, blend_only):
+    from satlas_super_resolution_amd.archs.rrdbnet_arch import SSR_RRDBNet
+    from satlas_super_resolution_amd.infer_scene import scene_chunk_origins, super_resolve_scene, super_resolve_scene_blended
+    rng = np.random.RandomState(0)
+    square, odd = _scene(rng, 8, 512, 512), _scene(rng, 8, 500, 731)
+    net = SSR_RRDBNet(24, 3, 4, 64, 23, 32, compute_dtype=mode).cuda().eval().freeze_packed()
+
+    def timed(fn, *a, **kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn(net, *a, **kw)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    timed(super_resolve_scene_blended, square, 8, overlap=overlap)      # warm-up: plans, graph capture, first touch
+    if blend_only:
+        print(json.dumps({"blended_seconds": timed(super_resolve_scene_blended, square, 8, overlap=overlap)[0]}))
+        return
+    timed(super_resolve_scene, square, 8)
+    timed(super_resolve_scene_blended, odd, 8, overlap=overlap)        # (the ragged last batch's plan)
+    a, b = [], []
+    for _ in range(3):
+        a.append(timed(super_resolve_scene, square, 8)[0])
+        b.append(timed(super_resolve_scene_blended, square, 8, overlap=overlap)[0])
+    c = [timed(super_resolve_scene_blended, odd, 8, overlap=overlap)[0] for _ in range(2)]
+    _, plain = timed(super_resolve_scene, square, 8)
+    _, zero = timed(super_resolve_scene_blended, square, 8, overlap=0)
+    n_sq = len(scene_chunk_origins(512, overlap)) ** 2
+    n_odd = len(scene_chunk_origins(500, overlap)) * len(scene_chunk_origins(731, overlap))
+    med = statistics.median
+    diff = np.abs(plain.astype(np.int16) - zero.astype(np.int16))
+    print(json.dumps({
+        "workload": "one Sentinel-2 scene of 8 frames, SSR_RRDBNet(nf=64, nb=23, gc=32), random weights, n_lr_images 8, batch 64, one GPU; "
+                    "wall time of one call, upload to download, no files",
+        "device": torch.cuda.get_device_name(0), "compute_dtype": mode, "overlap": overlap,
+        "scene_512x512": {"chunks": 256, "seconds": a, "median": med(a), "spread": max(a) - min(a)},
+        "blended_512x512": {"chunks": n_sq, "seconds": b, "median": med(b), "spread": max(b) - min(b)},
+        "blended_500x731": {"chunks": n_odd, "seconds": c, "seconds_per_chunk": min(c) / n_odd},
+        "blended_over_scene": med(b) / med(a), "expected_chunk_count_ratio": n_sq / 256,
+        "seconds_per_chunk": {"scene": med(a) / 256, "blended": med(b) / n_sq},
+        "overlap_0_against_scene": {"largest_difference_levels": int(diff.max()), "differing_samples": int((diff > 0).sum()),
+                                    "samples": int(diff.size)}}))
+
+
 def main():
+    if "--overlap" in sys.argv:
+        k = sys.argv.index("--overlap")
+        rest = [a for a in sys.argv[1:k] + sys.argv[k + 2:] if not a.startswith("--")]
+        return blend_leg(rest[0] if rest else "fp32h", int(sys.argv[k + 1]), "--blend-only" in sys.argv)
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     scene_only = "--scene-only" in sys.argv
     mode = args[0] if len(args) > 0 else "fp32h"
