@@ -458,6 +458,22 @@ int ssr_scene_blend_add(ssr_view src, int32_t dtype, const int32_t* origins, int
 int ssr_scene_blend_finish(const uint32_t* acc, const int32_t* Sy, const int32_t* Sx, int32_t C, uint8_t* mosaic, int32_t Ho,
                            int32_t Wo, void* stream);
 
+/* ---- scene inference for multi-band generators (csrc/scene.hip; additive: the ABI version stays 3) ----
+ * The option `s2_bands: [tci, b05, ...]` of the dataset at inference: beside the TCI scene, uint8 [T][H][W][3], lie K >= 1 extra
+ * bands as uint8 [K][T][H][W], one plane per band (a band PNG decodes straight into its plane).  Neither pointer needs an alignment.
+ * ssr_scene_gather_bands: ssr_scene_gather_at with 3 + K channels per chosen frame.  For item b, pixel (y, x), slot s < n and
+ *   f = frame_ids[b*n + s], (y0, x0) = origins[2b], origins[2b + 1]: channel s*(3 + K) + c of dst is tci[f][y0 + y][x0 + x][c] for
+ *   c < 3 and bands[c - 3][f][y0 + y][x0 + x] otherwise - frame-major, TCI first, then the bands in the order given, which is
+ *   S2NAIPDataset._load_s2(...)[frames].reshape(-1, 32, 32) - each x * fp32(1/255), then rounded to the storage type, as
+ *   ssr_scene_gather does.  Channels n*(3 + K) .. cs of the view are not written; grid chunks are the origins (32 i, 32 j).  An item
+ *   whose origin lies outside [0, H - 32] x [0, W - 32] or one of whose frame ids lies outside [0, T) is skipped: nothing is read
+ *   or written for it.  A null pointer, K < 1 or n*(3 + K) channels that do not fit the view: SSR_EINVAL; H or W below 32, n > T,
+ *   n > 512, more than 64 KiB of row staging (n*(26 + 10 K) words) or an unknown dtype: SSR_EUNSUP.  The zero test stays
+ *   ssr_scene_zero_scan(_at) over the TCI: the extra bands take no part in the choice of frames. */
+int ssr_scene_gather_bands(const uint8_t* tci, const uint8_t* bands, int32_t K, int32_t T, int32_t H, int32_t W,
+                           const int32_t* origins, const int32_t* frame_ids, int32_t B, int32_t n, ssr_view dst, int32_t dtype,
+                           void* stream);
+
 /* ---- VGG19 perceptual loss glue (csrc/vgg.hip; the convolutions run through ssr_conv2d with SSR_ACT_RELU / m_relu) ----
  * ssr_channel_affine: y[p, c] (+)= x[p, c] * scale[c] + shift[c] for c < C <= 8 (host float arrays, copied into the launch):
  *   the input normalisation (x - mean) / std of the feature extractor and, with accumulate = 1, its adjoint.

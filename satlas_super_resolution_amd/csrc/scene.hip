@@ -22,6 +22,10 @@
 //                            added (integer atomics: any arrival order gives the same words) into a uint32 accumulator
 //   ssr_scene_blend_finish   accumulator / weight sums -> the truncating uint8 mosaic
 //
+// Multi-band generators (`s2_bands: [tci, b05, ...]`): K extra bands lie beside the TCI as uint8 [K][T][H][W], one plane per band.
+//
+//   ssr_scene_gather_bands   ssr_scene_gather_at with 3 + K channels per chosen frame: the TCI pixel, then the K band samples
+//
 // Here a chunk row of the scene starts at any byte (W * 3 may be odd) and a mosaic row is only 4-byte aligned: rows are read as the
 // aligned words that lie inside them plus single bytes at the two ends, the mosaic is stored in aligned 4-byte units.
 #include "common.h"
@@ -166,18 +170,19 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 constexpr int ROWB = CH * 3;       // bytes per chunk row of the scene
 constexpr int ROWW = ROWB / 4 + 1; // aligned 4-byte words that cover a chunk row starting at any byte
 
-// Word i (< ROWW) of the aligned words covering the ROWB bytes at `a` (any alignment): one word load where the word lies inside
-// the row, single byte loads at its two ends (nothing outside [a, a + ROWB) is read); bytes outside the row come back as 0xff.
-// Row byte j sits at byte (a & 3) + j of the words.
+// Word i (<= LEN / 4) of the aligned words covering the LEN bytes at `a` (any alignment; LEN = ROWB for a TCI row, CH for a row of
+// a band plane): one word load where the word lies inside the row, single byte loads at its two ends (nothing outside
+// [a, a + LEN) is read); bytes outside the row come back as 0xff.  Row byte j sits at byte (a & 3) + j of the words.
+template <int LEN>
 __device__ __forceinline__ uint32_t row_word(const uint8_t* a, int i) {
     const int sh = (int)(reinterpret_cast<uintptr_t>(a) & 3);
     const int j0 = 4 * i - sh;                                    // row byte index of the word's first byte
-    if (j0 >= 0 && j0 + 4 <= ROWB) return *reinterpret_cast<const uint32_t*>(a + j0);
+    if (j0 >= 0 && j0 + 4 <= LEN) return *reinterpret_cast<const uint32_t*>(a + j0);
     uint32_t v = 0xffffffffu;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int j = j0 + u;
-        if (j >= 0 && j < ROWB) v = (v & ~(0xffu << (8 * u))) | ((uint32_t)a[j] << (8 * u));
+        if (j >= 0 && j < LEN) v = (v & ~(0xffu << (8 * u))) | ((uint32_t)a[j] << (8 * u));
     }
     return v;
 }
@@ -198,7 +203,7 @@ __global__ __launch_bounds__(256) void scene_zero_scan_at_kernel(const uint8_t* 
     bool z = false;
     for (int e = lane; e < CH * ROWW; e += 64) {
         const int row = e / ROWW, i = e - row * ROWW;
-        z |= has_zero_byte(row_word(base + (long)row * W * 3, i));
+        z |= has_zero_byte(row_word<ROWB>(base + (long)row * W * 3, i));
     }
     const bool any = __any(z);
     if (lane == 0) has_zero[item] = any ? 1 : 0;
@@ -223,7 +228,7 @@ __global__ __launch_bounds__(256) void scene_gather_at_kernel(const uint8_t* __r
         const int k = e / ROWW, i = e - k * ROWW;
         const long t = frame_ids[b * n + k];
         const uint8_t* a = scene + ((t * H + y0 + y) * W + x0) * 3;
-        roww[e] = row_word(a, i);
+        roww[e] = row_word<ROWB>(a, i);
         if (i == 0) shift[k] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
     }
     __syncthreads();
@@ -239,6 +244,66 @@ __global__ __launch_bounds__(256) void scene_gather_at_kernel(const uint8_t* __r
             const int c = c0 + u, k = c / 3;
             // x * (1.0f / 255.0f), then the storage type's rounding: scene_gather_kernel's arithmetic
             o.v[u] = from_f32<T>((float)bytes[k * (4 * ROWW) + shift[k] + x * 3 + (c - 3 * k)] * INV255);
+        }
+        *reinterpret_cast<Pack<T, V>*>(d + (pix0 + x) * dst.cs + dst.coff + c0) = o;
+    }
+}
+
+// scene_gather_at_kernel for 3 + K channels per chosen frame: the n TCI rows (n x ROWW words) and the n K rows of the band planes
+// (n K x BANDW words, slot-major) go through LDS as their covering aligned words, behind them the byte offsets of the rows inside
+// their words.  Channel s (3 + K) + c of a pixel is the TCI sample c < 3 of slot s, else band c - 3.  The row strides (25 and 9
+// words) are odd: the byte reads of consecutive channels, which step from one row to the next, spread over the banks.
+constexpr int BANDW = CH / 4 + 1;  // aligned 4-byte words that cover a row of a band plane starting at any byte
+
+template <typename T, int V>
+__global__ __launch_bounds__(256) void scene_gather_bands_kernel(const uint8_t* __restrict__ tci, const uint8_t* __restrict__ bands,
+                                                                 int K, int T_, int H, int W, const int32_t* __restrict__ origins,
+                                                                 const int32_t* __restrict__ frame_ids, int n, ssr_view dst) {
+    extern __shared__ uint32_t roww[];                            // [n][ROWW], [n K][BANDW] words, then [n] and [n K] byte offsets
+    uint32_t* bandw = roww + n * ROWW;
+    uint32_t* shift = bandw + n * K * BANDW;
+    uint32_t* bshift = shift + n;
+    const int b = blockIdx.x / CH, y = blockIdx.x - b * CH;
+    const int y0 = origins[2 * b], x0 = origins[2 * b + 1];
+    if (!origin_ok(y0, x0, H, W)) return;                         // block-uniform
+    for (int s = 0; s < n; ++s) {                                 // block-uniform: before any barrier
+        const int f = frame_ids[b * n + s];
+        if (f < 0 || f >= T_) return;
+    }
+    const int tci_words = n * ROWW;
+    for (int e = threadIdx.x; e < tci_words + n * K * BANDW; e += 256) {
+        if (e < tci_words) {
+            const int s = e / ROWW, i = e - s * ROWW;
+            const long t = frame_ids[b * n + s];
+            const uint8_t* a = tci + ((t * H + y0 + y) * W + x0) * 3;
+            roww[e] = row_word<ROWB>(a, i);
+            if (i == 0) shift[s] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
+        } else {
+            const int r = (e - tci_words) / BANDW, i = (e - tci_words) - r * BANDW;      // r = s K + band
+            const int s = r / K, kb = r - s * K;
+            const long t = frame_ids[b * n + s];
+            const uint8_t* a = bands + (((long)kb * T_ + t) * H + y0 + y) * W + x0;
+            bandw[r * BANDW + i] = row_word<CH>(a, i);
+            if (i == 0) bshift[r] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
+        }
+    }
+    __syncthreads();
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(roww);
+    const uint8_t* bbytes = reinterpret_cast<const uint8_t*>(bandw);
+    const int F = 3 + K, C = n * F, groups = C / V;
+    T* __restrict__ d = reinterpret_cast<T*>(dst.p);
+    const long pix0 = ((long)b * CH + y) * CH;
+    for (int e = threadIdx.x; e < CH * groups; e += 256) {
+        const int x = e / groups, c0 = (e - x * groups) * V;
+        int s = c0 / F, c = c0 - s * F;                           // slot and channel inside the slot of the pack's first element
+        Pack<T, V> o;
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+            const int r = s * K + c - 3;
+            const uint8_t v = c < 3 ? bytes[s * (4 * ROWW) + shift[s] + x * 3 + c] : bbytes[r * (4 * BANDW) + bshift[r] + x];
+            // x * (1.0f / 255.0f), then the storage type's rounding: scene_gather_kernel's arithmetic
+            o.v[u] = from_f32<T>((float)v * INV255);
+            if (++c == F) { c = 0; ++s; }
         }
         *reinterpret_cast<Pack<T, V>*>(d + (pix0 + x) * dst.cs + dst.coff + c0) = o;
     }
@@ -388,6 +453,31 @@ extern "C" int ssr_scene_gather_at(const uint8_t* scene, int32_t T, int32_t H, i
             hipLaunchKernelGGL((scene_gather_at_kernel<__bf16, 8>), grid, block, lds, ST(stream), scene, T, H, W, origins, frame_ids, n, dst);
         else
             hipLaunchKernelGGL((scene_gather_at_kernel<__bf16, 1>), grid, block, lds, ST(stream), scene, T, H, W, origins, frame_ids, n, dst);
+    }
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_gather_bands(const uint8_t* tci, const uint8_t* bands, int32_t K, int32_t T, int32_t H, int32_t W,
+                                      const int32_t* origins, const int32_t* frame_ids, int32_t B, int32_t n, ssr_view dst,
+                                      int32_t dtype, void* stream) {
+    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
+    if (!tci || !bands || !origins || !frame_ids || !dst.p || K <= 0 || T <= 0 || H <= 0 || W <= 0 || B <= 0 || n <= 0) return SSR_EINVAL;
+    const long C = (long)n * (3 + (long)K);
+    if (!aligned16(dst.p) || dst.cs % 8 || dst.coff % 8 || dst.coff < 0 || dst.coff + C > dst.cs || B > (1 << 20)) return SSR_EINVAL;
+    const size_t lds = ((size_t)n * (ROWW + 1) + (size_t)n * K * (BANDW + 1)) * 4;
+    if (H < CH || W < CH || n > T || n > 512 || lds > 65536 || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
+    const dim3 grid(B * CH), block(256);
+    if (dtype == SSR_F32) {
+        if (C % 4 == 0)
+            hipLaunchKernelGGL((scene_gather_bands_kernel<float, 4>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, n, dst);
+        else
+            hipLaunchKernelGGL((scene_gather_bands_kernel<float, 1>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, n, dst);
+    } else {
+        if (C % 8 == 0)
+            hipLaunchKernelGGL((scene_gather_bands_kernel<__bf16, 8>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, n, dst);
+        else
+            hipLaunchKernelGGL((scene_gather_bands_kernel<__bf16, 1>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, n, dst);
     }
     SSR_LAUNCH_CHECK();
     return SSR_OK;

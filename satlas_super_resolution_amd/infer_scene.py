@@ -17,12 +17,19 @@ straight from the plan's output into the mosaic, and the count of non-finite out
 `png_io` worker processes while the device runs another scene.
 
 Option keys: `data_dir`, `save_path`, `n_lr_images`, `network_g`, `path.*`, `compute_dtype` (default fp32h), `batch` (chunks per
-generator launch, default 64), `io_workers` as `infer_grid`; `scene_hw: [H, W]` for PNG scenes that are not square.
+generator launch, default 64), `io_workers` as `infer_grid`; `scene_hw: [H, W]` for PNG scenes that are not square; `s2_bands`.
 
 `overlap: K` (0 .. 16; absent: the path above, unchanged) takes scenes of ANY height and width >= 32 instead: chunks overlap their
 neighbours by K pixels, the last chunk of a row or column ends at the scene's edge, and the super-resolved chunks are cross-faded
 where they overlap (`super_resolve_scene_blended`), which removes the 128-pixel grid that chunks super-resolved alone leave in the
-mosaic.  The blend is integer arithmetic on the device, so runs stay bit-identical."""
+mosaic.  The blend is integer arithmetic on the device, so runs stay bit-identical.
+
+`s2_bands: [tci, b05, b08, ...]` (the dataset's option; absent: the paths above, unchanged) runs multi-band generators, which take
+`n_lr_images * (3 + K)` channels: a scene is then the DIRECTORY `{data_dir}/NAME/` with `tci.png` ([T*H, W, 3]) and one 8-bit
+grayscale `<band>.png` ([T*H, W]) per extra band - the dataset's `sentinel2/{tile}/{band}.png`, so a split's `sentinel2` folder is a
+`data_dir`.  `tci` goes first, the other bands follow in their order, a missing band file contributes zeros, as in
+`S2NAIPDataset`; the extra bands take no part in the choice of frames.  `super_resolve_scene(_blended)(..., bands=)` takes them as
+uint8 [K, T, H, W]."""
 from __future__ import annotations
 
 import argparse
@@ -142,6 +149,45 @@ def list_scenes(data_dir: str) -> List[Tuple[str, str]]:
     return sorted(found.items())
 
 
+def order_s2_bands(bands: Sequence[str]) -> List[str]:
+    """`s2_bands` as the dataset orders it (data/s2naip_dataset.py): `tci`, which is required, first, the rest in their order"""
+    bands = [str(b) for b in bands]
+    if "tci" not in bands:
+        raise ValueError(f"s2_bands = {bands}: 'tci' is required")
+    bands.insert(0, bands.pop(bands.index("tci")))
+    return bands
+
+
+def list_band_scenes(data_dir: str, bands: Sequence[str]) -> List[Tuple[str, str, List[Optional[str]]]]:
+    """[(NAME, path of tci.png, [path of <band>.png or None where the file is missing, per extra band])] of the scene directories
+    `data_dir/NAME/` (those that hold a tci.png), sorted by NAME; bands as `s2_bands` (any order, `tci` among them)"""
+    extra = order_s2_bands(bands)[1:]
+    out = []
+    for name in sorted(os.listdir(data_dir)):
+        tci = os.path.join(data_dir, name, "tci.png")
+        if os.path.isfile(tci):
+            paths = [os.path.join(data_dir, name, b + ".png") for b in extra]
+            out.append((name, tci, [p if os.path.isfile(p) else None for p in paths]))
+    return out
+
+
+def band_scene_shape(tci_path: str, band_paths: Sequence[Optional[str]]) -> Tuple[int, int]:
+    """(rows, W) of a band scene's tci.png, from the files' headers; ValueError naming the file for a band file of another size or
+    one that is not 8-bit grayscale"""
+    from PIL import Image
+    rows, W, _ = _png_shape(tci_path)
+    for p in band_paths:
+        if p is None:
+            continue
+        with Image.open(p) as im:          # header only
+            (w, h), mode = im.size, im.mode
+        if mode != "L":
+            raise ValueError(f"{p}: a band file is an 8-bit grayscale PNG, not mode {mode!r}")
+        if (h, w) != (rows, W):
+            raise ValueError(f"{p}: {h} x {w} pixels, {os.path.basename(tci_path)} beside it has {rows} x {W}")
+    return rows, W
+
+
 def scenes_of_rank(scenes: Sequence, rank: int, world: int) -> List:
     """rank r takes scenes r, r + world, ... of the sorted list (no collective, no barrier: every scene is one rank's own)"""
     return list(scenes[rank::world])
@@ -238,6 +284,27 @@ def scene_gather_at(scene: torch.Tensor, origins: torch.Tensor, frame_ids: torch
                                             hip.stream_ptr()), "ssr_scene_gather_at")
 
 
+def scene_gather_bands(scene: torch.Tensor, bands: torch.Tensor, origins: torch.Tensor, frame_ids: torch.Tensor, dst: torch.Tensor,
+                       dtype: Optional[int] = None):
+    """`scene_gather_at` with the K extra bands (uint8 [K, T, H, W], device) behind the TCI of every chosen frame: 3 + K channels
+    per frame, dst [B, 32, 32, >= n (3 + K)]"""
+    from . import hip
+    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
+    T, H, W = scene.shape[:3]
+    assert bands.is_cuda and bands.dtype == torch.uint8 and bands.is_contiguous() and bands.dim() == 4 and bands.shape[0] >= 1 \
+        and tuple(bands.shape[1:]) == (T, H, W), (bands.dtype, bands.shape, scene.shape)
+    _check_origins(origins)
+    assert frame_ids.dtype == torch.int32 and frame_ids.is_cuda and frame_ids.is_contiguous()
+    check_scene_size(H, W, True)
+    K = bands.shape[0]
+    B, n = frame_ids.shape
+    assert origins.shape[0] == B and tuple(dst.shape[:3]) == (B, CHUNK, CHUNK) and dst.shape[3] >= (3 + K) * n, (origins.shape, dst.shape)
+    if dtype is None:
+        dtype = hip.dtype_code(dst.dtype)
+    hip.check(hip.lib().ssr_scene_gather_bands(_ptr(scene), _ptr(bands), K, T, H, W, _ptr(origins), _ptr(frame_ids), B, n,
+                                               hip.view(dst), dtype, hip.stream_ptr()), "ssr_scene_gather_bands")
+
+
 def _check_acc(acc: torch.Tensor, C: int):
     assert acc.is_cuda and acc.dtype == torch.int32 and acc.is_contiguous() and acc.dim() == 3 and acc.shape[2] == C, (acc.dtype, acc.shape)
 
@@ -289,9 +356,28 @@ class _Pending:
         return img.numpy()
 
 
-def _upload_scene(model, frames, n: int, any_size: bool = False) -> Tuple[torch.Tensor, int]:
-    """the checks of the scene and of the generator's channels, the upload: (uint8 [T, H, W, 3] on the model's device, num_out_ch)"""
+def _check_bands(model, frames, bands, n: int):
+    """the refusals of a `bands` argument, before anything is uploaded: uint8 [K, T, H, W] with the frames' T, H, W and a generator
+    of n (3 + K) channels"""
+    if not isinstance(bands, torch.Tensor):
+        bands = np.asarray(bands)
+    u8 = torch.uint8 if isinstance(bands, torch.Tensor) else np.uint8
+    if bands.dtype != u8 or len(bands.shape) != 4 or bands.shape[0] < 1:
+        raise ValueError(f"bands are a uint8 array [K, T, H, W], not {bands.dtype} {tuple(bands.shape)}")
+    if len(frames.shape) == 4 and tuple(bands.shape[1:]) != tuple(frames.shape[:3]):
+        raise ValueError(f"bands of T, H, W = {tuple(bands.shape[1:])} beside frames of T, H, W = {tuple(frames.shape[:3])}")
+    K, C_in = int(bands.shape[0]), model.kwargs["num_in_ch"]
+    if C_in != n * (3 + K):
+        raise ValueError(f"n_lr_images = {n} with {K} extra band(s) gives {n * (3 + K)} input channels, the generator takes {C_in}")
+    return bands
+
+
+def _upload_scene(model, frames, n: int, any_size: bool = False, bands=None) -> Tuple[torch.Tensor, int, Optional[torch.Tensor]]:
+    """the checks of the scene and of the generator's channels, the upload: (uint8 [T, H, W, 3] on the model's device, num_out_ch,
+    the bands as uint8 [K, T, H, W] on that device or None)"""
     dev = next(model.parameters()).device
+    if bands is not None:
+        bands = _check_bands(model, frames if isinstance(frames, torch.Tensor) else np.asarray(frames), bands, n)
     if isinstance(frames, torch.Tensor):
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
             raise ValueError(f"a scene is a uint8 array [T, H, W, 3], not {frames.dtype} {tuple(frames.shape)}")
@@ -305,26 +391,33 @@ def _upload_scene(model, frames, n: int, any_size: bool = False) -> Tuple[torch.
         arr = np.ascontiguousarray(arr) if arr.flags.writeable else np.array(arr)      # (a read-only mapping of a .npy file: copy)
         scene = torch.from_numpy(arr).to(dev, non_blocking=True)
     C_in, C_out = model.kwargs["num_in_ch"], model.kwargs["num_out_ch"]
-    if C_in != 3 * n:
-        raise ValueError(f"n_lr_images = {n} gives {3 * n} input channels, the generator takes {C_in}")
-    return scene, C_out
+    if bands is None:
+        if C_in != 3 * n:
+            raise ValueError(f"n_lr_images = {n} gives {3 * n} input channels, the generator takes {C_in}")
+        return scene, C_out, None
+    if not isinstance(bands, torch.Tensor):
+        bands = torch.from_numpy(np.ascontiguousarray(bands) if bands.flags.writeable else np.array(bands))
+    return scene, C_out, bands.to(dev, non_blocking=True).contiguous()
 
 
-def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[torch.Tensor] = None) -> _Pending:
+def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[torch.Tensor] = None, bands=None) -> _Pending:
     """upload, zero scan, frame choice (the one host round trip: chunks x T flags down, chunks x n ids up), then every batch of
-    chunks through gather -> generator -> scatter and the download of mosaic + counter; returns without waiting for them"""
+    chunks through gather -> generator -> scatter and the download of mosaic + counter; returns without waiting for them.
+    With bands the gather is `scene_gather_bands` at the chunks' origins (32 i, 32 j); everything else is the same."""
     if getattr(model, "scale", SCALE) != SCALE:
         raise NotImplementedError(f"scene inference runs scale {SCALE} generators only (scale = {model.scale})")
     n, batch = int(n_lr_images), int(batch)
     if batch < 1:
         raise ValueError(f"batch = {batch}")
-    scene, C_out = _upload_scene(model, frames, n)
+    scene, C_out, bands = _upload_scene(model, frames, n, bands=bands)
     dev = scene.device
     T, H, W = scene.shape[:3]
     gw, n_chunks = W // CHUNK, (H // CHUNK) * (W // CHUNK)
     has_zero = scene_zero_scan(scene).cpu().numpy()
     frame_ids = torch.from_numpy(select_scene_frames(has_zero, n)).to(dev, non_blocking=True)
     chunk_ids = torch.arange(n_chunks, dtype=torch.int32, device=dev)
+    if bands is not None:
+        origins = torch.from_numpy(scene_chunk_grid(H, W, 0)).to(dev, non_blocking=True)    # (32 i, 32 j) in row-major order
     Ho, Wo = SCALE * H, SCALE * W
     nb = Ho * Wo * C_out
     off = -(-nb // 16) * 16
@@ -336,7 +429,10 @@ def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[t
         for c0 in range(0, n_chunks, batch):
             ids = chunk_ids[c0:c0 + batch]
             plan = model.plan_for_inference(ids.shape[0], CHUNK, CHUNK)
-            scene_gather(scene, ids, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
+            if bands is None:
+                scene_gather(scene, ids, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
+            else:
+                scene_gather_bands(scene, bands, origins[c0:c0 + batch], frame_ids[c0:c0 + batch], plan.xin, plan.dt)
             model.run_forward(plan)
             scene_scatter_u8(plan.out, ids, C_out, mosaic, counter, plan.dt)
     if host is None or host.numel() != buf.numel():
@@ -347,7 +443,8 @@ def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[t
     return _Pending(host, ev, (Ho, Wo, C_out), getattr(model, "compute_dtype", None), n_chunks)
 
 
-def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch: int, host: Optional[torch.Tensor] = None) -> _Pending:
+def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch: int, host: Optional[torch.Tensor] = None,
+                           bands=None) -> _Pending:
     """`_enqueue_scene` for a scene of any size >= 32 x 32 cut into chunks that overlap: upload, zero scan at the origins, frame
     choice (the one host round trip), a zeroed accumulator, every batch of chunks through gather -> generator -> blend-add, the
     division by the weight sums and the download of mosaic + counter"""
@@ -357,7 +454,7 @@ def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch:
     if batch < 1:
         raise ValueError(f"batch = {batch}")
     window = blend_window(overlap)                  # (refuses a bad overlap before anything is uploaded)
-    scene, C_out = _upload_scene(model, frames, n, any_size=True)
+    scene, C_out, bands = _upload_scene(model, frames, n, any_size=True, bands=bands)
     dev = scene.device
     T, H, W = scene.shape[:3]
     grid = scene_chunk_grid(H, W, overlap)
@@ -380,7 +477,10 @@ def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch:
         for c0 in range(0, n_chunks, batch):
             org = origins[c0:c0 + batch]
             plan = model.plan_for_inference(org.shape[0], CHUNK, CHUNK)
-            scene_gather_at(scene, org, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
+            if bands is None:
+                scene_gather_at(scene, org, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
+            else:
+                scene_gather_bands(scene, bands, org, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
             model.run_forward(plan)
             scene_blend_add(plan.out, org, C_out, window, acc, counter, plan.dt)
         scene_blend_finish(acc, Sy, Sx, mosaic)
@@ -393,7 +493,7 @@ def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch:
     return _Pending(host, ev, (Ho, Wo, C_out), getattr(model, "compute_dtype", None), n_chunks)
 
 
-def super_resolve_scene_blended(model, frames, n_lr_images: int, overlap: int = 8, batch: int = 64) -> np.ndarray:
+def super_resolve_scene_blended(model, frames, n_lr_images: int, overlap: int = 8, batch: int = 64, bands=None) -> np.ndarray:
     """frames: uint8 [T, H, W, 3] (numpy array or CUDA tensor), H and W ANY values >= 32 -> uint8 [4H, 4W, 3].  The scene is cut into
     32 x 32 chunks that overlap their neighbours by `overlap` pixels (0 .. 16; `scene_chunk_origins`: the last chunk of an axis ends
     at the scene's edge), every chunk is super-resolved from `n_lr_images` of its frames (select_scene_frames over the chunks in
@@ -402,15 +502,19 @@ def super_resolve_scene_blended(model, frames, n_lr_images: int, overlap: int = 
     The accumulator holds 4 bytes per output sample (48 H W bytes: 50 MB for 512 x 512, 23 GB for a whole 10980 x 10980
     acquisition) and is allocated per scene, next to the scene itself and the 12 H W bytes of the mosaic.
     Refusals as `super_resolve_scene`: scale 4 generators only, n_lr_images against the generator's channels, FloatingPointError
-    (metrics.nonfinite_error) if any output sample is NaN / Inf."""
-    return _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch).result()
+    (metrics.nonfinite_error) if any output sample is NaN / Inf.  `bands` as `super_resolve_scene`."""
+    return _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, bands=bands).result()
 
 
-def super_resolve_scene(model, frames, n_lr_images: int, batch: int = 64) -> np.ndarray:
+def super_resolve_scene(model, frames, n_lr_images: int, batch: int = 64, bands=None) -> np.ndarray:
     """frames: uint8 [T, H, W, 3] (numpy array or CUDA tensor), H and W multiples of 32 (ValueError otherwise) -> uint8
     [4H, 4W, 3]: every 32 x 32 chunk super-resolved on its own from `n_lr_images` of its frames (select_scene_frames) and placed
-    at rows 128 i, columns 128 j.  Raises FloatingPointError (metrics.nonfinite_error) if any output sample is NaN / Inf."""
-    return _enqueue_scene(model, frames, n_lr_images, batch).result()
+    at rows 128 i, columns 128 j.  Raises FloatingPointError (metrics.nonfinite_error) if any output sample is NaN / Inf.
+    bands: uint8 [K, T, H, W] (numpy array or CUDA tensor), the K extra Sentinel-2 bands of a multi-band generator, which then takes
+    n_lr_images * (3 + K) channels - per chosen frame the TCI, then the bands in their order, what `S2NAIPDataset` with `s2_bands`
+    feeds it in training; the frames are chosen on the TCI alone.  ValueError, before anything is uploaded, for bands of another
+    rank, dtype or T, H, W than the frames' and for a generator of another channel count."""
+    return _enqueue_scene(model, frames, n_lr_images, batch, bands=bands).result()
 
 
 # ------------------------------------------------------------------------------------------------ driver
@@ -427,7 +531,9 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
         device = torch.device("cuda")
     if model is None:
         model = load_generator(opt, device)
-    scenes = list_scenes(data_dir)
+    s2_bands = opt.get("s2_bands")                  # absent: scene files NAME.png / NAME.npy; given: scene directories NAME/<band>.png
+    K = 0 if s2_bands is None else len(order_s2_bands(s2_bands)) - 1
+    scenes = list_scenes(data_dir) if s2_bands is None else list_band_scenes(data_dir, s2_bands)
     if rank == 0:
         print("Running inference on ", len(scenes), " scenes.")
     mine = scenes_of_rank(scenes, rank, world)
@@ -457,20 +563,36 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
 
         def start_read(k):
             """scene k's pixels on their way to host memory: a PNG is decoded by a worker into a one-shot block, a .npy is mapped"""
+            if s2_bands is not None:
+                return start_read_bands(*mine[k])
             name, path = mine[k]
             if path.lower().endswith(".npy"):
                 return name, None, None, np.load(path, mmap_mode="r")
             shape = _png_shape(path)
             blk = block(int(np.prod(shape)), "scene")
-            return name, blk, pool.submit("read_into", [path], blk.path, blk.nbytes, [0], blk.nbytes, True), shape
+            return name, blk, [pool.submit("read_into", [path], blk.path, blk.nbytes, [0], blk.nbytes, True)], shape
 
-        def finish_read(rd) -> Tuple[str, object, np.ndarray]:
-            name, blk, fut, what = rd
+        def start_read_bands(name, tci, band_paths):
+            """a scene directory: tci.png and every band file that exists are decoded side by side into one block - the TCI first,
+            behind it the K planes [K][T*H][W]; the plane of a missing band stays zero (the block is new)"""
+            rows, W = band_scene_shape(tci, band_paths)          # (refuses a band file of another size or mode by name)
+            npix = rows * W
+            blk = block((3 + K) * npix, "scene")
+            futs = [pool.submit("read_into", [tci], blk.path, blk.nbytes, [0], 3 * npix, True)]
+            futs += [pool.submit("read_gray_into", p, blk.path, blk.nbytes, (3 + kb) * npix, (rows, W), True)
+                     for kb, p in enumerate(band_paths) if p is not None]
+            return name, blk, futs, (rows, W, 3)
+
+        def finish_read(rd) -> Tuple[str, object, np.ndarray, Optional[np.ndarray]]:
+            name, blk, futs, what = rd
             if blk is None:
-                return name, None, parse_scene(np.asarray(what), scene_hw, blended)
-            got = fut.result()[0]
+                return name, None, parse_scene(np.asarray(what), scene_hw, blended), None
+            got = [f.result() for f in futs][0][0]
             arr = got if isinstance(got, np.ndarray) else blk.buf[:int(np.prod(got))].reshape(got)
-            return name, blk, parse_scene(arr, scene_hw, blended)
+            frames = parse_scene(arr, scene_hw, blended)
+            if not K:
+                return name, blk, frames, None
+            return name, blk, frames, blk.buf[frames.size:].reshape((K,) + frames.shape[:3])
 
         def submit_save(arr: np.ndarray, path: str):
             """one image to an encoder through a block of its own (closed and unlinked as soon as the file is written)"""
@@ -489,15 +611,15 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
         for k in range(len(mine) + 1):
             cur = None
             if k < len(mine):
-                name, blk, frames = finish_read(reading)
+                name, blk, frames, bands = finish_read(reading)
                 reading = start_read(k + 1) if k + 1 < len(mine) else None
                 if blended:
-                    pending = _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, hosts[k & 1])
+                    pending = _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, hosts[k & 1], bands=bands)
                 else:
-                    pending = _enqueue_scene(model, frames, n_lr_images, batch, hosts[k & 1])
+                    pending = _enqueue_scene(model, frames, n_lr_images, batch, hosts[k & 1], bands=bands)
                 hosts[k & 1] = pending.host
                 cur = (name, np.array(frames[0]), pending)          # (the upload has been waited for: the flags came back)
-                del frames
+                del frames, bands
                 if blk is not None:
                     release(blk)
             if prev is not None:

@@ -202,6 +202,26 @@ def read_into(paths: Sequence[str], shm_path: str, nbytes: int, offsets: Sequenc
     return out
 
 
+def read_gray_into(path: str, shm_path: str, nbytes: int, offset: int, shape: Sequence[int], transient: bool = False):
+    """decode an 8-bit grayscale PNG of `shape` = (rows, width) into the block at `offset`, as it is (one plane of a band stack);
+    a file of another mode or size is refused by name"""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode != "L" or (im.size[1], im.size[0]) != tuple(shape):
+            raise ValueError(f"{path}: mode {im.mode!r}, {im.size[1]} x {im.size[0]} pixels; expected 8-bit grayscale, "
+                             f"{shape[0]} x {shape[1]}")
+        a = np.asarray(im)
+        n = int(shape[0]) * int(shape[1])
+        assert 0 <= offset and offset + n <= nbytes, (offset, n, nbytes)
+        e = _open_map(shm_path, nbytes) if transient else None
+        m = e[0] if transient else _map(shm_path, nbytes)
+        m[offset:offset + n] = a.reshape(-1)
+    if transient:
+        del m
+        _close_map(e)
+    return tuple(shape)
+
+
 def save_from(shm_path: str, nbytes: int, items: Sequence[Tuple[int, Tuple[int, ...], str]], transient: bool = False) -> int:
     """encode and write the images that lie at (offset, shape) in the block.  transient: a one-shot block (a tile's mosaic) -
     mapped, encoded and unmapped here, so that the driver's unlink really frees it"""
@@ -225,7 +245,7 @@ def timed(name: str, *args):
 
 
 _TASKS = {"read_many": read_many, "save_many": save_many, "stitch_and_save": stitch_and_save, "stitch_from_dir": stitch_from_dir,
-          "read_into": read_into, "save_from": save_from, "timed": timed}
+          "read_into": read_into, "read_gray_into": read_gray_into, "save_from": save_from, "timed": timed}
 
 
 class PngWorkerPool:

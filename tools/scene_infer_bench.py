@@ -18,6 +18,12 @@ dominates, so the expected ratio of the two is the ratio of the chunk counts.  `
 one blended run of the 512 x 512 scene, for a kernel trace.
 
     python tools/scene_infer_bench.py fp32h --overlap 8 > profiles/scene_blend/bench.json
+
+`--bands K` runs another leg INSTEAD: the same 512 x 512 scene of 8 frames with K extra bands (uint8 [K, 8, 512, 512]) through
+`super_resolve_scene(..., bands=)` and a generator of 8 (3 + K) channels; K = 0 is the TCI path and its 24-channel generator.  A
+warm-up and three timed calls; for the gather's share of device time, trace one run at K = 9 and one at K = 0:
+
+    rocprofv3 --kernel-trace --stats ... -- python tools/scene_infer_bench.py fp32h --bands 9
 """
 import json
 import os
@@ -83,7 +89,31 @@ def blend_leg(mode, overlap, blend_only):
                                     "samples": int(diff.size)}}))
 
 
+def bands_leg(mode, K):
+    from satlas_super_resolution_amd.archs.rrdbnet_arch import SSR_RRDBNet
+    from satlas_super_resolution_amd.infer_scene import super_resolve_scene
+    rng = np.random.RandomState(0)
+    tci = _scene(rng, 8, 512, 512)
+    bands = np.ascontiguousarray(_scene(rng, 8 * K, 512, 512)[..., 0].reshape(K, 8, 512, 512)) if K else None
+    net = SSR_RRDBNet(8 * (3 + K), 3, 4, 64, 23, 32, compute_dtype=mode).cuda().eval().freeze_packed()
+    secs = []
+    for _ in range(4):                              # the first call is the warm-up: plans, graph capture, first touch
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        super_resolve_scene(net, tci, 8, bands=bands)
+        torch.cuda.synchronize()
+        secs.append(time.perf_counter() - t0)
+    print(json.dumps({"workload": "one 512 x 512 Sentinel-2 scene of 8 frames, SSR_RRDBNet(nf=64, nb=23, gc=32), random weights, "
+                                  "n_lr_images 8, batch 64, one GPU; wall time of one call, upload to download, no files",
+                      "device": torch.cuda.get_device_name(0), "compute_dtype": mode, "extra_bands": K, "input_channels": 8 * (3 + K),
+                      "warm_up_seconds": secs[0], "seconds": secs[1:], "median": statistics.median(secs[1:])}))
+
+
 def main():
+    if "--bands" in sys.argv:
+        k = sys.argv.index("--bands")
+        rest = [a for a in sys.argv[1:k] + sys.argv[k + 2:] if not a.startswith("--")]
+        return bands_leg(rest[0] if rest else "fp32h", int(sys.argv[k + 1]))
     if "--overlap" in sys.argv:
         k = sys.argv.index("--overlap")
         rest = [a for a in sys.argv[1:k] + sys.argv[k + 2:] if not a.startswith("--")]
