@@ -474,6 +474,26 @@ int ssr_scene_gather_bands(const uint8_t* tci, const uint8_t* bands, int32_t K, 
                            const int32_t* origins, const int32_t* frame_ids, int32_t B, int32_t n, ssr_view dst, int32_t dtype,
                            void* stream);
 
+/* ---- scene inference, each chunk's clearest frames chosen on the device (csrc/scene.hip; additive: the ABI version stays 3) ----
+ * The option `frame_select: clearest`.  Both entries replace, for that policy, the frame choice of `select_frames` /
+ * format_s2naip_data (ssr/utils/infer_utils.py:12-31: `random.sample` among the frames without a zero sample); the policy itself is
+ * this project's own and has no counterpart file in the reference.  ESA's TCI encodes 0 as NODATA and 255 as SATURATED.
+ * ssr_scene_frame_keys: for frame t of the 32 x 32 window at origins[2b], origins[2b + 1] = (y0, x0) of the TCI scene uint8
+ *   [T][H][W][3] (H, W >= 32, SSR_EUNSUP below that; no alignment needed, nothing outside the rows of a window is read)
+ *     z = pixels with AT LEAST ONE zero sample among R, G, B       (z > 0 is ssr_scene_zero_scan_at's flag)
+ *     s = pixels whose THREE samples are all 255                   (never also in z: z + s <= 1024)
+ *     keys[b*T + t] = (z << 16) | s
+ *   keys is a DEVICE array uint32 [n_chunks][T], 4-byte aligned; the T words of an origin outside [0, H - 32] x [0, W - 32] are not
+ *   written.  A null pointer, a size <= 0 or more than 2^30 items: SSR_EINVAL.
+ * ssr_scene_rank_frames: frame_ids[b*n + r] = the frame of rank r < n among the T frames of chunk b ordered by (key, frame index)
+ *   ascending - fewest NODATA pixels first, then fewest saturated ones, then the lower index - an exact integer ranking without
+ *   atomics: every run writes the same words.  frame_ids is the int32 [n_chunks][n] DEVICE array the three gather entries read.
+ *   Because z leads the key every frame without a zero precedes every frame with one: the chosen SET is one the reference's rule
+ *   can draw.  T > 1024 or n > T: SSR_EUNSUP; a null pointer or a size <= 0: SSR_EINVAL. */
+int ssr_scene_frame_keys(const uint8_t* scene, int32_t T, int32_t H, int32_t W, const int32_t* origins, int32_t n_chunks,
+                         uint32_t* keys, void* stream);
+int ssr_scene_rank_frames(const uint32_t* keys, int32_t n_chunks, int32_t T, int32_t n, int32_t* frame_ids, void* stream);
+
 /* ---- VGG19 perceptual loss glue (csrc/vgg.hip; the convolutions run through ssr_conv2d with SSR_ACT_RELU / m_relu) ----
  * ssr_channel_affine: y[p, c] (+)= x[p, c] * scale[c] + shift[c] for c < C <= 8 (host float arrays, copied into the launch):
  *   the input normalisation (x - mean) / std of the feature extractor and, with accumulate = 1, its adjoint.

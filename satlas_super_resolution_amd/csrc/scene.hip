@@ -26,6 +26,12 @@
 //
 //   ssr_scene_gather_bands   ssr_scene_gather_at with 3 + K channels per chosen frame: the TCI pixel, then the K band samples
 //
+// Frame choice on the device (`frame_select: clearest`, this project's own policy: the reference has no counterpart file): per
+// (chunk, frame) a key that counts the window's NODATA and saturated pixels, per chunk the n frames of the smallest (key, index).
+//
+//   ssr_scene_frame_keys     per (chunk at an origin, frame): (pixels with a zero sample << 16) | pixels that are (255, 255, 255)
+//   ssr_scene_rank_frames    per chunk: its T keys ranked by (key, frame index), the first n frame indices -> frame_ids
+//
 // Here a chunk row of the scene starts at any byte (W * 3 may be odd) and a mosaic row is only 4-byte aligned: rows are read as the
 // aligned words that lie inside them plus single bytes at the two ends, the mosaic is stored in aligned 4-byte units.
 #include "common.h"
@@ -207,6 +213,66 @@ __global__ __launch_bounds__(256) void scene_zero_scan_at_kernel(const uint8_t* 
     }
     const bool any = __any(z);
     if (lane == 0) has_zero[item] = any ? 1 : 0;
+}
+
+// one block per (chunk, frame): the window's CH rows go through LDS as their covering aligned words (CH x ROWW words, behind them
+// the byte offsets of the rows inside their words - 3 W may be odd, so every row has its own), then 4 whole pixels per thread, three
+// bytes each wherever they lie in the words.  A pixel counts in z (a zero sample) or in s (all three 255), never in both: one packed
+// sum (z << 16) + s, at most 1024 in either half, is the key.  Shuffles inside a wave, one LDS step over the 4 waves.
+constexpr int KEYW = CH * ROWW;    // words of a staged window
+
+__global__ __launch_bounds__(256) void scene_frame_keys_kernel(const uint8_t* __restrict__ scene, int T, int H, int W,
+                                                               const int32_t* __restrict__ origins, uint32_t* __restrict__ keys) {
+    __shared__ uint32_t win[KEYW + CH + 4];                       // [CH][ROWW] words, [CH] byte offsets, the 4 waves' sums
+    uint32_t* shift = win + KEYW;
+    uint32_t* part = shift + CH;
+    const int chunk = blockIdx.x / T, t = blockIdx.x - chunk * T;
+    const int y0 = origins[2 * chunk], x0 = origins[2 * chunk + 1];
+    if (!origin_ok(y0, x0, H, W)) return;                         // block-uniform: before any barrier
+    const uint8_t* base = scene + (((long)t * H + y0) * W + x0) * 3;
+    for (int e = threadIdx.x; e < KEYW; e += 256) {
+        const int row = e / ROWW, i = e - row * ROWW;
+        const uint8_t* a = base + (long)row * W * 3;
+        win[e] = row_word<ROWB>(a, i);
+        if (i == 0) shift[row] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
+    }
+    __syncthreads();
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(win);
+    uint32_t zs = 0;
+#pragma unroll
+    for (int k = 0; k < CH * CH / 256; ++k) {
+        const int p = threadIdx.x + 256 * k, row = p / CH, x = p - row * CH;
+        const uint8_t* px = bytes + row * (4 * ROWW) + shift[row] + 3 * x;
+        const uint32_t r = px[0], g = px[1], b = px[2];
+        zs += (r == 0 || g == 0 || b == 0) ? 0x10000u : ((r & g & b) == 0xffu ? 1u : 0u);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) zs += __shfl_down(zs, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = zs;
+    __syncthreads();
+    if (threadIdx.x == 0) keys[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// one wave per chunk (a block of 64): the chunk's T keys in LDS, one lane per frame i (a strided loop beyond 64 frames) counts the
+// frames that come before it in the order (key, index) - every lane reads the same word, a broadcast - and, if fewer than n do,
+// writes i at that place.  The ranks are a permutation of 0 .. T - 1: every place below n is written exactly once.
+constexpr int MAX_T = 1024;        // frames ssr_scene_rank_frames accepts
+
+__global__ __launch_bounds__(64) void scene_rank_frames_kernel(const uint32_t* __restrict__ keys, int T, int n,
+                                                               int32_t* __restrict__ frame_ids) {
+    __shared__ uint32_t k[MAX_T];
+    const long chunk = blockIdx.x;
+    for (int i = threadIdx.x; i < T; i += 64) k[i] = keys[chunk * T + i];
+    __syncthreads();
+    for (int i = threadIdx.x; i < T; i += 64) {
+        const uint32_t ki = k[i];
+        int rank = 0;
+        for (int j = 0; j < T; ++j) {
+            const uint32_t kj = k[j];
+            rank += (kj < ki) || (kj == ki && j < i);
+        }
+        if (rank < n) frame_ids[chunk * n + rank] = i;
+    }
 }
 
 // scene_gather_kernel at an arbitrary origin: the rows go through LDS as their covering aligned words (n x ROWW words, and the n
@@ -479,6 +545,26 @@ extern "C" int ssr_scene_gather_bands(const uint8_t* tci, const uint8_t* bands, 
         else
             hipLaunchKernelGGL((scene_gather_bands_kernel<__bf16, 1>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, n, dst);
     }
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_frame_keys(const uint8_t* scene, int32_t T, int32_t H, int32_t W, const int32_t* origins, int32_t n_chunks,
+                                    uint32_t* keys, void* stream) {
+    if (!scene || !origins || !keys || T <= 0 || H <= 0 || W <= 0 || n_chunks <= 0 || !aligned4(keys)) return SSR_EINVAL;
+    if (H < CH || W < CH) return SSR_EUNSUP;
+    const long items = (long)n_chunks * T;
+    if (items > (1l << 30)) return SSR_EINVAL;
+    hipLaunchKernelGGL(scene_frame_keys_kernel, dim3((int)items), dim3(256), 0, ST(stream), scene, T, H, W, origins, keys);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_rank_frames(const uint32_t* keys, int32_t n_chunks, int32_t T, int32_t n, int32_t* frame_ids, void* stream) {
+    if (!keys || !frame_ids || n_chunks <= 0 || T <= 0 || n <= 0 || !aligned4(keys) || !aligned4(frame_ids)) return SSR_EINVAL;
+    if (T > MAX_T || n > T) return SSR_EUNSUP;
+    if ((long)n_chunks * T > (1l << 30)) return SSR_EINVAL;
+    hipLaunchKernelGGL(scene_rank_frames_kernel, dim3(n_chunks), dim3(64), 0, ST(stream), keys, T, n, frame_ids);
     SSR_LAUNCH_CHECK();
     return SSR_OK;
 }

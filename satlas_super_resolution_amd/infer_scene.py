@@ -17,7 +17,8 @@ straight from the plan's output into the mosaic, and the count of non-finite out
 `png_io` worker processes while the device runs another scene.
 
 Option keys: `data_dir`, `save_path`, `n_lr_images`, `network_g`, `path.*`, `compute_dtype` (default fp32h), `batch` (chunks per
-generator launch, default 64), `io_workers` as `infer_grid`; `scene_hw: [H, W]` for PNG scenes that are not square; `s2_bands`.
+generator launch, default 64), `io_workers` as `infer_grid`; `scene_hw: [H, W]` for PNG scenes that are not square; `overlap`;
+`s2_bands`; `frame_select`.
 
 `overlap: K` (0 .. 16; absent: the path above, unchanged) takes scenes of ANY height and width >= 32 instead: chunks overlap their
 neighbours by K pixels, the last chunk of a row or column ends at the scene's edge, and the super-resolved chunks are cross-faded
@@ -29,7 +30,16 @@ mosaic.  The blend is integer arithmetic on the device, so runs stay bit-identic
 grayscale `<band>.png` ([T*H, W]) per extra band - the dataset's `sentinel2/{tile}/{band}.png`, so a split's `sentinel2` folder is a
 `data_dir`.  `tci` goes first, the other bands follow in their order, a missing band file contributes zeros, as in
 `S2NAIPDataset`; the extra bands take no part in the choice of frames.  `super_resolve_scene(_blended)(..., bands=)` takes them as
-uint8 [K, T, H, W]."""
+uint8 [K, T, H, W].
+
+`frame_select: random | clearest` (absent: `random`, the paths above, unchanged) is the frame policy.  `random` is the reference's
+rule (`select_scene_frames`).  `clearest` is this project's own policy - the reference has no counterpart file - computed on the
+device (`ssr_scene_frame_keys`, `ssr_scene_rank_frames`): per chunk the `n_lr_images` frames with the fewest NODATA pixels (a zero
+sample), then the fewest saturated ones (255, 255, 255: clouds, snow, glint), then the lower index, best frame first
+(`rank_scene_frames`).  Every frame without a zero precedes every frame with one, so the chosen set is always one the reference's
+rule could have drawn.  It is deterministic, does not touch the `random` module and leaves no host round trip between the upload
+and the download of the mosaic.  It works with `overlap` and `s2_bands` (the keys are computed on the TCI alone); `stitched_s2.png`
+stays frame 0 under both policies."""
 from __future__ import annotations
 
 import argparse
@@ -61,6 +71,41 @@ def select_scene_frames(has_zero: np.ndarray, n: int) -> np.ndarray:
         else:
             out[k] = clean + random.sample(dirty, n - len(clean))
     return out
+
+
+FRAME_POLICIES = ("random", "clearest")
+MAX_SELECT_FRAMES = 1024      # frames per scene ssr_scene_rank_frames ranks (its LDS holds a chunk's keys)
+
+
+def rank_scene_frames(z: np.ndarray, s: np.ndarray, n: int) -> np.ndarray:
+    """The `clearest` policy restated in numpy (the inference path computes it on the device: `scene_frame_keys`,
+    `scene_rank_frames`).  z, s: integers [chunks, T], per frame t of a chunk's 32 x 32 TCI window the number of pixels with AT LEAST
+    ONE zero sample (ESA's NODATA) and the number whose three samples are ALL 255 (SATURATED: clouds, snow, glint) -> int32
+    [chunks, n]: the first n frames in the order (key, t) ascending, key = (z << 16) | s - fewest NODATA pixels first, then fewest
+    saturated ones, then the lower frame index - best frame first.  ValueError if n > T.
+    z > 0 is `select_scene_frames`' has_zero flag and z leads the key, so every frame without a zero precedes every frame with one:
+    the chosen set is all the clean frames topped up with dirty ones if there are fewer than n, otherwise n clean ones - always a
+    set the reference's rule could have drawn.  Nothing is drawn: the `random` module is not consumed."""
+    z, s = np.asarray(z), np.asarray(s)
+    assert z.ndim == 2 and z.shape == s.shape, (z.shape, s.shape)
+    n = int(n)
+    if not 1 <= n <= z.shape[1]:
+        raise ValueError(f"n_lr_images = {n} frames of a scene of {z.shape[1]}")
+    key = (z.astype(np.uint32) << np.uint32(16)) | s.astype(np.uint32)
+    return np.argsort(key, axis=1, kind="stable")[:, :n].astype(np.int32)      # stable: the lower index wins a tie
+
+
+def check_frame_select(frame_select, T: Optional[int] = None, n: Optional[int] = None) -> str:
+    """the refusals of a frame policy, all on the host: a value other than `random` / `clearest`; for `clearest`, given T and n,
+    more frames than the ranking kernel takes and fewer frames than are asked for (where `random.sample` raises under `random`)"""
+    if frame_select not in FRAME_POLICIES:
+        raise ValueError(f"frame_select = {frame_select!r}: one of {', '.join(FRAME_POLICIES)}")
+    if frame_select == "clearest" and T is not None:
+        if T > MAX_SELECT_FRAMES:
+            raise ValueError(f"frame_select: clearest ranks at most {MAX_SELECT_FRAMES} frames per scene, this one has {T}")
+        if n is not None and not 1 <= n <= T:
+            raise ValueError(f"n_lr_images = {n} frames of a scene of {T}")
+    return frame_select
 
 
 def check_scene_size(H: int, W: int, any_size: bool = False) -> None:
@@ -268,6 +313,39 @@ def scene_zero_scan_at(scene: torch.Tensor, origins: torch.Tensor) -> torch.Tens
     return out
 
 
+def scene_frame_keys(scene: torch.Tensor, origins: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [T, H, W, 3] (H, W >= 32, the TCI) and int32 [chunks, 2] origins (y0, x0), both on the device -> int32 storage [chunks, T]
+    on the device, read as uint32: (z << 16) | s of frame t of the 32 x 32 window at the origin, z its pixels with at least one zero
+    sample, s its pixels that are (255, 255, 255) (`rank_scene_frames`); rows of origins outside the scene are not written (they
+    keep what `out` held, zeros without one)"""
+    from . import hip
+    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
+    _check_origins(origins)
+    T, H, W = scene.shape[:3]
+    check_scene_size(H, W, True)
+    if out is None:
+        out = torch.zeros(origins.shape[0], T, dtype=torch.int32, device=scene.device)
+    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (origins.shape[0], T), (out.dtype, out.shape)
+    hip.check(hip.lib().ssr_scene_frame_keys(_ptr(scene), T, H, W, _ptr(origins), origins.shape[0], _ptr(out), hip.stream_ptr()),
+              "ssr_scene_frame_keys")
+    return out
+
+
+def scene_rank_frames(keys: torch.Tensor, n: int) -> torch.Tensor:
+    """keys (int32 storage [chunks, T] on the device, read as uint32: `scene_frame_keys`) -> int32 [chunks, n] on the device, the
+    frame_ids the gathers read: per chunk the first n frames in the order (key, frame index) ascending, exact and the same in every
+    run.  ValueError for more than 1024 frames and for n > T."""
+    from . import hip
+    assert keys.dtype == torch.int32 and keys.dim() == 2 and keys.shape[0] >= 1, (keys.dtype, keys.shape)
+    chunks, T = keys.shape
+    n = int(n)
+    check_frame_select("clearest", T, n)
+    assert keys.is_cuda and keys.is_contiguous()
+    out = torch.empty(chunks, n, dtype=torch.int32, device=keys.device)
+    hip.check(hip.lib().ssr_scene_rank_frames(_ptr(keys), chunks, T, n, _ptr(out), hip.stream_ptr()), "ssr_scene_rank_frames")
+    return out
+
+
 def scene_gather_at(scene: torch.Tensor, origins: torch.Tensor, frame_ids: torch.Tensor, dst: torch.Tensor, dtype: Optional[int] = None):
     """`scene_gather` for chunks at the origins (int32 [B, 2], device) of a scene of any size >= 32 x 32"""
     from . import hip
@@ -400,23 +478,39 @@ def _upload_scene(model, frames, n: int, any_size: bool = False, bands=None) -> 
     return scene, C_out, bands.to(dev, non_blocking=True).contiguous()
 
 
-def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[torch.Tensor] = None, bands=None) -> _Pending:
+def _frames_T(frames) -> Optional[int]:
+    """the frame count of a scene argument before it is parsed (None for what `_upload_scene` refuses anyway)"""
+    shape = getattr(frames, "shape", None)
+    if shape is None:
+        shape = np.asarray(frames).shape
+    return int(shape[0]) if len(shape) == 4 else None
+
+
+def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[torch.Tensor] = None, bands=None,
+                   frame_select: str = "random") -> _Pending:
     """upload, zero scan, frame choice (the one host round trip: chunks x T flags down, chunks x n ids up), then every batch of
     chunks through gather -> generator -> scatter and the download of mosaic + counter; returns without waiting for them.
-    With bands the gather is `scene_gather_bands` at the chunks' origins (32 i, 32 j); everything else is the same."""
+    With bands the gather is `scene_gather_bands` at the chunks' origins (32 i, 32 j); everything else is the same.
+    frame_select "clearest": the frame choice is keys -> rank on the current stream instead, and nothing comes back to the host
+    before the mosaic does."""
     if getattr(model, "scale", SCALE) != SCALE:
         raise NotImplementedError(f"scene inference runs scale {SCALE} generators only (scale = {model.scale})")
     n, batch = int(n_lr_images), int(batch)
     if batch < 1:
         raise ValueError(f"batch = {batch}")
+    check_frame_select(frame_select, _frames_T(frames), n)          # (before anything is uploaded)
     scene, C_out, bands = _upload_scene(model, frames, n, bands=bands)
     dev = scene.device
     T, H, W = scene.shape[:3]
     gw, n_chunks = W // CHUNK, (H // CHUNK) * (W // CHUNK)
-    has_zero = scene_zero_scan(scene).cpu().numpy()
-    frame_ids = torch.from_numpy(select_scene_frames(has_zero, n)).to(dev, non_blocking=True)
+    if frame_select == "clearest":
+        origins = torch.from_numpy(scene_chunk_grid(H, W, 0)).to(dev, non_blocking=True)    # (32 i, 32 j) in row-major order
+        frame_ids = scene_rank_frames(scene_frame_keys(scene, origins), n)
+    else:
+        has_zero = scene_zero_scan(scene).cpu().numpy()
+        frame_ids = torch.from_numpy(select_scene_frames(has_zero, n)).to(dev, non_blocking=True)
     chunk_ids = torch.arange(n_chunks, dtype=torch.int32, device=dev)
-    if bands is not None:
+    if bands is not None and frame_select != "clearest":
         origins = torch.from_numpy(scene_chunk_grid(H, W, 0)).to(dev, non_blocking=True)    # (32 i, 32 j) in row-major order
     Ho, Wo = SCALE * H, SCALE * W
     nb = Ho * Wo * C_out
@@ -444,16 +538,18 @@ def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[t
 
 
 def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch: int, host: Optional[torch.Tensor] = None,
-                           bands=None) -> _Pending:
+                           bands=None, frame_select: str = "random") -> _Pending:
     """`_enqueue_scene` for a scene of any size >= 32 x 32 cut into chunks that overlap: upload, zero scan at the origins, frame
-    choice (the one host round trip), a zeroed accumulator, every batch of chunks through gather -> generator -> blend-add, the
-    division by the weight sums and the download of mosaic + counter"""
+    choice (the one host round trip; with frame_select "clearest" keys -> rank on the device, no round trip), a zeroed accumulator,
+    every batch of chunks through gather -> generator -> blend-add, the division by the weight sums and the download of mosaic +
+    counter"""
     if getattr(model, "scale", SCALE) != SCALE:
         raise NotImplementedError(f"scene inference runs scale {SCALE} generators only (scale = {model.scale})")
     n, batch = int(n_lr_images), int(batch)
     if batch < 1:
         raise ValueError(f"batch = {batch}")
     window = blend_window(overlap)                  # (refuses a bad overlap before anything is uploaded)
+    check_frame_select(frame_select, _frames_T(frames), n)
     scene, C_out, bands = _upload_scene(model, frames, n, any_size=True, bands=bands)
     dev = scene.device
     T, H, W = scene.shape[:3]
@@ -463,8 +559,11 @@ def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch:
     window = torch.from_numpy(window).to(dev, non_blocking=True)
     Sy = torch.from_numpy(blend_weight_sums(H, overlap)).to(dev, non_blocking=True)
     Sx = torch.from_numpy(blend_weight_sums(W, overlap)).to(dev, non_blocking=True)
-    has_zero = scene_zero_scan_at(scene, origins).cpu().numpy()
-    frame_ids = torch.from_numpy(select_scene_frames(has_zero, n)).to(dev, non_blocking=True)
+    if frame_select == "clearest":
+        frame_ids = scene_rank_frames(scene_frame_keys(scene, origins), n)
+    else:
+        has_zero = scene_zero_scan_at(scene, origins).cpu().numpy()
+        frame_ids = torch.from_numpy(select_scene_frames(has_zero, n)).to(dev, non_blocking=True)
     Ho, Wo = SCALE * H, SCALE * W
     nb = Ho * Wo * C_out
     off = -(-nb // 16) * 16
@@ -493,7 +592,8 @@ def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch:
     return _Pending(host, ev, (Ho, Wo, C_out), getattr(model, "compute_dtype", None), n_chunks)
 
 
-def super_resolve_scene_blended(model, frames, n_lr_images: int, overlap: int = 8, batch: int = 64, bands=None) -> np.ndarray:
+def super_resolve_scene_blended(model, frames, n_lr_images: int, overlap: int = 8, batch: int = 64, bands=None,
+                                frame_select: str = "random") -> np.ndarray:
     """frames: uint8 [T, H, W, 3] (numpy array or CUDA tensor), H and W ANY values >= 32 -> uint8 [4H, 4W, 3].  The scene is cut into
     32 x 32 chunks that overlap their neighbours by `overlap` pixels (0 .. 16; `scene_chunk_origins`: the last chunk of an axis ends
     at the scene's edge), every chunk is super-resolved from `n_lr_images` of its frames (select_scene_frames over the chunks in
@@ -502,19 +602,26 @@ def super_resolve_scene_blended(model, frames, n_lr_images: int, overlap: int = 
     The accumulator holds 4 bytes per output sample (48 H W bytes: 50 MB for 512 x 512, 23 GB for a whole 10980 x 10980
     acquisition) and is allocated per scene, next to the scene itself and the 12 H W bytes of the mosaic.
     Refusals as `super_resolve_scene`: scale 4 generators only, n_lr_images against the generator's channels, FloatingPointError
-    (metrics.nonfinite_error) if any output sample is NaN / Inf.  `bands` as `super_resolve_scene`."""
-    return _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, bands=bands).result()
+    (metrics.nonfinite_error) if any output sample is NaN / Inf.  `bands` and `frame_select` as `super_resolve_scene`."""
+    return _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, bands=bands, frame_select=frame_select).result()
 
 
-def super_resolve_scene(model, frames, n_lr_images: int, batch: int = 64, bands=None) -> np.ndarray:
+def super_resolve_scene(model, frames, n_lr_images: int, batch: int = 64, bands=None, frame_select: str = "random") -> np.ndarray:
     """frames: uint8 [T, H, W, 3] (numpy array or CUDA tensor), H and W multiples of 32 (ValueError otherwise) -> uint8
     [4H, 4W, 3]: every 32 x 32 chunk super-resolved on its own from `n_lr_images` of its frames (select_scene_frames) and placed
     at rows 128 i, columns 128 j.  Raises FloatingPointError (metrics.nonfinite_error) if any output sample is NaN / Inf.
     bands: uint8 [K, T, H, W] (numpy array or CUDA tensor), the K extra Sentinel-2 bands of a multi-band generator, which then takes
     n_lr_images * (3 + K) channels - per chosen frame the TCI, then the bands in their order, what `S2NAIPDataset` with `s2_bands`
     feeds it in training; the frames are chosen on the TCI alone.  ValueError, before anything is uploaded, for bands of another
-    rank, dtype or T, H, W than the frames' and for a generator of another channel count."""
-    return _enqueue_scene(model, frames, n_lr_images, batch, bands=bands).result()
+    rank, dtype or T, H, W than the frames' and for a generator of another channel count.
+    frame_select: "random" (the default) is the reference's rule, `select_scene_frames`, which consumes the `random` module;
+    "clearest" is this project's own, deterministic policy, computed on the device (`rank_scene_frames` states it): per chunk the
+    n_lr_images frames with the fewest NODATA pixels, then the fewest saturated ones, then the lower index, best frame first.  Its
+    chosen set is always one the reference's rule could have drawn (all clean frames if there are fewer than n, else n clean ones),
+    nothing is copied to the host or waited for between the upload and the download of the mosaic, and `random` is not consumed.
+    ValueError, before anything is uploaded, for another value, and under "clearest" for fewer than n_lr_images frames or more than
+    1024."""
+    return _enqueue_scene(model, frames, n_lr_images, batch, bands=bands, frame_select=frame_select).result()
 
 
 # ------------------------------------------------------------------------------------------------ driver
@@ -527,6 +634,7 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
     blended = overlap is not None
     if blended:
         scene_chunk_origins(CHUNK, overlap)
+    frame_select = check_frame_select(opt.get("frame_select", "random"))      # absent: random, the reference's rule
     if device is None:
         device = torch.device("cuda")
     if model is None:
@@ -607,31 +715,38 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
         stack.callback(lambda: [f.exception() for f in saves])     # runs first, also on an error: earlier scenes' files are whole
         hosts = [None, None]
         reading = start_read(0) if mine else None
-        prev = None                                   # (name, first frame, pending) of the scene the device is running
+        prev = None                                   # (name, first frame, pending, block) of the scene the device is running
         for k in range(len(mine) + 1):
             cur = None
             if k < len(mine):
                 name, blk, frames, bands = finish_read(reading)
                 reading = start_read(k + 1) if k + 1 < len(mine) else None
                 if blended:
-                    pending = _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, hosts[k & 1], bands=bands)
+                    pending = _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, hosts[k & 1], bands=bands,
+                                                     frame_select=frame_select)
                 else:
-                    pending = _enqueue_scene(model, frames, n_lr_images, batch, hosts[k & 1], bands=bands)
+                    pending = _enqueue_scene(model, frames, n_lr_images, batch, hosts[k & 1], bands=bands, frame_select=frame_select)
                 hosts[k & 1] = pending.host
-                cur = (name, np.array(frames[0]), pending)          # (the upload has been waited for: the flags came back)
+                first = np.array(frames[0])
                 del frames, bands
-                if blk is not None:
-                    release(blk)
+                if frame_select == "random":
+                    if blk is not None:
+                        release(blk)                                # (the upload has been waited for: the flags came back)
+                    blk = None
+                cur = (name, first, pending, blk)                   # clearest: nothing came back yet, the block lives until the mosaic does
             if prev is not None:
-                pname, first, ppend = prev
+                pname, first, ppend, pblk = prev
                 sr = ppend.result(f" in scene {pname}")             # raises before any file of the scene is written
+                if pblk is not None:
+                    release(pblk)
                 saves.append(submit_save(sr, os.path.join(save_path, pname, "stitched_sr.png")))
                 saves.append(submit_save(first, os.path.join(save_path, pname, "stitched_s2.png")))
                 chunks += ppend.chunks
             prev = cur
         for f in saves:
             f.result()
-    return {"scenes": len(mine), "chunks": chunks, "seconds": round(time.perf_counter() - t_start, 3), "io_workers": workers}
+    return {"scenes": len(mine), "chunks": chunks, "seconds": round(time.perf_counter() - t_start, 3), "io_workers": workers,
+            "frame_select": frame_select}
 
 
 def main():

@@ -24,6 +24,14 @@ one blended run of the 512 x 512 scene, for a kernel trace.
 warm-up and three timed calls; for the gather's share of device time, trace one run at K = 9 and one at K = 0:
 
     rocprofv3 --kernel-trace --stats ... -- python tools/scene_infer_bench.py fp32h --bands 9
+
+`--frame-select POLICY[,POLICY]` runs another leg INSTEAD: the same 512 x 512 scene of 8 frames, now with NODATA and saturated
+patches so the policies have something to tell apart, through `super_resolve_scene(..., frame_select=POLICY)` for every policy named
+(`random`, `clearest`), alternating five times after a warm-up of each, upload to download, no files; with `--overlap K` through
+`super_resolve_scene_blended(overlap=K)` instead.  Both policies in one call is the only comparison that counts; one policy alone
+(`--frame-select clearest`) is the run to trace.
+
+    python tools/scene_infer_bench.py fp32h --frame-select random,clearest > profiles/scene_frame_select/bench.json
 """
 import json
 import os
@@ -109,7 +117,57 @@ def bands_leg(mode, K):
                       "warm_up_seconds": secs[0], "seconds": secs[1:], "median": statistics.median(secs[1:])}))
 
 
+def select_leg(mode, policies, overlap):
+    import random
+    from satlas_super_resolution_amd.archs.rrdbnet_arch import SSR_RRDBNet
+    from satlas_super_resolution_amd.infer_scene import scene_chunk_origins, super_resolve_scene, super_resolve_scene_blended
+    rng = np.random.RandomState(0)
+    scene = _scene(rng, 8, 512, 512)
+    scene[1, :, 100:180] = 255                      # a saturated band, a NODATA corner, a hazy frame
+    scene[2, 300:, 300:] = 0
+    scene[5][rng.rand(512, 512) < 0.3] = 255
+    net = SSR_RRDBNet(24, 3, 4, 64, 23, 32, compute_dtype=mode).cuda().eval().freeze_packed()
+
+    def run(policy):
+        random.seed(0)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if overlap is None:
+            super_resolve_scene(net, scene, 8, frame_select=policy)
+        else:
+            super_resolve_scene_blended(net, scene, 8, overlap=overlap, frame_select=policy)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    warm = {p: run(p) for p in policies}            # plans, graph capture, first touch
+    secs = {p: [] for p in policies}
+    for _ in range(5):
+        for p in policies:
+            secs[p].append(run(p))
+    med = statistics.median
+    rec = {"workload": "one 512 x 512 Sentinel-2 scene of 8 frames, SSR_RRDBNet(nf=64, nb=23, gc=32), random weights, n_lr_images 8, "
+                       "batch 64, one GPU; wall time of one call, upload to download, no files; the policies alternate in one process",
+           "device": torch.cuda.get_device_name(0), "compute_dtype": mode, "overlap": overlap,
+           "chunks": 256 if overlap is None else len(scene_chunk_origins(512, overlap)) ** 2,
+           "frame_select": {p: {"warm_up_seconds": warm[p], "seconds": secs[p], "median": med(secs[p]), "min": min(secs[p]),
+                                "spread": max(secs[p]) - min(secs[p])} for p in policies}}
+    if "random" in secs and "clearest" in secs:
+        rec["clearest_over_random"] = med(secs["clearest"]) / med(secs["random"])
+    print(json.dumps(rec))
+
+
 def main():
+    if "--frame-select" in sys.argv:
+        k = sys.argv.index("--frame-select")
+        policies = sys.argv[k + 1].split(",")
+        argv = sys.argv[1:k] + sys.argv[k + 2:]
+        overlap = None
+        if "--overlap" in argv:
+            j = argv.index("--overlap")
+            overlap = int(argv[j + 1])
+            argv = argv[:j] + argv[j + 2:]
+        rest = [a for a in argv if not a.startswith("--")]
+        return select_leg(rest[0] if rest else "fp32h", policies, overlap)
     if "--bands" in sys.argv:
         k = sys.argv.index("--bands")
         rest = [a for a in sys.argv[1:k] + sys.argv[k + 2:] if not a.startswith("--")]
