@@ -292,9 +292,9 @@ int ssr_add_views(ssr_view dst, ssr_view src, int32_t dtype, int64_t npix, int32
  * (lr_resized, ssr_esrgan_model.py:133). */
 int ssr_nchw_to_nhwc(const float* src, int32_t N, int32_t C, int32_t H, int32_t W, ssr_view dst, int32_t dtype,
                      int32_t unshuffle, int32_t up, float scale, void* stream);
+/* the inverse (outputs and gradients): dst NCHW fp32 [n,c,h,w] = src NHWC [n,h,w,coff+c], converted to fp32; dst is OVERWRITTEN */
 int ssr_nhwc_to_nchw(ssr_view src, int32_t dtype, float* dst, int32_t N, int32_t C, int32_t H, int32_t W,
                      void* stream);
-/* inverse for gradients: dst NCHW fp32 [n,c,h,w] (+)= src NHWC slice */
 int ssr_fill(void* p, int64_t n_elems, int32_t dtype, float value, void* stream);
 
 /* ---- bilinear x2 (align_corners=False): discriminator_arch.py:50,55,60 ---- */

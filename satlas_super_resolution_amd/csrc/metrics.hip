@@ -160,14 +160,15 @@ extern "C" int ssr_metric_ssim_sums(const uint8_t* a, const uint8_t* b, int32_t 
                                     double* out, void* stream) {
     if (!a || !b || !out || C <= 0 || crop < 0) return SSR_EINVAL;
     if (H - 2 * crop - 10 <= 0 || W - 2 * crop - 10 <= 0) return SSR_EINVAL;
-    static bool init = false;
-    if (!init) {   // cv2.getGaussianKernel(11, 1.5): exp(-(i - 5)^2 / (2 sigma^2)), normalised to sum 1, in double
+    static bool init[SSR_MAX_DEVICES] = {};      // a __constant__ symbol has one copy per DEVICE
+    const int init_dev = ssr_device_ordinal();
+    if (!init[init_dev]) {   // cv2.getGaussianKernel(11, 1.5): exp(-(i - 5)^2 / (2 sigma^2)), normalised to sum 1, in double
         double g[11], s = 0;
         for (int i = 0; i < 11; ++i) { g[i] = exp(-((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); s += g[i]; }
         for (int i = 0; i < 11; ++i) g[i] /= s;
         hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(SSIM_G), g, sizeof(g));
         if (e != hipSuccess) return (int)e;
-        init = true;
+        init[init_dev] = true;
     }
     hipError_t e = hipMemsetAsync(out, 0, sizeof(double) * C, ST(stream));
     if (e != hipSuccess) return (int)e;

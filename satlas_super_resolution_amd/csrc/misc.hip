@@ -839,6 +839,9 @@ static int up2x_bwd(ssr_view dy, ssr_view r, ssr_view y1, ssr_view y, ssr_view m
     dtype &= ~SSR_BILINEAR_FLAT;
     if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
     if (!dy.p || (!y.p && !y1.p) || (C % 8) != 0 || (dy.cs % 8) || (dy.coff % 8)) return SSR_EINVAL;
+    // every optional view goes through the same 16-byte vector loads / stores as dy: the forward's conditions on each of them
+    for (const ssr_view* v : {&r, &y1, &y, &m})
+        if (v->p && ((v->cs % 8) || (v->coff % 8))) return SSR_EINVAL;
     const long total = (long)N * H * W * C / 4;
     if (total >= (1L << 31)) return SSR_EINVAL;               // the kernel indexes in 32 bits
     const dim3 tgrid(N * ((H + BB_IH - 1) / BB_IH) * ((W + BB_IW - 1) / BB_IW), dtype == SSR_F32 ? C / 32 : C / 64);
