@@ -494,6 +494,26 @@ int ssr_scene_frame_keys(const uint8_t* scene, int32_t T, int32_t H, int32_t W, 
                          uint32_t* keys, void* stream);
 int ssr_scene_rank_frames(const uint32_t* keys, int32_t n_chunks, int32_t T, int32_t n, int32_t* frame_ids, void* stream);
 
+/* ---- scene inference, NODATA carried through to the mosaic (csrc/scene.hip; additive: the ABI version stays 3) ----
+ * The option `nodata: keep`.  The policy is this project's own: no counterpart in the reference, whose infer_grid.py writes
+ * whatever the generator makes of zero input.  ESA's TCI encodes 0 as NODATA: a low-resolution pixel of a frame HAS DATA if none of
+ * its three TCI samples is 0 (the complement of ssr_scene_frame_keys' z; extra bands take no part).
+ * ssr_scene_support_add: support is a DEVICE array int32 [H][W], 4-byte aligned, which the caller zeroes once per scene.  For each
+ *   of the B chunks at origins[2b], origins[2b + 1] = (y0, x0) and each pixel (y, x) of its 32 x 32 window,
+ *     support[y0 + y][x0 + x] += the number of slots k < n whose frame frame_ids[b*n + k] has data at (y0 + y, x0 + x)
+ *   by integer atomics: any arrival order of overlapping chunks gives the same words.  It counts what the gather entries fed to
+ *   the generator: a chunk whose origin lies outside [0, H - 32] x [0, W - 32] or one of whose frame ids lies outside [0, T) adds
+ *   nothing, as the gathers skip it.  The scene is uint8 [T][H][W][3] (H, W >= 32, SSR_EUNSUP below that, as n > T or n > 512); no
+ *   alignment needed, nothing outside the rows of a window is read.  A null pointer, a size <= 0 or B > 2^20: SSR_EINVAL.
+ * ssr_scene_apply_nodata: rewrites the mosaic uint8 [Ho][Wo][C] (Ho = 4 H, Wo = 4 W, 1 <= C <= 8, 4-byte aligned) in place: with
+ *   s = support[y / 4][x / 4], sample (y, x, c) becomes 0 if s < min_support, else max(1, sample) - 0 stays reserved for NODATA in
+ *   the output as it is in ESA's input.  support_u8, if not null, receives min(support, 255) as uint8 [H][W].  min_support < 1, a
+ *   null mosaic or support, C outside 1 .. 8: SSR_EINVAL; Ho or Wo no multiple of 4: SSR_EUNSUP. */
+int ssr_scene_support_add(const uint8_t* scene, int32_t T, int32_t H, int32_t W, const int32_t* origins, const int32_t* frame_ids,
+                          int32_t B, int32_t n, int32_t* support, void* stream);
+int ssr_scene_apply_nodata(uint8_t* mosaic, int32_t Ho, int32_t Wo, int32_t C, const int32_t* support, int32_t min_support,
+                           uint8_t* support_u8, void* stream);
+
 /* ---- VGG19 perceptual loss glue (csrc/vgg.hip; the convolutions run through ssr_conv2d with SSR_ACT_RELU / m_relu) ----
  * ssr_channel_affine: y[p, c] (+)= x[p, c] * scale[c] + shift[c] for c < C <= 8 (host float arrays, copied into the launch):
  *   the input normalisation (x - mean) / std of the feature extractor and, with accumulate = 1, its adjoint.

@@ -32,6 +32,15 @@
 //   ssr_scene_frame_keys     per (chunk at an origin, frame): (pixels with a zero sample << 16) | pixels that are (255, 255, 255)
 //   ssr_scene_rank_frames    per chunk: its T keys ranked by (key, frame index), the first n frame indices -> frame_ids
 //
+// NODATA in, NODATA out (`nodata: keep`, this project's own policy: the reference has no counterpart file): a low-resolution pixel of
+// a frame HAS DATA if none of its three TCI samples is 0 (the complement of ssr_scene_frame_keys' z); support[y][x] counts the
+// (covering chunk, chosen frame slot) pairs whose pixel has data - exactly what went into the generator.
+//
+//   ssr_scene_support_add    per chunk at an origin: the slots whose frame has data, per pixel of the window, added (integer
+//                            atomics) to an int32 [H][W] support map
+//   ssr_scene_apply_nodata   the uint8 mosaic in place: the 4 x 4 block of a pixel with support < min_support becomes 0, every other
+//                            sample max(1, sample) (0 stays reserved for NODATA); min(support, 255) as a uint8 [H][W] map
+//
 // Here a chunk row of the scene starts at any byte (W * 3 may be odd) and a mosaic row is only 4-byte aligned: rows are read as the
 // aligned words that lie inside them plus single bytes at the two ends, the mosaic is stored in aligned 4-byte units.
 #include "common.h"
@@ -427,6 +436,70 @@ __global__ __launch_bounds__(256) void scene_blend_finish_kernel(const uint32_t*
     mosaic[q] = out;
 }
 
+// one block per (chunk, row of its window): the n chosen frames' rows go through LDS as their covering aligned words, exactly as
+// scene_gather_at_kernel stages them (the same no-op tests, so support counts what the gather fed to the generator), then one
+// thread per pixel of the row counts the slots whose three samples are all non-zero and adds the count to the pixel's word of
+// support.  Integer atomics: overlapping chunks may arrive in any order.
+__global__ __launch_bounds__(256) void scene_support_add_kernel(const uint8_t* __restrict__ scene, int T_, int H, int W,
+                                                                const int32_t* __restrict__ origins,
+                                                                const int32_t* __restrict__ frame_ids, int n,
+                                                                int32_t* __restrict__ support) {
+    extern __shared__ uint32_t roww[];                            // [n][ROWW] words, then [n] byte offsets
+    uint32_t* shift = roww + n * ROWW;
+    const int b = blockIdx.x / CH, y = blockIdx.x - b * CH;
+    const int y0 = origins[2 * b], x0 = origins[2 * b + 1];
+    if (!origin_ok(y0, x0, H, W)) return;                         // block-uniform
+    for (int k = 0; k < n; ++k) {                                 // block-uniform: before any barrier
+        const int f = frame_ids[b * n + k];
+        if (f < 0 || f >= T_) return;
+    }
+    for (int e = threadIdx.x; e < n * ROWW; e += 256) {
+        const int k = e / ROWW, i = e - k * ROWW;
+        const long t = frame_ids[b * n + k];
+        const uint8_t* a = scene + ((t * H + y0 + y) * W + x0) * 3;
+        roww[e] = row_word<ROWB>(a, i);
+        if (i == 0) shift[k] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
+    }
+    __syncthreads();
+    if (threadIdx.x >= CH) return;                                // (after the only barrier)
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(roww);
+    const int x = threadIdx.x;
+    int count = 0;
+    for (int k = 0; k < n; ++k) {
+        const uint8_t* px = bytes + k * (4 * ROWW) + shift[k] + 3 * x;
+        count += (px[0] != 0) & (px[1] != 0) & (px[2] != 0);
+    }
+    if (count) atomicAdd(support + (long)(y0 + y) * W + x0 + x, count);
+}
+
+// one thread per aligned 4-byte unit of the mosaic (a row is Wo C bytes, Wo a multiple of 4), as scene_blend_finish_kernel stores:
+// for C = 3 a unit spans two output pixels, which can belong to two low-resolution pixels, so the rule is decided per byte.  The
+// thread that holds the first byte of a low-resolution pixel's 4 x 4 block also writes the pixel's saturated support.
+__global__ __launch_bounds__(256) void scene_apply_nodata_kernel(uint32_t* __restrict__ mosaic, int Ho, int Wo, int C,
+                                                                 const int32_t* __restrict__ support, int min_support,
+                                                                 uint8_t* __restrict__ support_u8) {
+    const long roww_ = (long)Wo * C / 4;
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= roww_ * Ho) return;
+    const int y = (int)(q / roww_);
+    const int j0 = (int)(q - (long)y * roww_) * 4;                // first byte of the unit inside its row
+    const int W = Wo / 4;
+    const int32_t* __restrict__ srow = support + (long)(y >> 2) * W;
+    int x = j0 / C, c = j0 - x * C;                               // output pixel and channel of the unit's first byte
+    const uint32_t in = mosaic[q];
+    uint32_t out = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int s = srow[x >> 2];
+        const uint32_t v = (in >> (8 * u)) & 0xffu;
+        out |= (s < min_support ? 0u : (v ? v : 1u)) << (8 * u);
+        if (support_u8 && c == 0 && (x & 3) == 0 && (y & 3) == 0)
+            support_u8[(long)(y >> 2) * W + (x >> 2)] = (uint8_t)(s > 255 ? 255 : s);
+        if (++c == C) { c = 0; ++x; }
+    }
+    mosaic[q] = out;
+}
+
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 }  // namespace
@@ -593,6 +666,31 @@ extern "C" int ssr_scene_blend_finish(const uint32_t* acc, const int32_t* Sy, co
     if (blocks > 0x7fffffffl) return SSR_EUNSUP;
     hipLaunchKernelGGL(scene_blend_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), acc, Sy, Sx, C,
                        reinterpret_cast<uint32_t*>(mosaic), Ho, Wo);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_support_add(const uint8_t* scene, int32_t T, int32_t H, int32_t W, const int32_t* origins,
+                                     const int32_t* frame_ids, int32_t B, int32_t n, int32_t* support, void* stream) {
+    if (!scene || !origins || !frame_ids || !support || T <= 0 || H <= 0 || W <= 0 || B <= 0 || n <= 0) return SSR_EINVAL;
+    if (!aligned4(support) || B > (1 << 20)) return SSR_EINVAL;
+    if (H < CH || W < CH || n > T || n > 512) return SSR_EUNSUP;
+    const size_t lds = (size_t)n * (ROWW + 1) * 4;
+    hipLaunchKernelGGL(scene_support_add_kernel, dim3(B * CH), dim3(256), lds, ST(stream), scene, T, H, W, origins, frame_ids, n,
+                       support);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_apply_nodata(uint8_t* mosaic, int32_t Ho, int32_t Wo, int32_t C, const int32_t* support,
+                                      int32_t min_support, uint8_t* support_u8, void* stream) {
+    if (!mosaic || !support || C <= 0 || Ho <= 0 || Wo <= 0 || min_support < 1) return SSR_EINVAL;
+    if (!aligned4(mosaic) || !aligned4(support) || C > MAX_C) return SSR_EINVAL;
+    if (Ho % 4 || Wo % 4) return SSR_EUNSUP;
+    const long units = (long)Ho * Wo * C / 4, blocks = (units + 255) / 256;
+    if (blocks > 0x7fffffffl) return SSR_EUNSUP;
+    hipLaunchKernelGGL(scene_apply_nodata_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream),
+                       reinterpret_cast<uint32_t*>(mosaic), Ho, Wo, C, support, min_support, support_u8);
     SSR_LAUNCH_CHECK();
     return SSR_OK;
 }

@@ -18,7 +18,7 @@ straight from the plan's output into the mosaic, and the count of non-finite out
 
 Option keys: `data_dir`, `save_path`, `n_lr_images`, `network_g`, `path.*`, `compute_dtype` (default fp32h), `batch` (chunks per
 generator launch, default 64), `io_workers` as `infer_grid`; `scene_hw: [H, W]` for PNG scenes that are not square; `overlap`;
-`s2_bands`; `frame_select`.
+`s2_bands`; `frame_select`; `nodata`, `nodata_min_support`.
 
 `overlap: K` (0 .. 16; absent: the path above, unchanged) takes scenes of ANY height and width >= 32 instead: chunks overlap their
 neighbours by K pixels, the last chunk of a row or column ends at the scene's edge, and the super-resolved chunks are cross-faded
@@ -39,7 +39,19 @@ sample), then the fewest saturated ones (255, 255, 255: clouds, snow, glint), th
 (`rank_scene_frames`).  Every frame without a zero precedes every frame with one, so the chosen set is always one the reference's
 rule could have drawn.  It is deterministic, does not touch the `random` module and leaves no host round trip between the upload
 and the download of the mosaic.  It works with `overlap` and `s2_bands` (the keys are computed on the TCI alone); `stitched_s2.png`
-stays frame 0 under both policies."""
+stays frame 0 under both policies.
+
+`nodata: fill | keep` (absent: `fill`, the paths above, unchanged byte for byte and launch for launch) is what becomes of ESA's
+NODATA (the value 0 of the TCI).  Under `fill` the generator runs on the zeros and whatever it makes of them is written as imagery,
+as the reference does.  `keep` is this project's own policy - the reference has no counterpart file: NODATA in, NODATA out.  A
+low-resolution pixel of a frame HAS DATA if none of its three TCI samples is 0 (the complement of the `z` count of
+`ssr_scene_frame_keys`; the extra bands of `s2_bands` take no part).  `support[y, x]` is the number of pairs (chunk that covers
+(y, x), chosen frame slot of that chunk) whose TCI pixel at (y, x) has data - exactly what went into the generator
+(`scene_support`).  With `nodata_min_support: m` (an integer >= 1, default 1) every sample of the 4 x 4 output block of a pixel with
+support < m becomes 0, every other sample max(1, sample): 0 stays reserved for NODATA in the output (`apply_nodata`).  The driver
+then writes a third file, `{save_path}/NAME/stitched_support.png`: min(support, 255), 8-bit grayscale [H, W].  All of it is integer
+work on the device (`ssr_scene_support_add`, `ssr_scene_apply_nodata`) between the upload and the one download, which grows by
+H W bytes; it works with `overlap`, `s2_bands` and both frame policies."""
 from __future__ import annotations
 
 import argparse
@@ -106,6 +118,64 @@ def check_frame_select(frame_select, T: Optional[int] = None, n: Optional[int] =
         if n is not None and not 1 <= n <= T:
             raise ValueError(f"n_lr_images = {n} frames of a scene of {T}")
     return frame_select
+
+
+NODATA_POLICIES = ("fill", "keep")
+
+
+def scene_support(tci: np.ndarray, origins, frame_ids) -> np.ndarray:
+    """The support map of the `nodata: keep` policy restated in numpy - the statement of the policy (the inference path computes
+    it on the device: `scene_support_add`).  tci uint8 [T, H, W, 3], origins integers [B, 2] (y0, x0), frame_ids integers [B, n] ->
+    int32 [H, W]: support[y, x] = the number of pairs (chunk b whose 32 x 32 window covers (y, x), slot k < n) whose TCI pixel
+    tci[frame_ids[b, k], y, x] HAS DATA, that is none of its three samples is 0 (ESA's NODATA; the complement of the `z` count of
+    `rank_scene_frames`).  It counts exactly what went into the generator: a chunk whose origin lies outside the scene or one of
+    whose frame ids lies outside 0 .. T - 1 contributes nothing - the gather kernels make such a chunk a no-op too.  A frame that
+    fills two slots counts twice.  On the grid path support <= n, on the blended path up to 3 chunks per axis cover a pixel
+    (`scene_chunk_origins(52, 16)` = [0, 16, 20]): support <= 9 n."""
+    tci = np.asarray(tci)
+    assert tci.dtype == np.uint8 and tci.ndim == 4 and tci.shape[3] == 3, (tci.dtype, tci.shape)
+    origins, frame_ids = np.asarray(origins).reshape(-1, 2), np.asarray(frame_ids)
+    assert frame_ids.ndim == 2 and frame_ids.shape[0] == origins.shape[0], (origins.shape, frame_ids.shape)
+    T, H, W = tci.shape[:3]
+    data = (tci != 0).all(axis=-1)
+    support = np.zeros((H, W), np.int32)
+    for (y0, x0), ids in zip(origins.tolist(), frame_ids):
+        if not (0 <= y0 <= H - CHUNK and 0 <= x0 <= W - CHUNK) or (ids < 0).any() or (ids >= T).any():
+            continue
+        support[y0:y0 + CHUNK, x0:x0 + CHUNK] += data[ids, y0:y0 + CHUNK, x0:x0 + CHUNK].sum(axis=0, dtype=np.int32)
+    return support
+
+
+def apply_nodata(mosaic: np.ndarray, support: np.ndarray, min_support: int = 1) -> np.ndarray:
+    """The output rule of the `nodata: keep` policy restated in numpy - the statement of the policy (on the device:
+    `scene_apply_nodata`).  mosaic uint8 [4H, 4W, C], support integers [H, W] (`scene_support`) -> uint8 [4H, 4W, C]: every sample of
+    the 4 x 4 output block of a low-resolution pixel becomes 0 where support < min_support and max(1, sample) where support >=
+    min_support: 0 stays reserved for NODATA in the output, as it is in ESA's input."""
+    mosaic, support = np.asarray(mosaic), np.asarray(support)
+    assert mosaic.dtype == np.uint8 and mosaic.ndim == 3 and support.ndim == 2, (mosaic.dtype, mosaic.shape, support.shape)
+    assert mosaic.shape[:2] == (SCALE * support.shape[0], SCALE * support.shape[1]), (mosaic.shape, support.shape)
+    _, m = check_nodata("keep", min_support)
+    up = np.repeat(np.repeat(support, SCALE, axis=0), SCALE, axis=1)[:, :, None]
+    return np.where(up < m, 0, np.maximum(mosaic, 1)).astype(np.uint8)
+
+
+def support_to_u8(support: np.ndarray) -> np.ndarray:
+    """the support map as it comes back with the mosaic: uint8 [H, W], min(support, 255)"""
+    return np.minimum(np.asarray(support), 255).astype(np.uint8)
+
+
+def check_nodata(nodata, min_support=1) -> Tuple[str, int]:
+    """the refusals of the NODATA option, all on the host: a value other than `fill` / `keep`; a min_support that is not an
+    integer >= 1; a min_support other than 1 together with `fill`, which has no support map to compare it with"""
+    if not isinstance(nodata, str) or nodata not in NODATA_POLICIES:
+        raise ValueError(f"nodata = {nodata!r}: one of {', '.join(NODATA_POLICIES)}")
+    if isinstance(min_support, bool) or not isinstance(min_support, (int, np.integer)) or min_support < 1:
+        raise ValueError(f"min_support = {min_support!r}: an integer >= 1")
+    if min_support >= 1 << 31:
+        raise ValueError(f"min_support = {min_support!r}: an integer below 2^31")
+    if nodata == "fill" and min_support != 1:
+        raise ValueError(f"min_support = {min_support} has a meaning under nodata: keep only (nodata = 'fill')")
+    return nodata, int(min_support)
 
 
 def check_scene_size(H: int, W: int, any_size: bool = False) -> None:
@@ -383,6 +453,45 @@ def scene_gather_bands(scene: torch.Tensor, bands: torch.Tensor, origins: torch.
                                                hip.view(dst), dtype, hip.stream_ptr()), "ssr_scene_gather_bands")
 
 
+def scene_support_add(scene: torch.Tensor, origins: torch.Tensor, frame_ids: torch.Tensor, support: torch.Tensor):
+    """`scene_support` on the device, for the chunks at the origins (int32 [B, 2], device) with the chosen frames frame_ids (int32
+    [B, n], device) - the arguments of the gather beside it: per pixel of every chunk's window the number of slots whose TCI pixel
+    has data (no zero sample) is ADDED to support (int32 [H, W], device; the caller zeroes it once per scene).  Chunks the gathers
+    skip (origin outside the scene, a frame id outside 0 .. T - 1) add nothing."""
+    from . import hip
+    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
+    _check_origins(origins)
+    assert frame_ids.dtype == torch.int32 and frame_ids.is_cuda and frame_ids.is_contiguous() and frame_ids.dim() == 2
+    T, H, W = scene.shape[:3]
+    check_scene_size(H, W, True)
+    B, n = frame_ids.shape
+    assert origins.shape[0] == B, (origins.shape, frame_ids.shape)
+    assert support.is_cuda and support.dtype == torch.int32 and support.is_contiguous() and tuple(support.shape) == (H, W), \
+        (support.dtype, support.shape)
+    hip.check(hip.lib().ssr_scene_support_add(_ptr(scene), T, H, W, _ptr(origins), _ptr(frame_ids), B, n, _ptr(support),
+                                              hip.stream_ptr()), "ssr_scene_support_add")
+
+
+def scene_apply_nodata(mosaic: torch.Tensor, support: torch.Tensor, min_support: int = 1, support_u8: Optional[torch.Tensor] = None):
+    """`apply_nodata` on the device, in place: mosaic uint8 [4H, 4W, C] and support int32 [H, W], both on the device - samples of
+    pixels with support < min_support become 0, all others max(1, sample); support_u8 (uint8 [H, W], device), if given, receives
+    min(support, 255)"""
+    from . import hip
+    assert mosaic.is_cuda and mosaic.dtype == torch.uint8 and mosaic.is_contiguous() and mosaic.dim() == 3, (mosaic.dtype, mosaic.shape)
+    Ho, Wo, C = mosaic.shape
+    assert Ho % SCALE == 0 and Wo % SCALE == 0, mosaic.shape
+    H, W = Ho // SCALE, Wo // SCALE
+    assert support.is_cuda and support.dtype == torch.int32 and support.is_contiguous() and tuple(support.shape) == (H, W), \
+        (support.dtype, support.shape)
+    _, m = check_nodata("keep", min_support)
+    if support_u8 is not None:
+        assert support_u8.is_cuda and support_u8.dtype == torch.uint8 and support_u8.is_contiguous() and \
+            tuple(support_u8.shape) == (H, W), (support_u8.dtype, support_u8.shape)
+    hip.check(hip.lib().ssr_scene_apply_nodata(_ptr(mosaic), Ho, Wo, C, _ptr(support), m,
+                                               None if support_u8 is None else _ptr(support_u8), hip.stream_ptr()),
+              "ssr_scene_apply_nodata")
+
+
 def _check_acc(acc: torch.Tensor, C: int):
     assert acc.is_cuda and acc.dtype == torch.int32 and acc.is_contiguous() and acc.dim() == 3 and acc.shape[2] == C, (acc.dtype, acc.shape)
 
@@ -418,11 +527,12 @@ def scene_blend_finish(acc: torch.Tensor, Sy: torch.Tensor, Sx: torch.Tensor, mo
 
 
 class _Pending:
-    """a scene whose launches are queued: the pinned host buffer its mosaic and counter are being copied to, and the event behind
-    that copy"""
+    """a scene whose launches are queued: the pinned host buffer its mosaic and counter (under `nodata: keep` the support map
+    behind them) are being copied to, and the event behind that copy"""
 
-    def __init__(self, host, event, shape, compute_dtype, chunks):
+    def __init__(self, host, event, shape, compute_dtype, chunks, support_off: Optional[int] = None):
         self.host, self.event, self.shape, self.compute_dtype, self.chunks = host, event, shape, compute_dtype, chunks
+        self.support_off = support_off          # where the uint8 [H, W] support map starts in the buffer; None under `fill`
 
     def result(self, where: str = "") -> np.ndarray:
         """waits for the download; raises FloatingPointError if an output sample was NaN / Inf (before any pixel is handed out)"""
@@ -432,6 +542,13 @@ class _Pending:
         if bad:
             raise nonfinite_error(bad, self.compute_dtype, where)
         return img.numpy()
+
+    def support(self) -> np.ndarray:
+        """after `result()`, under `nodata: keep`: uint8 [H, W], min(support, 255)"""
+        assert self.support_off is not None, "a support map comes back under nodata = 'keep' only"
+        self.event.synchronize()
+        H, W = self.shape[0] // SCALE, self.shape[1] // SCALE
+        return self.host[self.support_off:self.support_off + H * W].view(H, W).numpy()
 
 
 def _check_bands(model, frames, bands, n: int):
@@ -478,6 +595,21 @@ def _upload_scene(model, frames, n: int, any_size: bool = False, bands=None) -> 
     return scene, C_out, bands.to(dev, non_blocking=True).contiguous()
 
 
+def _download_buffer(dev, Ho: int, Wo: int, C_out: int, keep: bool):
+    """the one buffer a scene downloads: the mosaic and, behind it, the counter (zeroed here); under `nodata: keep` the counter's 16
+    bytes are followed by the uint8 [H, W] support map.  -> (buffer, mosaic view, counter view, support view or None, its offset or None)"""
+    nb = Ho * Wo * C_out
+    off = -(-nb // 16) * 16
+    n_sup = (Ho // SCALE) * (Wo // SCALE) if keep else 0
+    buf = torch.empty(off + (16 + n_sup if keep else 4), dtype=torch.uint8, device=dev)
+    counter = buf[off:off + 4].view(torch.int32)
+    counter.zero_()
+    mosaic = buf[:nb].view(Ho, Wo, C_out)
+    if not keep:
+        return buf, mosaic, counter, None, None
+    return buf, mosaic, counter, buf[off + 16:].view(Ho // SCALE, Wo // SCALE), off + 16
+
+
 def _frames_T(frames) -> Optional[int]:
     """the frame count of a scene argument before it is parsed (None for what `_upload_scene` refuses anyway)"""
     shape = getattr(frames, "shape", None)
@@ -487,18 +619,22 @@ def _frames_T(frames) -> Optional[int]:
 
 
 def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[torch.Tensor] = None, bands=None,
-                   frame_select: str = "random") -> _Pending:
+                   frame_select: str = "random", nodata: str = "fill", min_support: int = 1) -> _Pending:
     """upload, zero scan, frame choice (the one host round trip: chunks x T flags down, chunks x n ids up), then every batch of
     chunks through gather -> generator -> scatter and the download of mosaic + counter; returns without waiting for them.
     With bands the gather is `scene_gather_bands` at the chunks' origins (32 i, 32 j); everything else is the same.
     frame_select "clearest": the frame choice is keys -> rank on the current stream instead, and nothing comes back to the host
-    before the mosaic does."""
+    before the mosaic does.
+    nodata "keep": a zeroed support map, `scene_support_add` beside every gather (at the origins (32 i, 32 j)), `scene_apply_nodata`
+    behind the last scatter, and the support map behind the counter in the same download; nothing comes back earlier than before."""
     if getattr(model, "scale", SCALE) != SCALE:
         raise NotImplementedError(f"scene inference runs scale {SCALE} generators only (scale = {model.scale})")
     n, batch = int(n_lr_images), int(batch)
     if batch < 1:
         raise ValueError(f"batch = {batch}")
     check_frame_select(frame_select, _frames_T(frames), n)          # (before anything is uploaded)
+    nodata, min_support = check_nodata(nodata, min_support)
+    keep = nodata == "keep"
     scene, C_out, bands = _upload_scene(model, frames, n, bands=bands)
     dev = scene.device
     T, H, W = scene.shape[:3]
@@ -510,15 +646,11 @@ def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[t
         has_zero = scene_zero_scan(scene).cpu().numpy()
         frame_ids = torch.from_numpy(select_scene_frames(has_zero, n)).to(dev, non_blocking=True)
     chunk_ids = torch.arange(n_chunks, dtype=torch.int32, device=dev)
-    if bands is not None and frame_select != "clearest":
+    if (bands is not None or keep) and frame_select != "clearest":
         origins = torch.from_numpy(scene_chunk_grid(H, W, 0)).to(dev, non_blocking=True)    # (32 i, 32 j) in row-major order
     Ho, Wo = SCALE * H, SCALE * W
-    nb = Ho * Wo * C_out
-    off = -(-nb // 16) * 16
-    buf = torch.empty(off + 4, dtype=torch.uint8, device=dev)       # the mosaic and, behind it, the counter: one download
-    counter = buf[off:].view(torch.int32)
-    counter.zero_()
-    mosaic = buf[:nb].view(Ho, Wo, C_out)
+    buf, mosaic, counter, support_u8, support_off = _download_buffer(dev, Ho, Wo, C_out, keep)      # one download
+    support = torch.zeros(H, W, dtype=torch.int32, device=dev) if keep else None
     with torch.no_grad():
         for c0 in range(0, n_chunks, batch):
             ids = chunk_ids[c0:c0 + batch]
@@ -527,22 +659,26 @@ def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[t
                 scene_gather(scene, ids, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
             else:
                 scene_gather_bands(scene, bands, origins[c0:c0 + batch], frame_ids[c0:c0 + batch], plan.xin, plan.dt)
+            if keep:
+                scene_support_add(scene, origins[c0:c0 + batch], frame_ids[c0:c0 + batch], support)
             model.run_forward(plan)
             scene_scatter_u8(plan.out, ids, C_out, mosaic, counter, plan.dt)
+        if keep:
+            scene_apply_nodata(mosaic, support, min_support, support_u8)
     if host is None or host.numel() != buf.numel():
         host = torch.empty(buf.shape, dtype=torch.uint8, pin_memory=True)
     host.copy_(buf, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record()
-    return _Pending(host, ev, (Ho, Wo, C_out), getattr(model, "compute_dtype", None), n_chunks)
+    return _Pending(host, ev, (Ho, Wo, C_out), getattr(model, "compute_dtype", None), n_chunks, support_off)
 
 
 def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch: int, host: Optional[torch.Tensor] = None,
-                           bands=None, frame_select: str = "random") -> _Pending:
+                           bands=None, frame_select: str = "random", nodata: str = "fill", min_support: int = 1) -> _Pending:
     """`_enqueue_scene` for a scene of any size >= 32 x 32 cut into chunks that overlap: upload, zero scan at the origins, frame
     choice (the one host round trip; with frame_select "clearest" keys -> rank on the device, no round trip), a zeroed accumulator,
     every batch of chunks through gather -> generator -> blend-add, the division by the weight sums and the download of mosaic +
-    counter"""
+    counter; nodata "keep" as in `_enqueue_scene`, with `scene_apply_nodata` behind `scene_blend_finish`"""
     if getattr(model, "scale", SCALE) != SCALE:
         raise NotImplementedError(f"scene inference runs scale {SCALE} generators only (scale = {model.scale})")
     n, batch = int(n_lr_images), int(batch)
@@ -550,6 +686,8 @@ def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch:
         raise ValueError(f"batch = {batch}")
     window = blend_window(overlap)                  # (refuses a bad overlap before anything is uploaded)
     check_frame_select(frame_select, _frames_T(frames), n)
+    nodata, min_support = check_nodata(nodata, min_support)
+    keep = nodata == "keep"
     scene, C_out, bands = _upload_scene(model, frames, n, any_size=True, bands=bands)
     dev = scene.device
     T, H, W = scene.shape[:3]
@@ -565,12 +703,8 @@ def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch:
         has_zero = scene_zero_scan_at(scene, origins).cpu().numpy()
         frame_ids = torch.from_numpy(select_scene_frames(has_zero, n)).to(dev, non_blocking=True)
     Ho, Wo = SCALE * H, SCALE * W
-    nb = Ho * Wo * C_out
-    off = -(-nb // 16) * 16
-    buf = torch.empty(off + 4, dtype=torch.uint8, device=dev)       # the mosaic and, behind it, the counter: one download
-    counter = buf[off:].view(torch.int32)
-    counter.zero_()
-    mosaic = buf[:nb].view(Ho, Wo, C_out)
+    buf, mosaic, counter, support_u8, support_off = _download_buffer(dev, Ho, Wo, C_out, keep)      # one download
+    support = torch.zeros(H, W, dtype=torch.int32, device=dev) if keep else None
     acc = torch.zeros(Ho, Wo, C_out, dtype=torch.int32, device=dev)  # 4 bytes per output sample, this scene's own
     with torch.no_grad():
         for c0 in range(0, n_chunks, batch):
@@ -580,20 +714,37 @@ def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch:
                 scene_gather_at(scene, org, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
             else:
                 scene_gather_bands(scene, bands, org, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
+            if keep:
+                scene_support_add(scene, org, frame_ids[c0:c0 + batch], support)
             model.run_forward(plan)
             scene_blend_add(plan.out, org, C_out, window, acc, counter, plan.dt)
         scene_blend_finish(acc, Sy, Sx, mosaic)
+        if keep:
+            scene_apply_nodata(mosaic, support, min_support, support_u8)
     del acc
     if host is None or host.numel() != buf.numel():
         host = torch.empty(buf.shape, dtype=torch.uint8, pin_memory=True)
     host.copy_(buf, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record()
-    return _Pending(host, ev, (Ho, Wo, C_out), getattr(model, "compute_dtype", None), n_chunks)
+    return _Pending(host, ev, (Ho, Wo, C_out), getattr(model, "compute_dtype", None), n_chunks, support_off)
+
+
+def _check_return_support(nodata, min_support, return_support) -> None:
+    """the refusals of the public entry points' NODATA arguments, before anything is uploaded"""
+    nodata, _ = check_nodata(nodata, min_support)
+    if return_support and nodata != "keep":
+        raise ValueError(f"return_support: a support map comes back under nodata = 'keep' only (nodata = {nodata!r})")
+
+
+def _finish(pending: _Pending, return_support: bool):
+    mosaic = pending.result()
+    return (mosaic, pending.support()) if return_support else mosaic
 
 
 def super_resolve_scene_blended(model, frames, n_lr_images: int, overlap: int = 8, batch: int = 64, bands=None,
-                                frame_select: str = "random") -> np.ndarray:
+                                frame_select: str = "random", nodata: str = "fill", min_support: int = 1,
+                                return_support: bool = False):
     """frames: uint8 [T, H, W, 3] (numpy array or CUDA tensor), H and W ANY values >= 32 -> uint8 [4H, 4W, 3].  The scene is cut into
     32 x 32 chunks that overlap their neighbours by `overlap` pixels (0 .. 16; `scene_chunk_origins`: the last chunk of an axis ends
     at the scene's edge), every chunk is super-resolved from `n_lr_images` of its frames (select_scene_frames over the chunks in
@@ -602,11 +753,15 @@ def super_resolve_scene_blended(model, frames, n_lr_images: int, overlap: int = 
     The accumulator holds 4 bytes per output sample (48 H W bytes: 50 MB for 512 x 512, 23 GB for a whole 10980 x 10980
     acquisition) and is allocated per scene, next to the scene itself and the 12 H W bytes of the mosaic.
     Refusals as `super_resolve_scene`: scale 4 generators only, n_lr_images against the generator's channels, FloatingPointError
-    (metrics.nonfinite_error) if any output sample is NaN / Inf.  `bands` and `frame_select` as `super_resolve_scene`."""
-    return _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, bands=bands, frame_select=frame_select).result()
+    (metrics.nonfinite_error) if any output sample is NaN / Inf.  `bands`, `frame_select`, `nodata`, `min_support` and
+    `return_support` as `super_resolve_scene`; here up to 3 chunks per axis cover a pixel, so support <= 9 n_lr_images."""
+    _check_return_support(nodata, min_support, return_support)
+    return _finish(_enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, bands=bands, frame_select=frame_select,
+                                          nodata=nodata, min_support=min_support), return_support)
 
 
-def super_resolve_scene(model, frames, n_lr_images: int, batch: int = 64, bands=None, frame_select: str = "random") -> np.ndarray:
+def super_resolve_scene(model, frames, n_lr_images: int, batch: int = 64, bands=None, frame_select: str = "random",
+                        nodata: str = "fill", min_support: int = 1, return_support: bool = False):
     """frames: uint8 [T, H, W, 3] (numpy array or CUDA tensor), H and W multiples of 32 (ValueError otherwise) -> uint8
     [4H, 4W, 3]: every 32 x 32 chunk super-resolved on its own from `n_lr_images` of its frames (select_scene_frames) and placed
     at rows 128 i, columns 128 j.  Raises FloatingPointError (metrics.nonfinite_error) if any output sample is NaN / Inf.
@@ -620,8 +775,20 @@ def super_resolve_scene(model, frames, n_lr_images: int, batch: int = 64, bands=
     chosen set is always one the reference's rule could have drawn (all clean frames if there are fewer than n, else n clean ones),
     nothing is copied to the host or waited for between the upload and the download of the mosaic, and `random` is not consumed.
     ValueError, before anything is uploaded, for another value, and under "clearest" for fewer than n_lr_images frames or more than
-    1024."""
-    return _enqueue_scene(model, frames, n_lr_images, batch, bands=bands, frame_select=frame_select).result()
+    1024.
+    nodata: "fill" (the default) runs the generator on ESA's NODATA (the value 0 of the TCI) and writes whatever it makes of it,
+    as the reference does.  "keep" is this project's own policy (the reference has no counterpart file): NODATA in, NODATA out.  A
+    low-resolution pixel of a frame HAS DATA if none of its three TCI samples is 0 (bands take no part); support[y, x] is the number
+    of pairs (chunk that covers (y, x), chosen frame slot of that chunk) whose TCI pixel at (y, x) has data - what went into the
+    generator, here at most n_lr_images (`scene_support` states it).  Every sample of the 4 x 4 output block of a pixel with
+    support < min_support (an integer >= 1) becomes 0, every other sample max(1, sample): 0 stays reserved for NODATA
+    (`apply_nodata`).  Computed on the device, without a further round trip; a NaN / Inf under a masked pixel still raises.
+    return_support=True returns (mosaic, support_u8) with support_u8 = min(support, 255), uint8 [H, W].  ValueError, before anything
+    is uploaded, for another value of nodata, a min_support that is not an integer >= 1 or differs from 1 under "fill", and
+    return_support without "keep"."""
+    _check_return_support(nodata, min_support, return_support)
+    return _finish(_enqueue_scene(model, frames, n_lr_images, batch, bands=bands, frame_select=frame_select, nodata=nodata,
+                                  min_support=min_support), return_support)
 
 
 # ------------------------------------------------------------------------------------------------ driver
@@ -635,6 +802,8 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
     if blended:
         scene_chunk_origins(CHUNK, overlap)
     frame_select = check_frame_select(opt.get("frame_select", "random"))      # absent: random, the reference's rule
+    nodata, min_support = check_nodata(opt.get("nodata", "fill"), opt.get("nodata_min_support", 1))      # absent: fill, as ever
+    keep = nodata == "keep"
     if device is None:
         device = torch.device("cuda")
     if model is None:
@@ -723,9 +892,10 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
                 reading = start_read(k + 1) if k + 1 < len(mine) else None
                 if blended:
                     pending = _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, hosts[k & 1], bands=bands,
-                                                     frame_select=frame_select)
+                                                     frame_select=frame_select, nodata=nodata, min_support=min_support)
                 else:
-                    pending = _enqueue_scene(model, frames, n_lr_images, batch, hosts[k & 1], bands=bands, frame_select=frame_select)
+                    pending = _enqueue_scene(model, frames, n_lr_images, batch, hosts[k & 1], bands=bands, frame_select=frame_select,
+                                             nodata=nodata, min_support=min_support)
                 hosts[k & 1] = pending.host
                 first = np.array(frames[0])
                 del frames, bands
@@ -741,12 +911,17 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
                     release(pblk)
                 saves.append(submit_save(sr, os.path.join(save_path, pname, "stitched_sr.png")))
                 saves.append(submit_save(first, os.path.join(save_path, pname, "stitched_s2.png")))
+                if keep:
+                    saves.append(submit_save(ppend.support(), os.path.join(save_path, pname, "stitched_support.png")))
                 chunks += ppend.chunks
             prev = cur
         for f in saves:
             f.result()
-    return {"scenes": len(mine), "chunks": chunks, "seconds": round(time.perf_counter() - t_start, 3), "io_workers": workers,
-            "frame_select": frame_select}
+    res = {"scenes": len(mine), "chunks": chunks, "seconds": round(time.perf_counter() - t_start, 3), "io_workers": workers,
+           "frame_select": frame_select}
+    if keep:
+        res.update(nodata=nodata, nodata_min_support=min_support)
+    return res
 
 
 def main():

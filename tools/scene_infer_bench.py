@@ -32,6 +32,14 @@ patches so the policies have something to tell apart, through `super_resolve_sce
 (`--frame-select clearest`) is the run to trace.
 
     python tools/scene_infer_bench.py fp32h --frame-select random,clearest > profiles/scene_frame_select/bench.json
+
+`--nodata keep` runs another leg INSTEAD: a 512 x 512 scene of 8 frames with a NODATA wedge along one edge in every frame and a
+NODATA patch in three frames, through `super_resolve_scene(..., frame_select="clearest")` as it is (`nodata="fill"`, the behaviour
+without the option) and with `nodata="keep"`, the two alternating five times after a warm-up of each, upload to download, no files;
+with `--overlap K` through `super_resolve_scene_blended(overlap=K)` instead.  Both in one call is the only comparison that counts.
+`--nodata-trace` (with `--nodata keep`): the warm-up and one `keep` run, for a kernel trace.
+
+    python tools/scene_infer_bench.py fp32h --nodata keep > profiles/scene_nodata/bench.json
 """
 import json
 import os
@@ -156,7 +164,65 @@ def select_leg(mode, policies, overlap):
     print(json.dumps(rec))
 
 
+def nodata_leg(mode, overlap, trace_only):
+    from satlas_super_resolution_amd.archs.rrdbnet_arch import SSR_RRDBNet
+    from satlas_super_resolution_amd.infer_scene import scene_chunk_origins, super_resolve_scene, super_resolve_scene_blended
+    rng = np.random.RandomState(0)
+    scene = _scene(rng, 8, 512, 512)
+    yy, xx = np.mgrid[0:512, 0:512]
+    scene[:, 3 * xx + yy < 300] = 0                 # the swath edge: NODATA in every frame
+    scene[1:4, 300:400, 200:420] = 0                # and a patch in three frames
+    net = SSR_RRDBNet(24, 3, 4, 64, 23, 32, compute_dtype=mode).cuda().eval().freeze_packed()
+
+    def run(nodata):
+        kw = dict(frame_select="clearest", nodata=nodata, return_support=nodata == "keep")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if overlap is None:
+            out = super_resolve_scene(net, scene, 8, **kw)
+        else:
+            out = super_resolve_scene_blended(net, scene, 8, overlap=overlap, **kw)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    if trace_only:
+        run("keep")
+        print(json.dumps({"keep_seconds": run("keep")[0]}))
+        return
+    policies = ("fill", "keep")
+    warm = {p: run(p)[0] for p in policies}         # plans, graph capture, first touch
+    secs = {p: [] for p in policies}
+    for _ in range(5):
+        for p in policies:
+            secs[p].append(run(p)[0])
+    mosaic, support = run("keep")[1]
+    med = statistics.median
+    rec = {"workload": "one 512 x 512 Sentinel-2 scene of 8 frames with a NODATA wedge, SSR_RRDBNet(nf=64, nb=23, gc=32), random weights, "
+                       "n_lr_images 8, batch 64, frame_select clearest, one GPU; wall time of one call, upload to download, no files; "
+                       "fill (the behaviour without the option) and keep alternate in one process",
+           "device": torch.cuda.get_device_name(0), "compute_dtype": mode, "overlap": overlap,
+           "chunks": 256 if overlap is None else len(scene_chunk_origins(512, overlap)) ** 2,
+           "masked_share_of_pixels": float((support == 0).mean()), "largest_support": int(support.max()),
+           "zero_samples_outside_masked_pixels": int((mosaic[np.repeat(np.repeat(support > 0, 4, 0), 4, 1)] == 0).sum()),
+           "nodata": {p: {"warm_up_seconds": warm[p], "seconds": secs[p], "median": med(secs[p]), "min": min(secs[p]),
+                          "spread": max(secs[p]) - min(secs[p])} for p in policies},
+           "keep_over_fill": med(secs["keep"]) / med(secs["fill"])}
+    print(json.dumps(rec))
+
+
 def main():
+    if "--nodata" in sys.argv:
+        k = sys.argv.index("--nodata")
+        if sys.argv[k + 1] != "keep":
+            raise SystemExit("--nodata keep (fill is the other half of the same run)")
+        argv = sys.argv[1:k] + sys.argv[k + 2:]
+        overlap = None
+        if "--overlap" in argv:
+            j = argv.index("--overlap")
+            overlap = int(argv[j + 1])
+            argv = argv[:j] + argv[j + 2:]
+        rest = [a for a in argv if not a.startswith("--")]
+        return nodata_leg(rest[0] if rest else "fp32h", overlap, "--nodata-trace" in argv)
     if "--frame-select" in sys.argv:
         k = sys.argv.index("--frame-select")
         policies = sys.argv[k + 1].split(",")
