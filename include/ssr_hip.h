@@ -514,6 +514,34 @@ int ssr_scene_support_add(const uint8_t* scene, int32_t T, int32_t H, int32_t W,
 int ssr_scene_apply_nodata(uint8_t* mosaic, int32_t Ho, int32_t Wo, int32_t C, const int32_t* support, int32_t min_support,
                            uint8_t* support_u8, void* stream);
 
+/* ---- scene inference, self-ensemble over the eight flips and transposes (csrc/scene.hip; additive: the ABI version stays 3) ----
+ * The option `self_ensemble: true`: BasicSR's `val.self_ensemble` transform set (SRModel.test_selfensemble: 'v', 'h', 't'), averaged
+ * by this project's integer blend instead of a float mean.  A transform id tf in 0 .. 7 has three bits, applied in this order to the
+ * two spatial axes of a chunk P: bit 0 flips the columns, bit 1 flips the rows, bit 2 transposes.  So pixel (y, x) of a 32 x 32
+ * chunk lands at (y', x') with x' = tf & 1 ? 31 - x : x, y' = tf & 2 ? 31 - y : y, swapped if tf & 4; the inverse undoes the bits in
+ * the opposite order, on 128 x 128 outputs.  The generator rows are (chunk, tf) pairs: origins, frame_ids and tf are per ROW.
+ * ssr_scene_gather_tf: row b of dst is the transform tf[b] of the chunk ssr_scene_gather_at (bands == null, K == 0) or
+ *   ssr_scene_gather_bands (bands uint8 [K][T][H][W], K >= 1) writes for origins[2b .. 2b + 1] and frame_ids[b*n ..]: the same
+ *   x * fp32(1/255) and storage rounding, the same channel order, so with tf[b] == 0 the same bytes.  tf is a DEVICE array int32 [B].
+ *   A row whose origin lies outside the scene, one of whose frame ids lies outside [0, T) or whose tf lies outside [0, 7] is skipped:
+ *   nothing is read or written for it.  Conditions and return codes as ssr_scene_gather_bands, with K == 0 allowed (bands is then
+ *   not read; bands == null with K >= 1: SSR_EINVAL).
+ * ssr_scene_blend_add_tf: ssr_scene_blend_add of the INVERSE transform tf[b] of item b's output, with 13 fractional bits:
+ *     f = (uint32) (fminf(fmaxf(v, 0), 1) * 8191.0f)          fp32 multiply, truncation; NaN -> 0
+ *     acc[4 y0 + r][4 x0 + col][c] += f * window[r] * window[col]        v = sample c of the pixel of src that the inverse puts at (r, col)
+ *   window is indexed by the place in the accumulator (it is symmetric).  8 * 125 * 125 * 8191 < 2^32: the eight rows of every chunk
+ *   of a scene fit the uint32 words where 16 fractional bits would not.  Rows skipped as above add nothing and count nothing;
+ *   non-finite samples are counted over every row that is not skipped.  Other conditions as ssr_scene_blend_add.
+ * ssr_scene_blend_finish_scaled: ssr_scene_blend_finish with the denominator's scale as an argument,
+ *     mosaic[y][x][c] = (uint8) ((uint64) acc[y][x][c] * 255 / ((uint64) Sy[y] * Sx[x] * scale)),
+ *   scale = 8 * 8191 for the self-ensemble (65535 gives ssr_scene_blend_finish).  scale < 1: SSR_EINVAL. */
+int ssr_scene_gather_tf(const uint8_t* tci, const uint8_t* bands, int32_t K, int32_t T, int32_t H, int32_t W, const int32_t* origins,
+                        const int32_t* frame_ids, const int32_t* tf, int32_t B, int32_t n, ssr_view dst, int32_t dtype, void* stream);
+int ssr_scene_blend_add_tf(ssr_view src, int32_t dtype, const int32_t* origins, const int32_t* tf, int32_t B, int32_t C,
+                           const int32_t* window, uint32_t* acc, int32_t Ho, int32_t Wo, int32_t* nonfinite, void* stream);
+int ssr_scene_blend_finish_scaled(const uint32_t* acc, const int32_t* Sy, const int32_t* Sx, int32_t C, int32_t scale, uint8_t* mosaic,
+                                  int32_t Ho, int32_t Wo, void* stream);
+
 /* ---- VGG19 perceptual loss glue (csrc/vgg.hip; the convolutions run through ssr_conv2d with SSR_ACT_RELU / m_relu) ----
  * ssr_channel_affine: y[p, c] (+)= x[p, c] * scale[c] + shift[c] for c < C <= 8 (host float arrays, copied into the launch):
  *   the input normalisation (x - mean) / std of the feature extractor and, with accumulate = 1, its adjoint.

@@ -41,6 +41,14 @@
 //   ssr_scene_apply_nodata   the uint8 mosaic in place: the 4 x 4 block of a pixel with support < min_support becomes 0, every other
 //                            sample max(1, sample) (0 stays reserved for NODATA); min(support, 255) as a uint8 [H][W] map
 //
+// Self-ensemble (`self_ensemble: true`: BasicSR's val.self_ensemble transform set, averaged by the integer blend): a generator row
+// is a (chunk, transform) pair, the transform id tf in 0 .. 7 with bit 0 = flip the columns, bit 1 = flip the rows, bit 2 =
+// transpose, applied in that order.
+//
+//   ssr_scene_gather_tf            ssr_scene_gather_at / ssr_scene_gather_bands, the chunk written under its row's transform
+//   ssr_scene_blend_add_tf         ssr_scene_blend_add of the output turned back, in 13-bit fixed point (eight rows per chunk fit)
+//   ssr_scene_blend_finish_scaled  ssr_scene_blend_finish with the denominator's scale (8 * 8191) as an argument
+//
 // Here a chunk row of the scene starts at any byte (W * 3 may be odd) and a mosaic row is only 4-byte aligned: rows are read as the
 // aligned words that lie inside them plus single bytes at the two ends, the mosaic is stored in aligned 4-byte units.
 #include "common.h"
@@ -384,6 +392,70 @@ __global__ __launch_bounds__(256) void scene_gather_bands_kernel(const uint8_t* 
     }
 }
 
+// scene_gather_bands_kernel (K >= 1) and scene_gather_at_kernel (K == 0, bands not read) under a transform of the square: the
+// block of SOURCE row y stages the rows exactly as they do - whole rows as aligned words - and converts with the same arithmetic;
+// only the place of a pixel in dst turns.  Source pixel (y, x) goes to (yd, xd) = (tf & 2 ? 31 - y : y, tf & 1 ? 31 - x : x), swapped
+// if tf & 4: without a transpose the block writes a row of dst (backwards under a column flip), under a transpose a column of it,
+// one pixel's channel vector (or V of its channels) per store.  tf outside 0 .. 7: a no-op, block-uniform like the other two.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void scene_gather_tf_kernel(const uint8_t* __restrict__ tci, const uint8_t* __restrict__ bands,
+                                                              int K, int T_, int H, int W, const int32_t* __restrict__ origins,
+                                                              const int32_t* __restrict__ frame_ids, const int32_t* __restrict__ tf,
+                                                              int n, ssr_view dst) {
+    extern __shared__ uint32_t roww[];                            // [n][ROWW], [n K][BANDW] words, then [n] and [n K] byte offsets
+    uint32_t* bandw = roww + n * ROWW;
+    uint32_t* shift = bandw + n * K * BANDW;
+    uint32_t* bshift = shift + n;
+    const int b = blockIdx.x / CH, y = blockIdx.x - b * CH;
+    const int y0 = origins[2 * b], x0 = origins[2 * b + 1];
+    if (!origin_ok(y0, x0, H, W)) return;                         // block-uniform
+    const int t8 = tf[b];
+    if (t8 < 0 || t8 > 7) return;                                 // block-uniform
+    for (int s = 0; s < n; ++s) {                                 // block-uniform: before any barrier
+        const int f = frame_ids[b * n + s];
+        if (f < 0 || f >= T_) return;
+    }
+    const int tci_words = n * ROWW;
+    for (int e = threadIdx.x; e < tci_words + n * K * BANDW; e += 256) {
+        if (e < tci_words) {
+            const int s = e / ROWW, i = e - s * ROWW;
+            const long t = frame_ids[b * n + s];
+            const uint8_t* a = tci + ((t * H + y0 + y) * W + x0) * 3;
+            roww[e] = row_word<ROWB>(a, i);
+            if (i == 0) shift[s] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
+        } else {                                                  // (K >= 1 here)
+            const int r = (e - tci_words) / BANDW, i = (e - tci_words) - r * BANDW;      // r = s K + band
+            const int s = r / K, kb = r - s * K;
+            const long t = frame_ids[b * n + s];
+            const uint8_t* a = bands + (((long)kb * T_ + t) * H + y0 + y) * W + x0;
+            bandw[r * BANDW + i] = row_word<CH>(a, i);
+            if (i == 0) bshift[r] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
+        }
+    }
+    __syncthreads();
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(roww);
+    const uint8_t* bbytes = reinterpret_cast<const uint8_t*>(bandw);
+    const int F = 3 + K, C = n * F, groups = C / V;
+    T* __restrict__ d = reinterpret_cast<T*>(dst.p);
+    const int yd = (t8 & 2) ? CH - 1 - y : y;
+    for (int e = threadIdx.x; e < CH * groups; e += 256) {
+        const int x = e / groups, c0 = (e - x * groups) * V;
+        const int xd = (t8 & 1) ? CH - 1 - x : x;
+        const int py = (t8 & 4) ? xd : yd, px = (t8 & 4) ? yd : xd;      // both in 0 .. 31
+        int s = c0 / F, c = c0 - s * F;                           // slot and channel inside the slot of the pack's first element
+        Pack<T, V> o;
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+            const int r = s * K + c - 3;
+            const uint8_t v = c < 3 ? bytes[s * (4 * ROWW) + shift[s] + x * 3 + c] : bbytes[r * (4 * BANDW) + bshift[r] + x];
+            // x * (1.0f / 255.0f), then the storage type's rounding: scene_gather_kernel's arithmetic
+            o.v[u] = from_f32<T>((float)v * INV255);
+            if (++c == F) { c = 0; ++s; }
+        }
+        *reinterpret_cast<Pack<T, V>*>(d + (((long)b * CH + py) * CH + px) * dst.cs + dst.coff + c0) = o;
+    }
+}
+
 // one wave per (batch item, row of its 128 x 128 output): the row's 128 C fixed-point samples, weighted, are added to 128 C
 // consecutive words of the accumulator - wave-instructions of 256 contiguous bytes.  Integer adds: the sums do not depend on the
 // order in which overlapping chunks arrive.
@@ -414,16 +486,57 @@ __global__ __launch_bounds__(256) void scene_blend_add_kernel(ssr_view src, cons
     if (lane == 0 && bad) atomicAdd(nonfinite, bad);
 }
 
-// one thread per aligned 4-byte unit of the mosaic (a row is Wo C bytes, Wo a multiple of 4)
-__global__ __launch_bounds__(256) void scene_blend_finish_kernel(const uint32_t* __restrict__ acc, const int32_t* __restrict__ Sy,
-                                                                 const int32_t* __restrict__ Sx, int C, uint32_t* __restrict__ mosaic,
-                                                                 int Ho, int Wo) {
+// scene_blend_add_kernel for a (chunk, transform) row of the self-ensemble: the wave that owns accumulator row r of item b adds the
+// INVERSE transform of the item's output, so it reads src at the preimage of (r, x) - row rs = tf & 2 ? 127 - r : r and column
+// xs = tf & 1 ? 127 - x : x, swapped if tf & 4 (then a column of src: a strided read) - and adds into the same 128 C consecutive
+// words: the reads turn, the atomics stay contiguous.  The window is indexed by the place in the accumulator.  13 fractional bits:
+// 8 rows per chunk x 125 x 125 (the largest weight sums) x 8191 < 2^32.  tf outside 0 .. 7: a no-op, wave-uniform.
+constexpr float ENS_ONE = 8191.0f;
+
+template <typename T>
+__global__ __launch_bounds__(256) void scene_blend_add_tf_kernel(ssr_view src, const int32_t* __restrict__ origins,
+                                                                 const int32_t* __restrict__ tf, int B, int C,
+                                                                 const int32_t* __restrict__ window, uint32_t* __restrict__ acc,
+                                                                 int Ho, int Wo, int32_t* __restrict__ nonfinite) {
+    const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (long)B * SR) return;                             // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const int b = (int)(item / SR), r = (int)(item - (long)b * SR);
+    const int y0 = origins[2 * b], x0 = origins[2 * b + 1];
+    if (!origin_ok(y0, x0, Ho / 4, Wo / 4)) return;               // wave-uniform
+    const int t8 = tf[b];
+    if (t8 < 0 || t8 > 7) return;                                 // wave-uniform
+    const T* __restrict__ s = reinterpret_cast<const T*>(src.p) + (long)b * SR * SR * src.cs + src.coff;
+    uint32_t* __restrict__ a = acc + (((long)4 * y0 + r) * Wo + (long)4 * x0) * C;
+    const uint32_t wr = (uint32_t)window[r];
+    const int rs = (t8 & 2) ? SR - 1 - r : r;
+    int bad = 0;
+    for (int e = lane; e < SR * C; e += 64) {
+        const int x = e / C, c = e - x * C;
+        const int xs = (t8 & 1) ? SR - 1 - x : x;
+        const int pix = (t8 & 4) ? xs * SR + rs : rs * SR + xs;  // below 128 * 128
+        const float v = to_f32(s[(long)pix * src.cs + c]);
+        bad += (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
+        // clamp(0, 1) (NaN -> 0 via fmaxf) * 8191 in fp32, truncated: 13 fractional bits of the sample
+        const uint32_t f = (uint32_t)(fminf(fmaxf(v, 0.f), 1.f) * ENS_ONE);
+        atomicAdd(a + e, f * wr * (uint32_t)window[x]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_down(bad, o, 64);
+    if (lane == 0 && bad) atomicAdd(nonfinite, bad);
+}
+
+// one thread per aligned 4-byte unit of the mosaic (a row is Wo C bytes, Wo a multiple of 4); `scale` is the fixed point's one
+// times the rows per chunk: the constant 65535 in scene_blend_finish_kernel, an argument in scene_blend_finish_scaled_kernel
+__device__ __forceinline__ void blend_finish_unit(const uint32_t* __restrict__ acc, const int32_t* __restrict__ Sy,
+                                                  const int32_t* __restrict__ Sx, int C, uint32_t* __restrict__ mosaic, int Ho, int Wo,
+                                                  uint32_t scale) {
     const long roww_ = (long)Wo * C / 4;
     const long q = (long)blockIdx.x * 256 + threadIdx.x;
     if (q >= roww_ * Ho) return;
     const int y = (int)(q / roww_);
     const int j0 = (int)(q - (long)y * roww_) * 4;                // first byte of the unit inside its row
-    const uint64_t sy = (uint64_t)Sy[y] * 65535u;
+    const uint64_t sy = (uint64_t)Sy[y] * scale;
     const u32x4 a4 = *reinterpret_cast<const u32x4*>(acc + 4 * q);   // the unit's 4 samples: 16 aligned bytes
     uint32_t out = 0;
 #pragma unroll
@@ -434,6 +547,18 @@ __global__ __launch_bounds__(256) void scene_blend_finish_kernel(const uint32_t*
         out |= (uint32_t)(den ? (num / den) & 0xff : 0) << (8 * u);
     }
     mosaic[q] = out;
+}
+
+__global__ __launch_bounds__(256) void scene_blend_finish_kernel(const uint32_t* __restrict__ acc, const int32_t* __restrict__ Sy,
+                                                                 const int32_t* __restrict__ Sx, int C, uint32_t* __restrict__ mosaic,
+                                                                 int Ho, int Wo) {
+    blend_finish_unit(acc, Sy, Sx, C, mosaic, Ho, Wo, 65535u);
+}
+
+__global__ __launch_bounds__(256) void scene_blend_finish_scaled_kernel(const uint32_t* __restrict__ acc, const int32_t* __restrict__ Sy,
+                                                                        const int32_t* __restrict__ Sx, int C, uint32_t scale,
+                                                                        uint32_t* __restrict__ mosaic, int Ho, int Wo) {
+    blend_finish_unit(acc, Sy, Sx, C, mosaic, Ho, Wo, scale);
 }
 
 // one block per (chunk, row of its window): the n chosen frames' rows go through LDS as their covering aligned words, exactly as
@@ -666,6 +791,60 @@ extern "C" int ssr_scene_blend_finish(const uint32_t* acc, const int32_t* Sy, co
     if (blocks > 0x7fffffffl) return SSR_EUNSUP;
     hipLaunchKernelGGL(scene_blend_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), acc, Sy, Sx, C,
                        reinterpret_cast<uint32_t*>(mosaic), Ho, Wo);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_gather_tf(const uint8_t* tci, const uint8_t* bands, int32_t K, int32_t T, int32_t H, int32_t W,
+                                   const int32_t* origins, const int32_t* frame_ids, const int32_t* tf, int32_t B, int32_t n,
+                                   ssr_view dst, int32_t dtype, void* stream) {
+    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
+    if (!tci || !origins || !frame_ids || !tf || !dst.p || K < 0 || (K > 0 && !bands) || T <= 0 || H <= 0 || W <= 0 || B <= 0 || n <= 0)
+        return SSR_EINVAL;
+    const long C = (long)n * (3 + (long)K);
+    if (!aligned16(dst.p) || dst.cs % 8 || dst.coff % 8 || dst.coff < 0 || dst.coff + C > dst.cs || B > (1 << 20)) return SSR_EINVAL;
+    const size_t lds = ((size_t)n * (ROWW + 1) + (size_t)n * K * (BANDW + 1)) * 4;
+    if (H < CH || W < CH || n > T || n > 512 || lds > 65536 || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
+    const dim3 grid(B * CH), block(256);
+    if (dtype == SSR_F32) {
+        if (C % 4 == 0)
+            hipLaunchKernelGGL((scene_gather_tf_kernel<float, 4>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, tf, n, dst);
+        else
+            hipLaunchKernelGGL((scene_gather_tf_kernel<float, 1>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, tf, n, dst);
+    } else {
+        if (C % 8 == 0)
+            hipLaunchKernelGGL((scene_gather_tf_kernel<__bf16, 8>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, tf, n, dst);
+        else
+            hipLaunchKernelGGL((scene_gather_tf_kernel<__bf16, 1>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, tf, n, dst);
+    }
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_blend_add_tf(ssr_view src, int32_t dtype, const int32_t* origins, const int32_t* tf, int32_t B, int32_t C,
+                                      const int32_t* window, uint32_t* acc, int32_t Ho, int32_t Wo, int32_t* nonfinite, void* stream) {
+    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
+    if (!src.p || !origins || !tf || !window || !acc || !nonfinite || B <= 0 || C <= 0 || Ho <= 0 || Wo <= 0) return SSR_EINVAL;
+    if (!aligned4(src.p) || !aligned16(acc) || src.coff < 0 || src.coff + C > src.cs || C > MAX_C || B > (1 << 20)) return SSR_EINVAL;
+    if (Ho % 4 || Wo % 4 || Ho < SR || Wo < SR || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
+    const dim3 grid(B * (SR / 4)), block(256);
+    if (dtype == SSR_F32)
+        hipLaunchKernelGGL(scene_blend_add_tf_kernel<float>, grid, block, 0, ST(stream), src, origins, tf, B, C, window, acc, Ho, Wo, nonfinite);
+    else
+        hipLaunchKernelGGL(scene_blend_add_tf_kernel<__bf16>, grid, block, 0, ST(stream), src, origins, tf, B, C, window, acc, Ho, Wo, nonfinite);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+extern "C" int ssr_scene_blend_finish_scaled(const uint32_t* acc, const int32_t* Sy, const int32_t* Sx, int32_t C, int32_t scale,
+                                             uint8_t* mosaic, int32_t Ho, int32_t Wo, void* stream) {
+    if (!acc || !Sy || !Sx || !mosaic || C <= 0 || scale < 1 || Ho <= 0 || Wo <= 0) return SSR_EINVAL;
+    if (!aligned16(acc) || !aligned4(mosaic) || C > MAX_C) return SSR_EINVAL;
+    if (Ho % 4 || Wo % 4 || Ho < SR || Wo < SR) return SSR_EUNSUP;
+    const long units = (long)Ho * Wo * C / 4, blocks = (units + 255) / 256;
+    if (blocks > 0x7fffffffl) return SSR_EUNSUP;
+    hipLaunchKernelGGL(scene_blend_finish_scaled_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), acc, Sy, Sx, C,
+                       (uint32_t)scale, reinterpret_cast<uint32_t*>(mosaic), Ho, Wo);
     SSR_LAUNCH_CHECK();
     return SSR_OK;
 }

@@ -131,6 +131,7 @@ ABI_SYMBOLS = [
     "ssr_scene_gather_bands",
     "ssr_scene_frame_keys", "ssr_scene_rank_frames",
     "ssr_scene_support_add", "ssr_scene_apply_nodata",
+    "ssr_scene_gather_tf", "ssr_scene_blend_add_tf", "ssr_scene_blend_finish_scaled",
     "ssr_device_info", "ssr_abi_version",
 ]
 SCAN_MAX_RANGES = 8           # SSR_SCAN_MAX_RANGES: ranges per ssr_nonfinite_scan call
@@ -215,6 +216,9 @@ def lib() -> C.CDLL:
     l.ssr_scene_rank_frames.argtypes = [vp, i32, i32, i32, vp, vp]
     l.ssr_scene_support_add.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp]
     l.ssr_scene_apply_nodata.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp]
+    l.ssr_scene_gather_tf.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, View, i32, vp]
+    l.ssr_scene_blend_add_tf.argtypes = [View, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp]
+    l.ssr_scene_blend_finish_scaled.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp]
     l.ssr_device_info.argtypes = [C.c_char_p, i32]
     l.ssr_abi_version.argtypes = []
     for s in ABI_SYMBOLS:

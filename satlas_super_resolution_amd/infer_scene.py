@@ -18,7 +18,7 @@ straight from the plan's output into the mosaic, and the count of non-finite out
 
 Option keys: `data_dir`, `save_path`, `n_lr_images`, `network_g`, `path.*`, `compute_dtype` (default fp32h), `batch` (chunks per
 generator launch, default 64), `io_workers` as `infer_grid`; `scene_hw: [H, W]` for PNG scenes that are not square; `overlap`;
-`s2_bands`; `frame_select`; `nodata`, `nodata_min_support`.
+`s2_bands`; `frame_select`; `nodata`, `nodata_min_support`; `self_ensemble`.
 
 `overlap: K` (0 .. 16; absent: the path above, unchanged) takes scenes of ANY height and width >= 32 instead: chunks overlap their
 neighbours by K pixels, the last chunk of a row or column ends at the scene's edge, and the super-resolved chunks are cross-faded
@@ -51,7 +51,24 @@ low-resolution pixel of a frame HAS DATA if none of its three TCI samples is 0 (
 support < m becomes 0, every other sample max(1, sample): 0 stays reserved for NODATA in the output (`apply_nodata`).  The driver
 then writes a third file, `{save_path}/NAME/stitched_support.png`: min(support, 255), 8-bit grayscale [H, W].  All of it is integer
 work on the device (`ssr_scene_support_add`, `ssr_scene_apply_nodata`) between the upload and the one download, which grows by
-H W bytes; it works with `overlap`, `s2_bands` and both frame policies."""
+H W bytes; it works with `overlap`, `s2_bands` and both frame policies.
+
+`self_ensemble: true | false` (absent: false, the paths above, unchanged byte for byte and launch for launch) is BasicSR's
+`val.self_ensemble` (`SRModel.test_selfensemble`; the reference's model overrides `test`, so it never offers it) over chunks: every
+chunk goes through the generator under the eight flips and transposes of the square and the eight outputs are turned back and
+averaged, which takes away the orientation-dependent texture a GAN generator invents - satellite imagery has no preferred orientation.
+The transform set is BasicSR's ('v', 'h', 't': here bit 0 of the transform id flips the columns, bit 1 the rows, bit 2 transposes;
+`ensemble_transform`, `ensemble_inverse` state them).  The averaging is NOT BasicSR's float mean but this project's integer blend, so
+the bytes are not BasicSR's: each of the eight outputs in 13-bit fixed point ((uint32) (clamp(v, 0, 1) * 8191.0f) - eight rows per
+chunk would overflow the accumulator at the blend's 16 bits), times the blend window, into the same uint32 accumulator, and
+mosaic = acc * 255 // (8 * Sy * Sx * 8191).  It always runs on the accumulator path: with `overlap` as documented above, without it
+as overlap 0 (sizes still multiples of 32).  The generator's rows are the (chunk, transform) pairs in chunk-major order and `batch`
+slices that list, so a scene takes eight times the generator time; the frames of a chunk are chosen once, as without the option
+(`random` is consumed once per chunk), `nodata` and the support map are what they are without it.  On the device:
+`ssr_scene_gather_tf` writes a transformed chunk into the plan's input, `ssr_scene_blend_add_tf` turns the output back while it
+accumulates, `ssr_scene_blend_finish_scaled` divides.  Integer sums: the bytes do not depend on `batch`, and with `frame_select:
+clearest` and chunk origins symmetric about the centre the mosaic of a flipped or transposed scene is the flipped or transposed mosaic,
+byte for byte."""
 from __future__ import annotations
 
 import argparse
@@ -176,6 +193,52 @@ def check_nodata(nodata, min_support=1) -> Tuple[str, int]:
     if nodata == "fill" and min_support != 1:
         raise ValueError(f"min_support = {min_support} has a meaning under nodata: keep only (nodata = 'fill')")
     return nodata, int(min_support)
+
+
+ENSEMBLE = 8                  # the symmetries of the square: the rows a chunk takes in the generator under `self_ensemble`
+ENSEMBLE_ONE = 8191           # 1.0 in the self-ensemble's fixed point: 13 fractional bits (8 * 125 * 125 * 8191 < 2^32)
+
+
+def ensemble_transform(P: np.ndarray, tf: int) -> np.ndarray:
+    """The self-ensemble's transform tf (0 .. 7) of a chunk restated in numpy - the statement of the option (the inference path
+    computes it on the device: `scene_gather_tf`).  P: an array whose first two axes are the chunk's rows and columns ([32, 32, C_in]
+    going into the generator); the channel axis is untouched.  Bit 0 of tf flips the columns, bit 1 flips the rows, bit 2
+    transposes, applied in that order: the eight symmetries of the square, the set of BasicSR's `val.self_ensemble`
+    (SRModel.test_selfensemble: 'v', 'h', 't')."""
+    tf = int(tf)
+    if not 0 <= tf < ENSEMBLE:
+        raise ValueError(f"tf = {tf}: a transform id from 0 to {ENSEMBLE - 1}")
+    A = np.asarray(P)
+    if tf & 1:
+        A = A[:, ::-1]
+    if tf & 2:
+        A = A[::-1]
+    if tf & 4:
+        A = A.swapaxes(0, 1)
+    return A
+
+
+def ensemble_inverse(O: np.ndarray, tf: int) -> np.ndarray:
+    """What undoes `ensemble_transform(., tf)`: the bits in the opposite order (on the device: `scene_blend_add_tf`, which turns a
+    [128, 128, C_out] output back while it accumulates).  ensemble_inverse(ensemble_transform(P, tf), tf) == P."""
+    tf = int(tf)
+    if not 0 <= tf < ENSEMBLE:
+        raise ValueError(f"tf = {tf}: a transform id from 0 to {ENSEMBLE - 1}")
+    A = np.asarray(O)
+    if tf & 4:
+        A = A.swapaxes(0, 1)
+    if tf & 2:
+        A = A[::-1]
+    if tf & 1:
+        A = A[:, ::-1]
+    return A
+
+
+def check_self_ensemble(self_ensemble) -> bool:
+    """the refusal of the self-ensemble option, on the host: anything but a bool"""
+    if not isinstance(self_ensemble, (bool, np.bool_)):
+        raise ValueError(f"self_ensemble = {self_ensemble!r}: true or false")
+    return bool(self_ensemble)
 
 
 def check_scene_size(H: int, W: int, any_size: bool = False) -> None:
@@ -526,6 +589,69 @@ def scene_blend_finish(acc: torch.Tensor, Sy: torch.Tensor, Sx: torch.Tensor, mo
               "ssr_scene_blend_finish")
 
 
+def _check_tf(tf: torch.Tensor, B: int):
+    assert tf.is_cuda and tf.dtype == torch.int32 and tf.is_contiguous() and tuple(tf.shape) == (B,), (tf.dtype, tf.shape)
+
+
+def scene_gather_tf(scene: torch.Tensor, bands: Optional[torch.Tensor], origins: torch.Tensor, frame_ids: torch.Tensor,
+                    tf: torch.Tensor, dst: torch.Tensor, dtype: Optional[int] = None):
+    """`ensemble_transform` on the device: row b of dst is the transform tf[b] (int32 [B], device) of the chunk `scene_gather_at`
+    (bands None) or `scene_gather_bands` writes for origins[b] and frame_ids[b] - with tf[b] == 0 their bytes.  A row whose tf lies
+    outside 0 .. 7 is left as it is, as a row they skip."""
+    from . import hip
+    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
+    T, H, W = scene.shape[:3]
+    K = 0
+    if bands is not None:
+        assert bands.is_cuda and bands.dtype == torch.uint8 and bands.is_contiguous() and bands.dim() == 4 and bands.shape[0] >= 1 \
+            and tuple(bands.shape[1:]) == (T, H, W), (bands.dtype, bands.shape, scene.shape)
+        K = bands.shape[0]
+    _check_origins(origins)
+    assert frame_ids.dtype == torch.int32 and frame_ids.is_cuda and frame_ids.is_contiguous()
+    check_scene_size(H, W, True)
+    B, n = frame_ids.shape
+    _check_tf(tf, B)
+    assert origins.shape[0] == B and tuple(dst.shape[:3]) == (B, CHUNK, CHUNK) and dst.shape[3] >= (3 + K) * n, (origins.shape, dst.shape)
+    if dtype is None:
+        dtype = hip.dtype_code(dst.dtype)
+    hip.check(hip.lib().ssr_scene_gather_tf(_ptr(scene), None if bands is None else _ptr(bands), K, T, H, W, _ptr(origins),
+                                            _ptr(frame_ids), _ptr(tf), B, n, hip.view(dst), dtype, hip.stream_ptr()),
+              "ssr_scene_gather_tf")
+
+
+def scene_blend_add_tf(src: torch.Tensor, origins: torch.Tensor, tf: torch.Tensor, C: int, window: torch.Tensor, acc: torch.Tensor,
+                       nonfinite: torch.Tensor, dtype: Optional[int] = None):
+    """`scene_blend_add` of `ensemble_inverse(src[b], tf[b])` (tf int32 [B], device) in 13-bit fixed point (`ENSEMBLE_ONE`): the
+    eight rows of a chunk add up in acc, which `scene_blend_finish_scaled` divides by 8 x 8191 x the weight sums"""
+    from . import hip
+    B = origins.shape[0]
+    _check_origins(origins)
+    _check_tf(tf, B)
+    _check_acc(acc, C)
+    assert tuple(src.shape[:3]) == (B, SR_CHUNK, SR_CHUNK) and src.shape[3] >= C, src.shape
+    assert window.is_cuda and window.dtype == torch.int32 and window.is_contiguous() and tuple(window.shape) == (SR_CHUNK,)
+    assert nonfinite.dtype == torch.int32 and nonfinite.is_cuda
+    if dtype is None:
+        dtype = hip.dtype_code(src.dtype)
+    hip.check(hip.lib().ssr_scene_blend_add_tf(hip.view(src), dtype, _ptr(origins), _ptr(tf), B, C, _ptr(window), _ptr(acc),
+                                               acc.shape[0], acc.shape[1], _ptr(nonfinite), hip.stream_ptr()), "ssr_scene_blend_add_tf")
+
+
+def scene_blend_finish_scaled(acc: torch.Tensor, Sy: torch.Tensor, Sx: torch.Tensor, mosaic: torch.Tensor, scale: int):
+    """`scene_blend_finish` with the denominator's scale given: mosaic = acc * 255 // (Sy Sx scale); ENSEMBLE * ENSEMBLE_ONE under
+    the self-ensemble"""
+    from . import hip
+    Ho, Wo, C = acc.shape
+    _check_acc(acc, C)
+    assert mosaic.is_cuda and mosaic.dtype == torch.uint8 and mosaic.is_contiguous() and tuple(mosaic.shape) == (Ho, Wo, C)
+    for S, L in ((Sy, Ho), (Sx, Wo)):
+        assert S.is_cuda and S.dtype == torch.int32 and S.is_contiguous() and tuple(S.shape) == (L,)
+    scale = int(scale)
+    assert 1 <= scale < 1 << 31, scale
+    hip.check(hip.lib().ssr_scene_blend_finish_scaled(_ptr(acc), _ptr(Sy), _ptr(Sx), C, scale, _ptr(mosaic), Ho, Wo, hip.stream_ptr()),
+              "ssr_scene_blend_finish_scaled")
+
+
 class _Pending:
     """a scene whose launches are queued: the pinned host buffer its mosaic and counter (under `nodata: keep` the support map
     behind them) are being copied to, and the event behind that copy"""
@@ -619,14 +745,19 @@ def _frames_T(frames) -> Optional[int]:
 
 
 def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[torch.Tensor] = None, bands=None,
-                   frame_select: str = "random", nodata: str = "fill", min_support: int = 1) -> _Pending:
+                   frame_select: str = "random", nodata: str = "fill", min_support: int = 1, self_ensemble: bool = False) -> _Pending:
     """upload, zero scan, frame choice (the one host round trip: chunks x T flags down, chunks x n ids up), then every batch of
     chunks through gather -> generator -> scatter and the download of mosaic + counter; returns without waiting for them.
     With bands the gather is `scene_gather_bands` at the chunks' origins (32 i, 32 j); everything else is the same.
     frame_select "clearest": the frame choice is keys -> rank on the current stream instead, and nothing comes back to the host
     before the mosaic does.
     nodata "keep": a zeroed support map, `scene_support_add` beside every gather (at the origins (32 i, 32 j)), `scene_apply_nodata`
-    behind the last scatter, and the support map behind the counter in the same download; nothing comes back earlier than before."""
+    behind the last scatter, and the support map behind the counter in the same download; nothing comes back earlier than before.
+    self_ensemble: the accumulator path with overlap 0 (`_enqueue_scene_blended`: the same chunks in the same order, so the same
+    frame choice) under this path's refusal of sizes that are no multiples of 32."""
+    if check_self_ensemble(self_ensemble):
+        return _enqueue_scene_blended(model, frames, n_lr_images, 0, batch, host, bands=bands, frame_select=frame_select,
+                                      nodata=nodata, min_support=min_support, self_ensemble=True, any_size=False)
     if getattr(model, "scale", SCALE) != SCALE:
         raise NotImplementedError(f"scene inference runs scale {SCALE} generators only (scale = {model.scale})")
     n, batch = int(n_lr_images), int(batch)
@@ -674,11 +805,16 @@ def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[t
 
 
 def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch: int, host: Optional[torch.Tensor] = None,
-                           bands=None, frame_select: str = "random", nodata: str = "fill", min_support: int = 1) -> _Pending:
+                           bands=None, frame_select: str = "random", nodata: str = "fill", min_support: int = 1,
+                           self_ensemble: bool = False, any_size: bool = True) -> _Pending:
     """`_enqueue_scene` for a scene of any size >= 32 x 32 cut into chunks that overlap: upload, zero scan at the origins, frame
     choice (the one host round trip; with frame_select "clearest" keys -> rank on the device, no round trip), a zeroed accumulator,
     every batch of chunks through gather -> generator -> blend-add, the division by the weight sums and the download of mosaic +
-    counter; nodata "keep" as in `_enqueue_scene`, with `scene_apply_nodata` behind `scene_blend_finish`"""
+    counter; nodata "keep" as in `_enqueue_scene`, with `scene_apply_nodata` behind `scene_blend_finish`.
+    self_ensemble: the generator's rows are the (chunk, tf) pairs, chunk-major with tf 0 .. 7 inside a chunk, and `batch` slices THAT
+    list: gather_tf -> generator -> blend_add_tf per slice, then `scene_blend_finish_scaled`.  The frames are chosen once per chunk
+    as without it, and `scene_support_add` runs once per chunk (beside the launch that holds the chunk's tf 0 row)."""
+    self_ensemble = check_self_ensemble(self_ensemble)          # (before anything is uploaded)
     if getattr(model, "scale", SCALE) != SCALE:
         raise NotImplementedError(f"scene inference runs scale {SCALE} generators only (scale = {model.scale})")
     n, batch = int(n_lr_images), int(batch)
@@ -688,7 +824,7 @@ def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch:
     check_frame_select(frame_select, _frames_T(frames), n)
     nodata, min_support = check_nodata(nodata, min_support)
     keep = nodata == "keep"
-    scene, C_out, bands = _upload_scene(model, frames, n, any_size=True, bands=bands)
+    scene, C_out, bands = _upload_scene(model, frames, n, any_size=any_size, bands=bands)
     dev = scene.device
     T, H, W = scene.shape[:3]
     grid = scene_chunk_grid(H, W, overlap)
@@ -707,18 +843,34 @@ def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch:
     support = torch.zeros(H, W, dtype=torch.int32, device=dev) if keep else None
     acc = torch.zeros(Ho, Wo, C_out, dtype=torch.int32, device=dev)  # 4 bytes per output sample, this scene's own
     with torch.no_grad():
-        for c0 in range(0, n_chunks, batch):
-            org = origins[c0:c0 + batch]
-            plan = model.plan_for_inference(org.shape[0], CHUNK, CHUNK)
-            if bands is None:
-                scene_gather_at(scene, org, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
-            else:
-                scene_gather_bands(scene, bands, org, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
-            if keep:
-                scene_support_add(scene, org, frame_ids[c0:c0 + batch], support)
-            model.run_forward(plan)
-            scene_blend_add(plan.out, org, C_out, window, acc, counter, plan.dt)
-        scene_blend_finish(acc, Sy, Sx, mosaic)
+        if self_ensemble:
+            row_org = origins.repeat_interleave(ENSEMBLE, dim=0)              # the rows: (chunk, tf), chunk-major
+            row_ids = frame_ids.repeat_interleave(ENSEMBLE, dim=0)
+            row_tf = torch.arange(ENSEMBLE, dtype=torch.int32, device=dev).repeat(n_chunks)
+            for r0 in range(0, ENSEMBLE * n_chunks, batch):
+                r1 = min(r0 + batch, ENSEMBLE * n_chunks)
+                org, tf = row_org[r0:r1], row_tf[r0:r1]
+                plan = model.plan_for_inference(r1 - r0, CHUNK, CHUNK)
+                scene_gather_tf(scene, bands, org, row_ids[r0:r1], tf, plan.xin, plan.dt)
+                c0, c1 = -(-r0 // ENSEMBLE), -(-r1 // ENSEMBLE)              # the chunks whose tf 0 row lies in this slice
+                if keep and c1 > c0:
+                    scene_support_add(scene, origins[c0:c1], frame_ids[c0:c1], support)
+                model.run_forward(plan)
+                scene_blend_add_tf(plan.out, org, tf, C_out, window, acc, counter, plan.dt)
+            scene_blend_finish_scaled(acc, Sy, Sx, mosaic, ENSEMBLE * ENSEMBLE_ONE)
+        else:
+            for c0 in range(0, n_chunks, batch):
+                org = origins[c0:c0 + batch]
+                plan = model.plan_for_inference(org.shape[0], CHUNK, CHUNK)
+                if bands is None:
+                    scene_gather_at(scene, org, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
+                else:
+                    scene_gather_bands(scene, bands, org, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
+                if keep:
+                    scene_support_add(scene, org, frame_ids[c0:c0 + batch], support)
+                model.run_forward(plan)
+                scene_blend_add(plan.out, org, C_out, window, acc, counter, plan.dt)
+            scene_blend_finish(acc, Sy, Sx, mosaic)
         if keep:
             scene_apply_nodata(mosaic, support, min_support, support_u8)
     del acc
@@ -744,7 +896,7 @@ def _finish(pending: _Pending, return_support: bool):
 
 def super_resolve_scene_blended(model, frames, n_lr_images: int, overlap: int = 8, batch: int = 64, bands=None,
                                 frame_select: str = "random", nodata: str = "fill", min_support: int = 1,
-                                return_support: bool = False):
+                                return_support: bool = False, self_ensemble: bool = False):
     """frames: uint8 [T, H, W, 3] (numpy array or CUDA tensor), H and W ANY values >= 32 -> uint8 [4H, 4W, 3].  The scene is cut into
     32 x 32 chunks that overlap their neighbours by `overlap` pixels (0 .. 16; `scene_chunk_origins`: the last chunk of an axis ends
     at the scene's edge), every chunk is super-resolved from `n_lr_images` of its frames (select_scene_frames over the chunks in
@@ -754,14 +906,26 @@ def super_resolve_scene_blended(model, frames, n_lr_images: int, overlap: int = 
     acquisition) and is allocated per scene, next to the scene itself and the 12 H W bytes of the mosaic.
     Refusals as `super_resolve_scene`: scale 4 generators only, n_lr_images against the generator's channels, FloatingPointError
     (metrics.nonfinite_error) if any output sample is NaN / Inf.  `bands`, `frame_select`, `nodata`, `min_support` and
-    `return_support` as `super_resolve_scene`; here up to 3 chunks per axis cover a pixel, so support <= 9 n_lr_images."""
+    `return_support` as `super_resolve_scene`; here up to 3 chunks per axis cover a pixel, so support <= 9 n_lr_images.
+    self_ensemble=True (a bool, ValueError otherwise, before anything is uploaded) is BasicSR's `val.self_ensemble`
+    (SRModel.test_selfensemble) over chunks: every chunk goes through the generator under the eight flips and transposes of the
+    square (`ensemble_transform`, tf 0 .. 7), the eight outputs are turned back (`ensemble_inverse`) and averaged.  The transform set
+    is BasicSR's; the averaging is this project's integer blend, not a float mean, so the bytes are not BasicSR's: every output in
+    13-bit fixed point (`ENSEMBLE_ONE`), times the blend window, into the same accumulator, and
+    mosaic = acc * 255 // (8 * Sy * Sx * 8191).  The generator's rows are the (chunk, tf) pairs in chunk-major order and `batch`
+    slices that list, so a scene costs eight times the generator launches' rows; integer sums keep the bytes independent of
+    `batch`.  Frames are chosen once per chunk exactly as without it (all eight transforms of a chunk use them, `random` is
+    consumed once per chunk), support and `nodata` are what they are without it, and the non-finite count covers all eight
+    outputs.  With `frame_select="clearest"` the mosaic of a flipped or transposed scene is the flipped or transposed mosaic, byte
+    for byte, when the chunk origins are symmetric about the centre."""
     _check_return_support(nodata, min_support, return_support)
     return _finish(_enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, bands=bands, frame_select=frame_select,
-                                          nodata=nodata, min_support=min_support), return_support)
+                                          nodata=nodata, min_support=min_support, self_ensemble=check_self_ensemble(self_ensemble)),
+                   return_support)
 
 
 def super_resolve_scene(model, frames, n_lr_images: int, batch: int = 64, bands=None, frame_select: str = "random",
-                        nodata: str = "fill", min_support: int = 1, return_support: bool = False):
+                        nodata: str = "fill", min_support: int = 1, return_support: bool = False, self_ensemble: bool = False):
     """frames: uint8 [T, H, W, 3] (numpy array or CUDA tensor), H and W multiples of 32 (ValueError otherwise) -> uint8
     [4H, 4W, 3]: every 32 x 32 chunk super-resolved on its own from `n_lr_images` of its frames (select_scene_frames) and placed
     at rows 128 i, columns 128 j.  Raises FloatingPointError (metrics.nonfinite_error) if any output sample is NaN / Inf.
@@ -785,10 +949,13 @@ def super_resolve_scene(model, frames, n_lr_images: int, batch: int = 64, bands=
     (`apply_nodata`).  Computed on the device, without a further round trip; a NaN / Inf under a masked pixel still raises.
     return_support=True returns (mosaic, support_u8) with support_u8 = min(support, 255), uint8 [H, W].  ValueError, before anything
     is uploaded, for another value of nodata, a min_support that is not an integer >= 1 or differs from 1 under "fill", and
-    return_support without "keep"."""
+    return_support without "keep".
+    self_ensemble=True: as `super_resolve_scene_blended(..., overlap=0, self_ensemble=True)` - the eight flips and transposes of
+    every chunk through the generator, turned back and averaged by the integer blend at 13 fractional bits - with this function's
+    refusal of sizes that are no multiples of 32.  A bool; ValueError otherwise, before anything is uploaded."""
     _check_return_support(nodata, min_support, return_support)
     return _finish(_enqueue_scene(model, frames, n_lr_images, batch, bands=bands, frame_select=frame_select, nodata=nodata,
-                                  min_support=min_support), return_support)
+                                  min_support=min_support, self_ensemble=check_self_ensemble(self_ensemble)), return_support)
 
 
 # ------------------------------------------------------------------------------------------------ driver
@@ -804,6 +971,7 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
     frame_select = check_frame_select(opt.get("frame_select", "random"))      # absent: random, the reference's rule
     nodata, min_support = check_nodata(opt.get("nodata", "fill"), opt.get("nodata_min_support", 1))      # absent: fill, as ever
     keep = nodata == "keep"
+    self_ensemble = check_self_ensemble(opt.get("self_ensemble", False))      # absent: false, the launches of the paths above
     if device is None:
         device = torch.device("cuda")
     if model is None:
@@ -892,10 +1060,11 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
                 reading = start_read(k + 1) if k + 1 < len(mine) else None
                 if blended:
                     pending = _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, hosts[k & 1], bands=bands,
-                                                     frame_select=frame_select, nodata=nodata, min_support=min_support)
+                                                     frame_select=frame_select, nodata=nodata, min_support=min_support,
+                                                     self_ensemble=self_ensemble)
                 else:
                     pending = _enqueue_scene(model, frames, n_lr_images, batch, hosts[k & 1], bands=bands, frame_select=frame_select,
-                                             nodata=nodata, min_support=min_support)
+                                             nodata=nodata, min_support=min_support, self_ensemble=self_ensemble)
                 hosts[k & 1] = pending.host
                 first = np.array(frames[0])
                 del frames, bands
@@ -921,6 +1090,8 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
            "frame_select": frame_select}
     if keep:
         res.update(nodata=nodata, nodata_min_support=min_support)
+    if self_ensemble:
+        res.update(self_ensemble=True)
     return res
 
 

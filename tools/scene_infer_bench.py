@@ -40,6 +40,14 @@ with `--overlap K` through `super_resolve_scene_blended(overlap=K)` instead.  Bo
 `--nodata-trace` (with `--nodata keep`): the warm-up and one `keep` run, for a kernel trace.
 
     python tools/scene_infer_bench.py fp32h --nodata keep > profiles/scene_nodata/bench.json
+
+`--self-ensemble` runs another leg INSTEAD: the scene of the `--nodata` leg through `super_resolve_scene_blended(overlap=K,
+frame_select="clearest")` (K from `--overlap`, default 8) as it is and with `self_ensemble=True` (eight generator rows per chunk),
+the two alternating five times after a warm-up of each, upload to download, no files.  The generator sees eight times the rows, so
+the expected ratio is about 8.  `--ensemble-trace` (with `--self-ensemble`): the warm-up and one self-ensembled run, for a kernel
+trace.
+
+    python tools/scene_infer_bench.py fp32h --self-ensemble --overlap 8 > profiles/scene_ensemble/bench.json
 """
 import json
 import os
@@ -210,7 +218,60 @@ def nodata_leg(mode, overlap, trace_only):
     print(json.dumps(rec))
 
 
+def ensemble_leg(mode, overlap, trace_only):
+    from satlas_super_resolution_amd.archs.rrdbnet_arch import SSR_RRDBNet
+    from satlas_super_resolution_amd.infer_scene import scene_chunk_origins, super_resolve_scene_blended
+    rng = np.random.RandomState(0)
+    scene = _scene(rng, 8, 512, 512)
+    yy, xx = np.mgrid[0:512, 0:512]
+    scene[:, 3 * xx + yy < 300] = 0                 # the scene of the --nodata leg
+    scene[1:4, 300:400, 200:420] = 0
+    net = SSR_RRDBNet(24, 3, 4, 64, 23, 32, compute_dtype=mode).cuda().eval().freeze_packed()
+
+    def run(ensemble):
+        kw = dict(self_ensemble=True) if ensemble else {}      # absent, not False: the call as it was before the option
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = super_resolve_scene_blended(net, scene, 8, overlap=overlap, frame_select="clearest", **kw)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    if trace_only:
+        run(True)
+        print(json.dumps({"self_ensemble_seconds": run(True)[0]}))
+        return
+    names = {"plain": False, "self_ensemble": True}
+    warm = {k: run(v)[0] for k, v in names.items()}      # plans, graph capture, first touch
+    secs = {k: [] for k in names}
+    for _ in range(5):
+        for k, v in names.items():
+            secs[k].append(run(v)[0])
+    plain, ens = run(False)[1], run(True)[1]
+    med = statistics.median
+    diff = np.abs(plain.astype(np.int16) - ens.astype(np.int16))
+    print(json.dumps({
+        "workload": "one 512 x 512 Sentinel-2 scene of 8 frames with a NODATA wedge, SSR_RRDBNet(nf=64, nb=23, gc=32), random weights, "
+                    "n_lr_images 8, batch 64, frame_select clearest, one GPU; wall time of one call, upload to download, no files; "
+                    "the blended path as it is and with self_ensemble alternate in one process",
+        "device": torch.cuda.get_device_name(0), "compute_dtype": mode, "overlap": overlap,
+        "chunks": len(scene_chunk_origins(512, overlap)) ** 2, "generator_rows": {"plain": len(scene_chunk_origins(512, overlap)) ** 2,
+                                                                                   "self_ensemble": 8 * len(scene_chunk_origins(512, overlap)) ** 2},
+        "runs": {k: {"warm_up_seconds": warm[k], "seconds": secs[k], "median": med(secs[k]), "min": min(secs[k]),
+                     "spread": max(secs[k]) - min(secs[k])} for k in names},
+        "self_ensemble_over_plain": med(secs["self_ensemble"]) / med(secs["plain"]),
+        "self_ensemble_against_plain": {"mean_difference_levels": float(diff.mean()), "largest_difference_levels": int(diff.max())}}))
+
+
 def main():
+    if "--self-ensemble" in sys.argv:
+        argv = [a for a in sys.argv[1:] if a != "--self-ensemble"]
+        overlap = 8
+        if "--overlap" in argv:
+            j = argv.index("--overlap")
+            overlap = int(argv[j + 1])
+            argv = argv[:j] + argv[j + 2:]
+        rest = [a for a in argv if not a.startswith("--")]
+        return ensemble_leg(rest[0] if rest else "fp32h", overlap, "--ensemble-trace" in argv)
     if "--nodata" in sys.argv:
         k = sys.argv.index("--nodata")
         if sys.argv[k + 1] != "keep":
