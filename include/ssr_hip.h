@@ -352,6 +352,17 @@ int ssr_usm_sharp(const float* src, float* dst, int32_t planes, int32_t H, int32
 /* loss_out[0] += weight * mean|a-b| over (N,H,W,C valid); grad (optional) = weight*sign(a-b)/numel */
 int ssr_l1_loss(ssr_view a, ssr_view b, ssr_view grad, int32_t dtype, int64_t npix, int32_t C, float weight,
                 float* loss_out, void* stream);
+/* SSIM loss of train.ssim_opt (SSIMLoss; csrc/ssim.hip; additive: the ABI version stays 3).  x (the generator's output), y (the target)
+ * and grad are NHWC views of N x H x W pixels with C valid channels; fp32 storage for SSR_F32 / SSR_F32X3, bf16 for SSR_BF16, fp32
+ * arithmetic in both.  Per channel plane: S = the 5 x 5 Gaussian-window (sigma 1.5) SSIM over 2-pixel reflect padding (edge not
+ * repeated), C1 = 1e-4, C2 = 9e-4, eps = 1e-12;  loss_out[0] += weight * mean(clamp((1 - S) / 2, 0, 1)) over N*H*W*C elements
+ * (SSR_DETERMINISTIC in dtype: per-block slots as ssr_l1_loss, at most SSR_LOSS_SLOTS blocks).  grad (optional: a null view gives the
+ * loss only) receives d loss / d x: accumulate 0 writes the C valid channels, 1 adds to them (bf16: one rounding of the sum); channels
+ * >= C of grad are never written, channels >= C of x and y never read.  The gradient is a gather (no float atomics): two launches
+ * on the same inputs give the same bytes.  Null x or y, N or C <= 0, H or W < 3, or a view narrower than coff + C: SSR_EINVAL; another
+ * dtype: SSR_EUNSUP; no launch in either case. */
+int ssr_ssim_loss(ssr_view x, ssr_view y, ssr_view grad, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, float weight,
+                  int32_t accumulate, float* loss_out, void* stream);
 /* BCE-with-logits against constant target t: loss_out[0] += weight*mean(softplus(x) - x*t);
  * mean_out[0] += mean(x) (optional); grad = weight*(sigmoid(x)-t)/numel (optional) */
 int ssr_bce_logits_loss(ssr_view x, ssr_view grad, int32_t dtype, int64_t npix, float target, float weight,

@@ -8,9 +8,9 @@
 
 Same registry name and the same `opt` dictionary (YAML) keys.  Instead of autograd over ~41k ATen ops per
 step, optimize_parameters() replays the fused HIP-graph step of train_step.ESRGANTrainStep.
-Scope: L1 + vanilla-GAN (+ VGG19 perceptual: feature and Gram-style terms) losses, USM-sharpened ground truth, `feed_disc_lr`
-and `old_hr` discriminator inputs.  Anything this path does not implement raises NotImplementedError naming the
-option (clip / ssim / ldl losses, other optimizers or schedulers, weight decay) — nothing is silently ignored."""
+Scope: L1 + vanilla-GAN (+ VGG19 perceptual: feature and Gram-style terms; + SSIM) losses, USM-sharpened ground truth,
+`feed_disc_lr` and `old_hr` discriminator inputs.  Anything this path does not implement raises NotImplementedError naming the
+option (clip / ldl losses, other optimizers or schedulers, weight decay) — nothing is silently ignored."""
 from __future__ import annotations
 
 import math
@@ -76,6 +76,32 @@ def step_config_from_opt(opt: dict) -> StepConfig:
         deterministic=bool(opt.get("deterministic", False)))   # ours: fixed-order reductions only (bit-identical runs; train_step.StepConfig)
 
 
+def train_config_from_opt(opt: dict) -> StepConfig:
+    """step_config_from_opt plus `train.ssim_opt` (SSIMLoss: ssr/losses/basic_loss.py:50-60, built at ssr_esrgan_model.py:62-65): what
+    SSRESRGANModel configures its step from.
+
+    Why two functions: step_config_from_opt's refusal of `ssim_opt` is pinned by tests/test_host_boundary.py, so it stays as it is; this
+    one validates the block, hands a copy of `opt` without it to step_config_from_opt and sets StepConfig.ssim on the result.  Folding
+    the two into one goes with a change of that test.
+
+    The block holds `type: SSIMLoss` and optionally `loss_weight` (default 1.0, as SSIMLoss.__init__); the window (5 x 5) is fixed in
+    the reference's forward.  Any other type or key raises NotImplementedError naming it."""
+    train_opt = opt.get("train", {}) or {}
+    so = train_opt.get("ssim_opt")
+    if not so:
+        return step_config_from_opt(opt)
+    if so.get("type") != "SSIMLoss":
+        raise NotImplementedError(f"train.ssim_opt.type={so.get('type')!r}: only SSIMLoss")
+    for k in so:
+        if k not in ("type", "loss_weight"):
+            raise NotImplementedError(f"train.ssim_opt.{k}: SSIMLoss takes loss_weight only")
+    rest = dict(opt)
+    rest["train"] = {k: v for k, v in train_opt.items() if k != "ssim_opt"}
+    cfg = step_config_from_opt(rest)
+    cfg.ssim = {"loss_weight": float(so.get("loss_weight", 1.0))}
+    return cfg
+
+
 @MODEL_REGISTRY.register()
 class SSRESRGANModel:
     def __init__(self, opt: dict):
@@ -96,7 +122,7 @@ class SSRESRGANModel:
         if self.is_train:      # test.py builds the model with is_train=False: generator only (SRGANModel.__init__ / init_training_settings)
             self.d_kwargs = _arch_kwargs(opt["network_d"], "SSR_UNetDiscriminatorSN")
             self.d_kwargs.pop("compute_dtype", None)
-            self.cfg = step_config_from_opt(opt)
+            self.cfg = train_config_from_opt(opt)
         else:
             self.d_kwargs, self.cfg = None, StepConfig()
         sch = opt.get("train", {}).get("scheduler", {})

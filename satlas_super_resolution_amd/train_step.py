@@ -37,12 +37,14 @@ class StepConfig:
     gan_gt_usm: bool = False       # D real input = USM-sharpened gt (:127-129; yml :11)
     percep_gt_usm: bool = False    # perceptual target = USM-sharpened gt (:125-126; yml :10)
     perceptual: Optional[Dict] = None   # train.perceptual_opt (VGG19 feature L1, :153-160; yml :123-137)
+    ssim: Optional[Dict] = None         # train.ssim_opt (SSIMLoss, :163-166; ssimloss_esrgan_s2naip_urban.yml): {"loss_weight": w}
     real_label: float = 1.0
     fake_label: float = 0.0
     deterministic: bool = False    # fixed-order reductions only: two runs give bit-identical parameters (engine.deterministic; SSR_DETERMINISTIC=1)
 
 
 LOSS_KEYS = ("l_g_pix", "l_g_gan", "l_d_real", "out_d_real", "l_d_fake", "out_d_fake")
+N_LOSS = 9      # scalars of the loss arena: LOSS_KEYS, then 6 l_g_percep, 7 l_g_style, 8 l_g_ssim
 
 
 class AdamState:
@@ -123,7 +125,8 @@ class ESRGANTrainStep:
                 by_flag[flag] = z(B, H, W, cdp)
             return by_flag[flag]
         self.l1_tgt = target_for(bool(cfg.l1_gt_usm))
-        self.percep_tgt = target_for(bool(cfg.percep_gt_usm)) if cfg.perceptual else None
+        # the SSIM term takes the perceptual target (ssr_esrgan_model.py:163-166: cri_ssim(self.output, percep_gt))
+        self.percep_tgt = target_for(bool(cfg.percep_gt_usm)) if (cfg.perceptual or cfg.ssim) else None
         self._tgt_by_flag = by_flag
         self._gt_usm = None   # fp32 NCHW scratch for ssr_usm_sharp
         # deterministic mode (cfg.deterministic / SSR_DETERMINISTIC=1): every loss scalar is SSR_LOSS_SLOTS per-block slots that
@@ -134,7 +137,7 @@ class ESRGANTrainStep:
         with engine.deterministic_mode(self.det):
             self.loss_dt = self.dt | (hip.DETERMINISTIC if self.det else 0)
             self.loss_stride = hip.LOSS_SLOTS if self.det else 1
-            self.losses = torch.zeros(8 * self.loss_stride, dtype=torch.float32, device=dev)
+            self.losses = torch.zeros(N_LOSS * self.loss_stride, dtype=torch.float32, device=dev)
             self.d_plan = engine.DiscriminatorPlan(self.d_store, B, H, W, num_in_ch=cd,
                                                    num_feat=d_kwargs.get("num_feat", 64),
                                                    skip_connection=d_kwargs.get("skip_connection", True))
@@ -273,6 +276,10 @@ class ESRGANTrainStep:
         hip.check(hip.lib().ssr_l1_loss(view(self.fake_in), view(self.l1_tgt), view(self.grad_l1), self.loss_dt,
                                         self.B * self.H * self.W, self.cout, cfg.l1_weight, self.losses.data_ptr(),
                                         hip.stream_ptr()), "ssr_l1_loss")   # :147-150
+        if cfg.ssim:                                                       # :163-166; its image gradient joins the L1 gradient buffer
+            hip.check(hip.lib().ssr_ssim_loss(view(self.fake_in), view(self.percep_tgt), view(self.grad_l1), self.loss_dt, self.B,
+                                              self.H, self.W, self.cout, float(cfg.ssim.get("loss_weight", 1.0)), 1,
+                                              self.losses.data_ptr() + 4 * 8 * self.loss_stride, hip.stream_ptr()), "ssr_ssim_loss")
         if self.p_plan is not None:                                        # :153-160
             self.p_plan.fwd_target.run()
             self.p_plan.fwd.run()
@@ -465,13 +472,15 @@ class ESRGANTrainStep:
     # ------------------------------------------------------------------ results
     def log(self) -> "OrderedDict[str, float]":
         """get_current_log(): one host sync, only when the caller logs (train.py:116-121)."""
-        scal = self.losses if not self.det else self.losses.view(8, self.loss_stride).double().cpu().sum(1).float().to(self.losses.device)
+        scal = self.losses if not self.det else self.losses.view(N_LOSS, self.loss_stride).double().cpu().sum(1).float().to(self.losses.device)
         vals = self.dp.reduce_scalars(scal).tolist()      # det: the per-block slots added in index order on the host
         out = OrderedDict((k, vals[i]) for i, k in enumerate(LOSS_KEYS))
         if self.p_plan is not None and self.p_plan.feature:
             out["l_g_percep"] = vals[6]
         if self.p_plan is not None and self.p_plan.style:      # ssr_esrgan_model.py:157-160
             out["l_g_style"] = vals[7]
+        if self.cfg.ssim:
+            out["l_g_ssim"] = vals[8]
         return out
 
     def output(self) -> torch.Tensor:
