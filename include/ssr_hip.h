@@ -367,6 +367,30 @@ int ssr_ssim_loss(ssr_view x, ssr_view y, ssr_view grad, int32_t dtype, int32_t 
  * mean_out[0] += mean(x) (optional); grad = weight*(sigmoid(x)-t)/numel (optional) */
 int ssr_bce_logits_loss(ssr_view x, ssr_view grad, int32_t dtype, int64_t npix, float target, float weight,
                         float* loss_out, float* mean_out, void* stream);
+/* The other pixel and GAN losses of BasicSR 1.4.2 (csrc/losses.hip; additive: the ABI version stays 3), with the conventions of
+ * ssr_l1_loss / ssr_bce_logits_loss: NHWC views, fp32 storage for SSR_F32 / SSR_F32X3 and bf16 for SSR_BF16 (fp32 terms, fp64 partial
+ * sums), grad optional (a null view gives the loss only; channels outside the C valid ones are never written), loss_out[0] +=
+ * weight * mean(...), SSR_DETERMINISTIC in dtype: per-block slots, at most SSR_LOSS_SLOTS blocks.  One launch each, the inputs read
+ * once, no scratch.
+ * ssr_pixel_loss (basicsr/losses/basic_loss.py: MSELoss, CharbonnierLoss; reduction 'mean'), d = a - b, n = npix * C:
+ *   kind 1 MSE          weight * mean(d^2)                grad = 2 * weight * d / n
+ *   kind 2 Charbonnier  weight * mean(sqrt(d^2 + eps))    grad = weight * d / (n * sqrt(d^2 + eps)), 0 where d == 0
+ *   (eps: BasicSR's default is 1e-12; not read by kind 1).
+ * ssr_gan_loss (basicsr/losses/gan_loss.py: GANLoss.forward), one logit x per pixel, n = npix, w = weight (the caller passes 1 for
+ * is_disc and loss_weight otherwise, as for ssr_bce_logits_loss); target_val is the label of gan_type 1 and not read by the others
+ * (GANLoss.get_target_label); is_disc is read by gan_type 4 only:
+ *   gan_type 1 lsgan          w * mean((x - target_val)^2)                                     grad = 2 w (x - target_val) / n
+ *   gan_type 2 wgan           real: -w * mean(x), fake: w * mean(x)                            grad = -+ w / n
+ *   gan_type 3 wgan_softplus  real: w * mean(softplus(-x)), fake: w * mean(softplus(x))        grad = w (sigmoid(x) - 1) / n, w sigmoid(x) / n
+ *   gan_type 4 hinge          is_disc: real w * mean(relu(1 - x)), fake w * mean(relu(1 + x))  grad = -+ w / n where the relu's argument
+ *                             is > 0 (strictly, as torch), else 0;  generator: -w * mean(x)    grad = -w / n
+ *   softplus(z) = max(z, 0) + log1p(exp(-|z|)).  mean_out[0] += mean(x) (optional).
+ * A null input, npix or C <= 0, a view narrower than coff + C, eps < 0 (or NaN): SSR_EINVAL; another dtype, kind or gan_type:
+ * SSR_EUNSUP; no launch in either case. */
+int ssr_pixel_loss(ssr_view a, ssr_view b, ssr_view grad, int32_t dtype, int64_t npix, int32_t C, int32_t kind, float eps, float weight,
+                   float* loss_out, void* stream);
+int ssr_gan_loss(ssr_view x, ssr_view grad, int32_t dtype, int64_t npix, int32_t gan_type, int32_t target_is_real, int32_t is_disc,
+                 float target_val, float weight, float* loss_out, float* mean_out, void* stream);
 
 /* dst[e] += sum over p = 0 .. parts-1 (in that order) of src[p * stride + e], e < n: the fixed-order sum of per-split partial
  * weight gradients (deterministic mode: each pixel-range split of a layer is given its own partial dW / db as `dw` / `db` of a

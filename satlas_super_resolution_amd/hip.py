@@ -20,6 +20,8 @@ F32H3 = 3                     # SSR_F32H: forward convolutions with fp16-split o
 ACT_NONE, ACT_LRELU, ACT_RELU = 0, 1, 2
 DETERMINISTIC = 0x200          # OR-ed into the dtype of ssr_l1_loss / ssr_bce_logits_loss: per-block loss slots (include/ssr_hip.h)
 LOSS_SLOTS = 256
+PIXEL_KINDS = {"MSELoss": 1, "CharbonnierLoss": 2}                            # `kind` of ssr_pixel_loss (L1Loss: ssr_l1_loss)
+GAN_TYPES = {"lsgan": 1, "wgan": 2, "wgan_softplus": 3, "hinge": 4}          # `gan_type` of ssr_gan_loss (vanilla: ssr_bce_logits_loss)
 SN_BWD_SLOTS = 64
 BILINEAR_FLAT = 0x100         # OR-ed into the dtype of ssr_bilinear2x_fwd / _bwd: per-pixel kernels for this call (include/ssr_hip.h)
 
@@ -122,7 +124,7 @@ class AdamArgs(C.Structure):
 ABI_SYMBOLS = [
     "ssr_conv2d", "ssr_conv2d_fixup", "ssr_conv2d_batch", "ssr_conv2d_impl", "ssr_conv2d_variant", "ssr_conv2d_symbol", "ssr_conv2d_chain", "ssr_conv2d_chain_ok", "ssr_conv2d_chain_state_bytes", "ssr_conv2d_ck", "ssr_conv2d_s2d_ok", "ssr_rdb_forward", "ssr_rdb_backward", "ssr_rdb_tile_of", "ssr_conv2d_wgrad", "ssr_wgrad_reduce", "ssr_wgrad_tiles", "ssr_wgrad_ci_tile", "ssr_wgrad_co_tile", "ssr_pack_weights", "ssr_pack_dgrad_gather", "ssr_add_views", "ssr_nchw_to_nhwc", "ssr_nhwc_to_nchw",
     "ssr_fill", "ssr_bilinear2x_fwd", "ssr_bilinear2x_bwd", "ssr_nearest2x_bwd", "ssr_spectral_norm",
-    "ssr_spectral_norm_bwd", "ssr_usm_sharp", "ssr_l1_loss", "ssr_ssim_loss", "ssr_bce_logits_loss", "ssr_adam_step", "ssr_axpby_f32",
+    "ssr_spectral_norm_bwd", "ssr_usm_sharp", "ssr_l1_loss", "ssr_ssim_loss", "ssr_bce_logits_loss", "ssr_pixel_loss", "ssr_gan_loss", "ssr_adam_step", "ssr_axpby_f32",
     "ssr_quantize_u8", "ssr_metric_shift_sums", "ssr_metric_ssim_sums", "ssr_split_bf16", "ssr_split_bf16_multi", "ssr_channel_affine", "ssr_relu_maxpool2_fwd", "ssr_relu_maxpool2_bwd",
     "ssr_gram_splits", "ssr_gram_fwd", "ssr_gram_l1", "ssr_gram_bwd",
     "ssr_nonfinite_scan", "ssr_adam_step_guarded", "ssr_quantize_u8_checked",
@@ -188,6 +190,8 @@ def lib() -> C.CDLL:
     l.ssr_ssim_loss.argtypes = [View, View, View, i32, i32, i32, i32, i32, f32, i32, vp, vp]
     l.ssr_usm_sharp.argtypes = [vp, vp, i32, i32, i32, f32, f32, f32, vp]
     l.ssr_bce_logits_loss.argtypes = [View, View, i32, i64, f32, f32, vp, vp, vp]
+    l.ssr_pixel_loss.argtypes = [View, View, View, i32, i64, i32, i32, f32, f32, vp, vp]
+    l.ssr_gan_loss.argtypes = [View, View, i32, i64, i32, i32, i32, f32, f32, vp, vp, vp]
     l.ssr_adam_step.argtypes = [C.POINTER(AdamArgs), vp]
     l.ssr_axpby_f32.argtypes = [f32, vp, f32, vp, i64, vp]
     l.ssr_quantize_u8.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]

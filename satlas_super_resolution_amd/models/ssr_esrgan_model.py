@@ -8,7 +8,7 @@
 
 Same registry name and the same `opt` dictionary (YAML) keys.  Instead of autograd over ~41k ATen ops per
 step, optimize_parameters() replays the fused HIP-graph step of train_step.ESRGANTrainStep.
-Scope: L1 + vanilla-GAN (+ VGG19 perceptual: feature and Gram-style terms; + SSIM) losses, USM-sharpened ground truth,
+Scope: BasicSR's pixel (L1 / MSE / Charbonnier) and GAN (vanilla / lsgan / wgan / wgan_softplus / hinge) losses (+ VGG19 perceptual: feature and Gram-style terms; + SSIM) losses, USM-sharpened ground truth,
 `feed_disc_lr` and `old_hr` discriminator inputs.  Anything this path does not implement raises NotImplementedError naming the
 option (clip / ldl losses, other optimizers or schedulers, weight decay) — nothing is silently ignored."""
 from __future__ import annotations
@@ -77,28 +77,57 @@ def step_config_from_opt(opt: dict) -> StepConfig:
 
 
 def train_config_from_opt(opt: dict) -> StepConfig:
-    """step_config_from_opt plus `train.ssim_opt` (SSIMLoss: ssr/losses/basic_loss.py:50-60, built at ssr_esrgan_model.py:62-65): what
-    SSRESRGANModel configures its step from.
+    """step_config_from_opt plus `train.ssim_opt` (SSIMLoss: ssr/losses/basic_loss.py:50-60, built at ssr_esrgan_model.py:62-65) and
+    BasicSR's other pixel and GAN losses (`pixel_opt.type`: MSELoss, CharbonnierLoss; `gan_opt.gan_type`: lsgan, wgan, wgan_softplus,
+    hinge - basicsr/losses/basic_loss.py, gan_loss.py): what SSRESRGANModel configures its step from.
 
-    Why two functions: step_config_from_opt's refusal of `ssim_opt` is pinned by tests/test_host_boundary.py, so it stays as it is; this
-    one validates the block, hands a copy of `opt` without it to step_config_from_opt and sets StepConfig.ssim on the result.  Folding
-    the two into one goes with a change of that test.
+    Why two functions: step_config_from_opt's refusals of `ssim_opt`, of `wgan` and of `MSELoss` are pinned by
+    tests/test_host_boundary.py, so it stays as it is; this one validates those settings, hands step_config_from_opt a copy of `opt`
+    without the block / with the two types set back to L1Loss and vanilla, and sets StepConfig.ssim / .pixel_type / .pixel_eps /
+    .gan_type on the result.  Folding the two into one goes with a change of that test.
 
-    The block holds `type: SSIMLoss` and optionally `loss_weight` (default 1.0, as SSIMLoss.__init__); the window (5 x 5) is fixed in
-    the reference's forward.  Any other type or key raises NotImplementedError naming it."""
+    ssim_opt holds `type: SSIMLoss` and optionally `loss_weight` (default 1.0, as SSIMLoss.__init__); the window (5 x 5) is fixed in
+    the reference's forward.  pixel_opt holds `type`, `loss_weight`, `reduction: mean` and, for CharbonnierLoss, `eps` (default 1e-12) -
+    the constructors' arguments.  Any other type or key raises NotImplementedError naming it."""
     train_opt = opt.get("train", {}) or {}
+    rest_train = dict(train_opt)
+    ssim = None
     so = train_opt.get("ssim_opt")
-    if not so:
-        return step_config_from_opt(opt)
-    if so.get("type") != "SSIMLoss":
-        raise NotImplementedError(f"train.ssim_opt.type={so.get('type')!r}: only SSIMLoss")
-    for k in so:
-        if k not in ("type", "loss_weight"):
-            raise NotImplementedError(f"train.ssim_opt.{k}: SSIMLoss takes loss_weight only")
+    if so:
+        if so.get("type") != "SSIMLoss":
+            raise NotImplementedError(f"train.ssim_opt.type={so.get('type')!r}: only SSIMLoss")
+        for k in so:
+            if k not in ("type", "loss_weight"):
+                raise NotImplementedError(f"train.ssim_opt.{k}: SSIMLoss takes loss_weight only")
+        del rest_train["ssim_opt"]
+        ssim = {"loss_weight": float(so.get("loss_weight", 1.0))}
+    pixel_type, pixel_eps = "L1Loss", 1e-12
+    pix = train_opt.get("pixel_opt")
+    if pix:
+        pixel_type = pix.get("type", "L1Loss")
+        if pixel_type not in ("L1Loss",) + tuple(hip.PIXEL_KINDS):
+            raise NotImplementedError(f"train.pixel_opt.type={pixel_type!r}: only L1Loss, MSELoss, CharbonnierLoss")
+        takes = ("type", "loss_weight", "reduction") + (("eps",) if pixel_type == "CharbonnierLoss" else ())
+        for k in pix:
+            if k not in takes:
+                raise NotImplementedError(f"train.pixel_opt.{k}: {pixel_type} takes {', '.join(takes[1:])}")
+        if pix.get("reduction", "mean") != "mean":
+            raise NotImplementedError(f"train.pixel_opt.reduction={pix.get('reduction')!r}: only 'mean'")
+        pixel_eps = float(pix.get("eps", 1e-12))
+        if not pixel_eps >= 0.0:
+            raise NotImplementedError(f"train.pixel_opt.eps={pix.get('eps')!r}: must be >= 0")
+        rest_train["pixel_opt"] = {k: ("L1Loss" if k == "type" else v) for k, v in pix.items() if k != "eps"}
+    gan_type = "vanilla"
+    gan = train_opt.get("gan_opt")
+    if gan:
+        gan_type = gan.get("gan_type", "vanilla")
+        if gan_type not in ("vanilla",) + tuple(hip.GAN_TYPES):
+            raise NotImplementedError(f"train.gan_opt.gan_type={gan_type!r}: only vanilla, lsgan, wgan, wgan_softplus, hinge")
+        rest_train["gan_opt"] = dict(gan, gan_type="vanilla")
     rest = dict(opt)
-    rest["train"] = {k: v for k, v in train_opt.items() if k != "ssim_opt"}
+    rest["train"] = rest_train
     cfg = step_config_from_opt(rest)
-    cfg.ssim = {"loss_weight": float(so.get("loss_weight", 1.0))}
+    cfg.ssim, cfg.pixel_type, cfg.pixel_eps, cfg.gan_type = ssim, pixel_type, pixel_eps, gan_type
     return cfg
 
 

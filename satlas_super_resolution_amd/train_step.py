@@ -40,6 +40,9 @@ class StepConfig:
     ssim: Optional[Dict] = None         # train.ssim_opt (SSIMLoss, :163-166; ssimloss_esrgan_s2naip_urban.yml): {"loss_weight": w}
     real_label: float = 1.0
     fake_label: float = 0.0
+    gan_type: str = "vanilla"      # gan_opt.gan_type: vanilla | lsgan | wgan | wgan_softplus | hinge (basicsr GANLoss; hip.GAN_TYPES)
+    pixel_type: str = "L1Loss"     # pixel_opt.type: L1Loss | MSELoss | CharbonnierLoss (basicsr basic_loss.py; hip.PIXEL_KINDS)
+    pixel_eps: float = 1e-12       # pixel_opt.eps of CharbonnierLoss
     deterministic: bool = False    # fixed-order reductions only: two runs give bit-identical parameters (engine.deterministic; SSR_DETERMINISTIC=1)
 
 
@@ -254,13 +257,22 @@ class ESRGANTrainStep:
         """fp32 arena <- 0 by the library's own fill kernel: no ATen launch inside the (captured) step"""
         hip.check(hip.lib().ssr_fill(t.data_ptr(), t.numel(), hip.F32, 0.0, hip.stream_ptr()), "ssr_fill")
 
-    def _bce(self, target, weight, loss_idx, mean_idx, with_grad=True, plan=None):
+    def _bce(self, target_is_real, weight, loss_idx, mean_idx, with_grad=True, plan=None, is_disc=True):
+        """cri_gan(D's logits, target_is_real, is_disc) of cfg.gan_type: vanilla is ssr_bce_logits_loss against the label, every other
+        type ssr_gan_loss (csrc/losses.hip).  `weight`: 1 for is_disc, gan_opt.loss_weight otherwise (GANLoss.forward)."""
+        cfg = self.cfg
         d = plan or self.d_plan
         lp, ls = self.losses.data_ptr(), 4 * self.loss_stride
-        hip.check(hip.lib().ssr_bce_logits_loss(view(d.logits), view(d.d_logits) if with_grad else hip.NULL_VIEW,
-                                                self.loss_dt, self.B * self.H * self.W, target, weight, lp + ls * loss_idx,
-                                                (lp + ls * mean_idx) if mean_idx is not None else None,
-                                                hip.stream_ptr()), "ssr_bce_logits_loss")
+        target = cfg.real_label if target_is_real else cfg.fake_label
+        x, g = view(d.logits), view(d.d_logits) if with_grad else hip.NULL_VIEW
+        loss_ptr, mean_ptr = lp + ls * loss_idx, (lp + ls * mean_idx) if mean_idx is not None else None
+        if cfg.gan_type == "vanilla":
+            hip.check(hip.lib().ssr_bce_logits_loss(x, g, self.loss_dt, self.B * self.H * self.W, target, weight, loss_ptr, mean_ptr,
+                                                    hip.stream_ptr()), "ssr_bce_logits_loss")
+        else:
+            hip.check(hip.lib().ssr_gan_loss(x, g, self.loss_dt, self.B * self.H * self.W, hip.GAN_TYPES[cfg.gan_type],
+                                             int(target_is_real), int(is_disc), target, weight, loss_ptr, mean_ptr,
+                                             hip.stream_ptr()), "ssr_gan_loss")
 
     def _d_forward(self, x_buf):
         self.d_store.spectral_norm(power_iter=True)   # train-mode hook: one power iteration per forward
@@ -273,9 +285,14 @@ class ESRGANTrainStep:
         self._zero(self.losses)
         self.g_store.pack()
         self.g_plan.fwd.run()                                              # :140
-        hip.check(hip.lib().ssr_l1_loss(view(self.fake_in), view(self.l1_tgt), view(self.grad_l1), self.loss_dt,
-                                        self.B * self.H * self.W, self.cout, cfg.l1_weight, self.losses.data_ptr(),
-                                        hip.stream_ptr()), "ssr_l1_loss")   # :147-150
+        if cfg.pixel_type == "L1Loss":
+            hip.check(hip.lib().ssr_l1_loss(view(self.fake_in), view(self.l1_tgt), view(self.grad_l1), self.loss_dt,
+                                            self.B * self.H * self.W, self.cout, cfg.l1_weight, self.losses.data_ptr(),
+                                            hip.stream_ptr()), "ssr_l1_loss")   # :147-150
+        else:                                                              # MSELoss / CharbonnierLoss: same slot, same gradient buffer
+            hip.check(hip.lib().ssr_pixel_loss(view(self.fake_in), view(self.l1_tgt), view(self.grad_l1), self.loss_dt,
+                                               self.B * self.H * self.W, self.cout, hip.PIXEL_KINDS[cfg.pixel_type], cfg.pixel_eps,
+                                               cfg.l1_weight, self.losses.data_ptr(), hip.stream_ptr()), "ssr_pixel_loss")
         if cfg.ssim:                                                       # :163-166; its image gradient joins the L1 gradient buffer
             hip.check(hip.lib().ssr_ssim_loss(view(self.fake_in), view(self.percep_tgt), view(self.grad_l1), self.loss_dt, self.B,
                                               self.H, self.W, self.cout, float(cfg.ssim.get("loss_weight", 1.0)), 1,
@@ -285,7 +302,7 @@ class ESRGANTrainStep:
             self.p_plan.fwd.run()
             self.p_plan.bwd.run()
         self._d_forward(self.fake_in)                                      # :181
-        self._bce(cfg.real_label, cfg.gan_weight, 1, None)                 # :182 (is_disc=False)
+        self._bce(True, cfg.gan_weight, 1, None, is_disc=False)            # :182
         self.d_plan.backward_plan(self.fake_in, param_grads=False, input_grad=True,
                                   in_residual=self.grad_l1).run()          # :192, D frozen (:136-137)
         if run_bwd:
@@ -302,11 +319,11 @@ class ESRGANTrainStep:
         self._zero(self.d_store.grad)                                      # optimizer_d.zero_grad() :215
         self._zero(self.d_store.grad_sn)
         self._d_forward(self.real_in)                                      # :217
-        self._bce(cfg.real_label, 1.0, 2, 3)                               # :218-220
+        self._bce(True, 1.0, 2, 3)                                         # :218-220
         self.d_plan.backward_plan(self.real_in, param_grads=True, input_grad=False).run()   # :221
         self.d_store.spectral_norm_backward()
         self._d_forward(self.fake_in)                                      # :224 (output.detach())
-        self._bce(cfg.fake_label, 1.0, 4, 5)                               # :225-226
+        self._bce(False, 1.0, 4, 5)                                        # :225-226
         self.d_plan.backward_plan(self.fake_in, param_grads=True, input_grad=False).run()   # :227
         self.d_store.spectral_norm_backward()
 
