@@ -51,6 +51,17 @@
 //
 // Here a chunk row of the scene starts at any byte (W * 3 may be odd) and a mosaic row is only 4-byte aligned: rows are read as the
 // aligned words that lie inside them plus single bytes at the two ends, the mosaic is stored in aligned 4-byte units.
+//
+// The kernels behind the fifteen entry points:
+//
+//   scene_zero_scan_kernel, scene_gather_kernel<T, V>, scene_scatter_u8_kernel<T>      the grid path's own, aligned 16-byte accesses
+//   scene_zero_scan_at_kernel, scene_frame_keys_kernel, scene_rank_frames_kernel, scene_apply_nodata_kernel      one entry point each
+//   scene_gather_at_kernel<T, V, BANDS, TF>   ssr_scene_gather_at <.., false, false>, ssr_scene_gather_bands <.., true, false>,
+//                                             ssr_scene_gather_tf <.., true, true> (host side: gather_at, pick_pack)
+//   scene_support_add_kernel                  ssr_scene_support_add; it and the gather above stage a chunk's rows with stage_rows
+//   scene_blend_add_kernel<T, TF>             ssr_scene_blend_add <T, false>, ssr_scene_blend_add_tf <T, true> (host side: blend_add)
+//   scene_blend_finish_kernel                 ssr_scene_blend_finish with the scale 65535, ssr_scene_blend_finish_scaled (host side:
+//                                             blend_finish)
 #include "common.h"
 
 namespace {
@@ -210,6 +221,13 @@ __device__ __forceinline__ uint32_t row_word(const uint8_t* a, int i) {
     return v;
 }
 
+// staging of a row through LDS: word i of the row at `a` to *word and, once per row, the row's byte offset inside its words to *shift
+template <int LEN>
+__device__ __forceinline__ void stage_word(const uint8_t* a, int i, uint32_t* word, uint32_t* shift) {
+    *word = row_word<LEN>(a, i);
+    if (i == 0) *shift = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
+}
+
 __device__ __forceinline__ bool origin_ok(int y0, int x0, int H, int W) { return y0 >= 0 && x0 >= 0 && y0 <= H - CH && x0 <= W - CH; }
 
 // one wave per (chunk, frame): CH rows x ROWW words, 0xff outside the rows
@@ -249,9 +267,7 @@ __global__ __launch_bounds__(256) void scene_frame_keys_kernel(const uint8_t* __
     const uint8_t* base = scene + (((long)t * H + y0) * W + x0) * 3;
     for (int e = threadIdx.x; e < KEYW; e += 256) {
         const int row = e / ROWW, i = e - row * ROWW;
-        const uint8_t* a = base + (long)row * W * 3;
-        win[e] = row_word<ROWB>(a, i);
-        if (i == 0) shift[row] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
+        stage_word<ROWB>(base + (long)row * W * 3, i, win + e, shift + row);
     }
     __syncthreads();
     const uint8_t* bytes = reinterpret_cast<const uint8_t*>(win);
@@ -292,150 +308,74 @@ __global__ __launch_bounds__(64) void scene_rank_frames_kernel(const uint32_t* _
     }
 }
 
-// scene_gather_kernel at an arbitrary origin: the rows go through LDS as their covering aligned words (n x ROWW words, and the n
-// byte offsets of the rows inside them), the conversion and the stores are the same
-template <typename T, int V>
-__global__ __launch_bounds__(256) void scene_gather_at_kernel(const uint8_t* __restrict__ scene, int T_, int H, int W,
-                                                              const int32_t* __restrict__ origins,
-                                                              const int32_t* __restrict__ frame_ids, int n, ssr_view dst) {
-    extern __shared__ uint32_t roww[];                            // [n][ROWW] words, then [n] byte offsets
-    uint32_t* shift = roww + n * ROWW;
-    const int b = blockIdx.x / CH, y = blockIdx.x - b * CH;
-    const int y0 = origins[2 * b], x0 = origins[2 * b + 1];
-    if (!origin_ok(y0, x0, H, W)) return;                         // block-uniform
-    for (int k = 0; k < n; ++k) {                                 // block-uniform: before any barrier
-        const int f = frame_ids[b * n + k];
-        if (f < 0 || f >= T_) return;
-    }
-    for (int e = threadIdx.x; e < n * ROWW; e += 256) {
-        const int k = e / ROWW, i = e - k * ROWW;
-        const long t = frame_ids[b * n + k];
-        const uint8_t* a = scene + ((t * H + y0 + y) * W + x0) * 3;
-        roww[e] = row_word<ROWB>(a, i);
-        if (i == 0) shift[k] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
-    }
-    __syncthreads();
-    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(roww);
-    const int C = 3 * n, groups = C / V;
-    T* __restrict__ d = reinterpret_cast<T*>(dst.p);
-    const long pix0 = ((long)b * CH + y) * CH;
-    for (int e = threadIdx.x; e < CH * groups; e += 256) {
-        const int x = e / groups, c0 = (e - x * groups) * V;
-        Pack<T, V> o;
-#pragma unroll
-        for (int u = 0; u < V; ++u) {
-            const int c = c0 + u, k = c / 3;
-            // x * (1.0f / 255.0f), then the storage type's rounding: scene_gather_kernel's arithmetic
-            o.v[u] = from_f32<T>((float)bytes[k * (4 * ROWW) + shift[k] + x * 3 + (c - 3 * k)] * INV255);
-        }
-        *reinterpret_cast<Pack<T, V>*>(d + (pix0 + x) * dst.cs + dst.coff + c0) = o;
-    }
-}
-
-// scene_gather_at_kernel for 3 + K channels per chosen frame: the n TCI rows (n x ROWW words) and the n K rows of the band planes
-// (n K x BANDW words, slot-major) go through LDS as their covering aligned words, behind them the byte offsets of the rows inside
-// their words.  Channel s (3 + K) + c of a pixel is the TCI sample c < 3 of slot s, else band c - 3.  The row strides (25 and 9
-// words) are odd: the byte reads of consecutive channels, which step from one row to the next, spread over the banks.
+// Row y of the window of chunk b, once per chosen frame, through LDS: the n TCI rows as their covering aligned words (n x ROWW) and,
+// with BANDS, the n K rows of the band planes (n K x BANDW words, slot-major, r = s K + band), behind them the byte offsets of the
+// rows inside their words - the dynamic LDS is [n][ROWW], [n K][BANDW], [n], [n K].  The row strides (25 and 9 words) are odd: the
+// byte reads of consecutive channels, which step from one row to the next, spread over the banks.  False, with nothing read or
+// staged, for a chunk that is a no-op: its origin outside the scene or a frame id outside 0 .. T - 1 - block-uniform, before the
+// barrier.  Every kernel that reads a chunk's rows at an origin stages them here, so what scene_support_add_kernel counts is what
+// the gather fed to the generator.
 constexpr int BANDW = CH / 4 + 1;  // aligned 4-byte words that cover a row of a band plane starting at any byte
 
-template <typename T, int V>
-__global__ __launch_bounds__(256) void scene_gather_bands_kernel(const uint8_t* __restrict__ tci, const uint8_t* __restrict__ bands,
-                                                                 int K, int T_, int H, int W, const int32_t* __restrict__ origins,
-                                                                 const int32_t* __restrict__ frame_ids, int n, ssr_view dst) {
-    extern __shared__ uint32_t roww[];                            // [n][ROWW], [n K][BANDW] words, then [n] and [n K] byte offsets
+struct StagedRows {
+    const uint8_t *bytes, *bbytes;     // the TCI and the band words, read as bytes
+    const uint32_t *shift, *bshift;    // per TCI row s and band row r: row byte j is byte shift + j of the row's words
+    int y0, x0;                        // the window's origin
+};
+
+template <bool BANDS>
+__device__ __forceinline__ bool stage_rows(const uint8_t* tci, const uint8_t* bands, int K, int T_, int H, int W,
+                                           const int32_t* origins, const int32_t* frame_ids, int n, int b, int y, StagedRows& st) {
+    extern __shared__ uint32_t roww[];
+    if (!BANDS) K = 0;                                            // (no band rows: the layout is [n][ROWW], [n])
     uint32_t* bandw = roww + n * ROWW;
     uint32_t* shift = bandw + n * K * BANDW;
     uint32_t* bshift = shift + n;
-    const int b = blockIdx.x / CH, y = blockIdx.x - b * CH;
     const int y0 = origins[2 * b], x0 = origins[2 * b + 1];
-    if (!origin_ok(y0, x0, H, W)) return;                         // block-uniform
-    for (int s = 0; s < n; ++s) {                                 // block-uniform: before any barrier
+    if (!origin_ok(y0, x0, H, W)) return false;                   // block-uniform
+    for (int s = 0; s < n; ++s) {                                 // block-uniform: before the barrier
         const int f = frame_ids[b * n + s];
-        if (f < 0 || f >= T_) return;
+        if (f < 0 || f >= T_) return false;
     }
     const int tci_words = n * ROWW;
     for (int e = threadIdx.x; e < tci_words + n * K * BANDW; e += 256) {
-        if (e < tci_words) {
+        if (!BANDS || e < tci_words) {
             const int s = e / ROWW, i = e - s * ROWW;
             const long t = frame_ids[b * n + s];
-            const uint8_t* a = tci + ((t * H + y0 + y) * W + x0) * 3;
-            roww[e] = row_word<ROWB>(a, i);
-            if (i == 0) shift[s] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
-        } else {
-            const int r = (e - tci_words) / BANDW, i = (e - tci_words) - r * BANDW;      // r = s K + band
+            stage_word<ROWB>(tci + ((t * H + y0 + y) * W + x0) * 3, i, roww + e, shift + s);
+        } else if constexpr (BANDS) {                             // (K >= 1 here)
+            const int r = (e - tci_words) / BANDW, i = (e - tci_words) - r * BANDW;
             const int s = r / K, kb = r - s * K;
             const long t = frame_ids[b * n + s];
-            const uint8_t* a = bands + (((long)kb * T_ + t) * H + y0 + y) * W + x0;
-            bandw[r * BANDW + i] = row_word<CH>(a, i);
-            if (i == 0) bshift[r] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
+            stage_word<CH>(bands + (((long)kb * T_ + t) * H + y0 + y) * W + x0, i, bandw + r * BANDW + i, bshift + r);
         }
     }
     __syncthreads();
-    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(roww);
-    const uint8_t* bbytes = reinterpret_cast<const uint8_t*>(bandw);
-    const int F = 3 + K, C = n * F, groups = C / V;
-    T* __restrict__ d = reinterpret_cast<T*>(dst.p);
-    const long pix0 = ((long)b * CH + y) * CH;
-    for (int e = threadIdx.x; e < CH * groups; e += 256) {
-        const int x = e / groups, c0 = (e - x * groups) * V;
-        int s = c0 / F, c = c0 - s * F;                           // slot and channel inside the slot of the pack's first element
-        Pack<T, V> o;
-#pragma unroll
-        for (int u = 0; u < V; ++u) {
-            const int r = s * K + c - 3;
-            const uint8_t v = c < 3 ? bytes[s * (4 * ROWW) + shift[s] + x * 3 + c] : bbytes[r * (4 * BANDW) + bshift[r] + x];
-            // x * (1.0f / 255.0f), then the storage type's rounding: scene_gather_kernel's arithmetic
-            o.v[u] = from_f32<T>((float)v * INV255);
-            if (++c == F) { c = 0; ++s; }
-        }
-        *reinterpret_cast<Pack<T, V>*>(d + (pix0 + x) * dst.cs + dst.coff + c0) = o;
-    }
+    st = {reinterpret_cast<const uint8_t*>(roww), reinterpret_cast<const uint8_t*>(bandw), shift, bshift, y0, x0};
+    return true;
 }
 
-// scene_gather_bands_kernel (K >= 1) and scene_gather_at_kernel (K == 0, bands not read) under a transform of the square: the
-// block of SOURCE row y stages the rows exactly as they do - whole rows as aligned words - and converts with the same arithmetic;
-// only the place of a pixel in dst turns.  Source pixel (y, x) goes to (yd, xd) = (tf & 2 ? 31 - y : y, tf & 1 ? 31 - x : x), swapped
-// if tf & 4: without a transpose the block writes a row of dst (backwards under a column flip), under a transpose a column of it,
-// one pixel's channel vector (or V of its channels) per store.  tf outside 0 .. 7: a no-op, block-uniform like the other two.
-template <typename T, int V>
-__global__ __launch_bounds__(256) void scene_gather_tf_kernel(const uint8_t* __restrict__ tci, const uint8_t* __restrict__ bands,
+// scene_gather_kernel at the origins (ssr_scene_gather_at: BANDS and TF off), with 3 + K channels per chosen frame (ssr_scene_gather_bands:
+// BANDS; channel s (3 + K) + c of a pixel is the TCI sample c < 3 of slot s, else band c - 3) and under a transform of the square
+// (ssr_scene_gather_tf: BANDS and TF, K >= 0 at run time).  One block per (batch item, SOURCE row y): the rows staged by stage_rows,
+// the conversion and the stores of scene_gather_kernel; only the place of a pixel in dst turns under TF.  Source pixel (y, x) goes
+// to (yd, xd) = (tf & 2 ? 31 - y : y, tf & 1 ? 31 - x : x), swapped if tf & 4: without a transpose the block writes a row of dst
+// (backwards under a column flip), under a transpose a column of it, one pixel's channel vector (or V of its channels) per store.
+// tf outside 0 .. 7: a no-op, block-uniform like stage_rows' two.
+template <typename T, int V, bool BANDS, bool TF>
+__global__ __launch_bounds__(256) void scene_gather_at_kernel(const uint8_t* __restrict__ tci, const uint8_t* __restrict__ bands,
                                                               int K, int T_, int H, int W, const int32_t* __restrict__ origins,
                                                               const int32_t* __restrict__ frame_ids, const int32_t* __restrict__ tf,
                                                               int n, ssr_view dst) {
-    extern __shared__ uint32_t roww[];                            // [n][ROWW], [n K][BANDW] words, then [n] and [n K] byte offsets
-    uint32_t* bandw = roww + n * ROWW;
-    uint32_t* shift = bandw + n * K * BANDW;
-    uint32_t* bshift = shift + n;
     const int b = blockIdx.x / CH, y = blockIdx.x - b * CH;
-    const int y0 = origins[2 * b], x0 = origins[2 * b + 1];
-    if (!origin_ok(y0, x0, H, W)) return;                         // block-uniform
-    const int t8 = tf[b];
-    if (t8 < 0 || t8 > 7) return;                                 // block-uniform
-    for (int s = 0; s < n; ++s) {                                 // block-uniform: before any barrier
-        const int f = frame_ids[b * n + s];
-        if (f < 0 || f >= T_) return;
+    int t8 = 0;
+    if constexpr (TF) {
+        t8 = tf[b];
+        if (t8 < 0 || t8 > 7) return;                             // block-uniform
     }
-    const int tci_words = n * ROWW;
-    for (int e = threadIdx.x; e < tci_words + n * K * BANDW; e += 256) {
-        if (e < tci_words) {
-            const int s = e / ROWW, i = e - s * ROWW;
-            const long t = frame_ids[b * n + s];
-            const uint8_t* a = tci + ((t * H + y0 + y) * W + x0) * 3;
-            roww[e] = row_word<ROWB>(a, i);
-            if (i == 0) shift[s] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
-        } else {                                                  // (K >= 1 here)
-            const int r = (e - tci_words) / BANDW, i = (e - tci_words) - r * BANDW;      // r = s K + band
-            const int s = r / K, kb = r - s * K;
-            const long t = frame_ids[b * n + s];
-            const uint8_t* a = bands + (((long)kb * T_ + t) * H + y0 + y) * W + x0;
-            bandw[r * BANDW + i] = row_word<CH>(a, i);
-            if (i == 0) bshift[r] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
-        }
-    }
-    __syncthreads();
-    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(roww);
-    const uint8_t* bbytes = reinterpret_cast<const uint8_t*>(bandw);
-    const int F = 3 + K, C = n * F, groups = C / V;
+    StagedRows st;
+    if (!stage_rows<BANDS>(tci, bands, K, T_, H, W, origins, frame_ids, n, b, y, st)) return;
+    const int F = BANDS ? 3 + K : 3, C = n * F, groups = C / V;
     T* __restrict__ d = reinterpret_cast<T*>(dst.p);
     const int yd = (t8 & 2) ? CH - 1 - y : y;
     for (int e = threadIdx.x; e < CH * groups; e += 256) {
@@ -447,8 +387,9 @@ __global__ __launch_bounds__(256) void scene_gather_tf_kernel(const uint8_t* __r
 #pragma unroll
         for (int u = 0; u < V; ++u) {
             const int r = s * K + c - 3;
-            const uint8_t v = c < 3 ? bytes[s * (4 * ROWW) + shift[s] + x * 3 + c] : bbytes[r * (4 * BANDW) + bshift[r] + x];
-            // x * (1.0f / 255.0f), then the storage type's rounding: scene_gather_kernel's arithmetic
+            const uint8_t v = !BANDS || c < 3 ? st.bytes[s * (4 * ROWW) + st.shift[s] + x * 3 + c]
+                                              : st.bbytes[r * (4 * BANDW) + st.bshift[r] + x];
+            // `.float() / 255` of frames_to_input: x * (1.0f / 255.0f), then the storage type's rounding (scene_gather_kernel's arithmetic)
             o.v[u] = from_f32<T>((float)v * INV255);
             if (++c == F) { c = 0; ++s; }
         }
@@ -458,9 +399,15 @@ __global__ __launch_bounds__(256) void scene_gather_tf_kernel(const uint8_t* __r
 
 // one wave per (batch item, row of its 128 x 128 output): the row's 128 C fixed-point samples, weighted, are added to 128 C
 // consecutive words of the accumulator - wave-instructions of 256 contiguous bytes.  Integer adds: the sums do not depend on the
-// order in which overlapping chunks arrive.
-template <typename T>
-__global__ __launch_bounds__(256) void scene_blend_add_kernel(ssr_view src, const int32_t* __restrict__ origins, int B, int C,
+// order in which overlapping chunks arrive.  16 fractional bits of the sample.
+// TF (ssr_scene_blend_add_tf), for a (chunk, transform) row of the self-ensemble: the wave that owns accumulator row r of item b adds
+// the INVERSE transform of the item's output, so it reads src at the preimage of (r, x) - row rs = tf & 2 ? 127 - r : r and column
+// xs = tf & 1 ? 127 - x : x, swapped if tf & 4 (then a column of src: a strided read) - and adds into the same 128 C consecutive
+// words: the reads turn, the atomics stay contiguous.  The window is indexed by the place in the accumulator.  13 fractional bits:
+// 8 rows per chunk x 125 x 125 (the largest weight sums) x 8191 < 2^32.  tf outside 0 .. 7: a no-op, wave-uniform.
+template <typename T, bool TF>
+__global__ __launch_bounds__(256) void scene_blend_add_kernel(ssr_view src, const int32_t* __restrict__ origins,
+                                                              const int32_t* __restrict__ tf, int B, int C,
                                                               const int32_t* __restrict__ window, uint32_t* __restrict__ acc,
                                                               int Ho, int Wo, int32_t* __restrict__ nonfinite) {
     const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -469,56 +416,26 @@ __global__ __launch_bounds__(256) void scene_blend_add_kernel(ssr_view src, cons
     const int b = (int)(item / SR), r = (int)(item - (long)b * SR);
     const int y0 = origins[2 * b], x0 = origins[2 * b + 1];
     if (!origin_ok(y0, x0, Ho / 4, Wo / 4)) return;               // wave-uniform
-    const T* __restrict__ s = reinterpret_cast<const T*>(src.p) + ((long)b * SR + r) * SR * src.cs + src.coff;
-    uint32_t* __restrict__ a = acc + (((long)4 * y0 + r) * Wo + (long)4 * x0) * C;
-    const uint32_t wr = (uint32_t)window[r];
-    int bad = 0;
-    for (int e = lane; e < SR * C; e += 64) {
-        const int x = e / C, c = e - x * C;
-        const float v = to_f32(s[(long)x * src.cs + c]);
-        bad += (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
-        // clamp(0, 1) (NaN -> 0 via fmaxf) * 65535 in fp32, truncated: 16 fractional bits of the sample
-        const uint32_t f = (uint32_t)(fminf(fmaxf(v, 0.f), 1.f) * 65535.0f);
-        atomicAdd(a + e, f * wr * (uint32_t)window[x]);
+    int t8 = 0;
+    if constexpr (TF) {
+        t8 = tf[b];
+        if (t8 < 0 || t8 > 7) return;                             // wave-uniform
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bad += __shfl_down(bad, o, 64);
-    if (lane == 0 && bad) atomicAdd(nonfinite, bad);
-}
-
-// scene_blend_add_kernel for a (chunk, transform) row of the self-ensemble: the wave that owns accumulator row r of item b adds the
-// INVERSE transform of the item's output, so it reads src at the preimage of (r, x) - row rs = tf & 2 ? 127 - r : r and column
-// xs = tf & 1 ? 127 - x : x, swapped if tf & 4 (then a column of src: a strided read) - and adds into the same 128 C consecutive
-// words: the reads turn, the atomics stay contiguous.  The window is indexed by the place in the accumulator.  13 fractional bits:
-// 8 rows per chunk x 125 x 125 (the largest weight sums) x 8191 < 2^32.  tf outside 0 .. 7: a no-op, wave-uniform.
-constexpr float ENS_ONE = 8191.0f;
-
-template <typename T>
-__global__ __launch_bounds__(256) void scene_blend_add_tf_kernel(ssr_view src, const int32_t* __restrict__ origins,
-                                                                 const int32_t* __restrict__ tf, int B, int C,
-                                                                 const int32_t* __restrict__ window, uint32_t* __restrict__ acc,
-                                                                 int Ho, int Wo, int32_t* __restrict__ nonfinite) {
-    const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (item >= (long)B * SR) return;                             // wave-uniform
-    const int lane = threadIdx.x & 63;
-    const int b = (int)(item / SR), r = (int)(item - (long)b * SR);
-    const int y0 = origins[2 * b], x0 = origins[2 * b + 1];
-    if (!origin_ok(y0, x0, Ho / 4, Wo / 4)) return;               // wave-uniform
-    const int t8 = tf[b];
-    if (t8 < 0 || t8 > 7) return;                                 // wave-uniform
-    const T* __restrict__ s = reinterpret_cast<const T*>(src.p) + (long)b * SR * SR * src.cs + src.coff;
+    // the item's output under TF, which turns the reads; without it row r of the output
+    const T* __restrict__ s = reinterpret_cast<const T*>(src.p) + ((long)b * SR + (TF ? 0 : r)) * SR * src.cs + src.coff;
     uint32_t* __restrict__ a = acc + (((long)4 * y0 + r) * Wo + (long)4 * x0) * C;
     const uint32_t wr = (uint32_t)window[r];
     const int rs = (t8 & 2) ? SR - 1 - r : r;
+    constexpr float ONE = TF ? 8191.0f : 65535.0f;                // 1.0 in the accumulator's fixed point
     int bad = 0;
     for (int e = lane; e < SR * C; e += 64) {
         const int x = e / C, c = e - x * C;
         const int xs = (t8 & 1) ? SR - 1 - x : x;
-        const int pix = (t8 & 4) ? xs * SR + rs : rs * SR + xs;  // below 128 * 128
+        const int pix = !TF ? x : (t8 & 4) ? xs * SR + rs : rs * SR + xs;      // below 128 * 128
         const float v = to_f32(s[(long)pix * src.cs + c]);
         bad += (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
-        // clamp(0, 1) (NaN -> 0 via fmaxf) * 8191 in fp32, truncated: 13 fractional bits of the sample
-        const uint32_t f = (uint32_t)(fminf(fmaxf(v, 0.f), 1.f) * ENS_ONE);
+        // clamp(0, 1) (NaN -> 0 via fmaxf) * ONE in fp32, truncated
+        const uint32_t f = (uint32_t)(fminf(fmaxf(v, 0.f), 1.f) * ONE);
         atomicAdd(a + e, f * wr * (uint32_t)window[x]);
     }
 #pragma unroll
@@ -527,10 +444,10 @@ __global__ __launch_bounds__(256) void scene_blend_add_tf_kernel(ssr_view src, c
 }
 
 // one thread per aligned 4-byte unit of the mosaic (a row is Wo C bytes, Wo a multiple of 4); `scale` is the fixed point's one
-// times the rows per chunk: the constant 65535 in scene_blend_finish_kernel, an argument in scene_blend_finish_scaled_kernel
-__device__ __forceinline__ void blend_finish_unit(const uint32_t* __restrict__ acc, const int32_t* __restrict__ Sy,
-                                                  const int32_t* __restrict__ Sx, int C, uint32_t* __restrict__ mosaic, int Ho, int Wo,
-                                                  uint32_t scale) {
+// times the rows per chunk: 65535 behind scene_blend_add_kernel<T, false>, 8 * 8191 behind the self-ensemble's
+__global__ __launch_bounds__(256) void scene_blend_finish_kernel(const uint32_t* __restrict__ acc, const int32_t* __restrict__ Sy,
+                                                                 const int32_t* __restrict__ Sx, int C, uint32_t scale,
+                                                                 uint32_t* __restrict__ mosaic, int Ho, int Wo) {
     const long roww_ = (long)Wo * C / 4;
     const long q = (long)blockIdx.x * 256 + threadIdx.x;
     if (q >= roww_ * Ho) return;
@@ -549,52 +466,24 @@ __device__ __forceinline__ void blend_finish_unit(const uint32_t* __restrict__ a
     mosaic[q] = out;
 }
 
-__global__ __launch_bounds__(256) void scene_blend_finish_kernel(const uint32_t* __restrict__ acc, const int32_t* __restrict__ Sy,
-                                                                 const int32_t* __restrict__ Sx, int C, uint32_t* __restrict__ mosaic,
-                                                                 int Ho, int Wo) {
-    blend_finish_unit(acc, Sy, Sx, C, mosaic, Ho, Wo, 65535u);
-}
-
-__global__ __launch_bounds__(256) void scene_blend_finish_scaled_kernel(const uint32_t* __restrict__ acc, const int32_t* __restrict__ Sy,
-                                                                        const int32_t* __restrict__ Sx, int C, uint32_t scale,
-                                                                        uint32_t* __restrict__ mosaic, int Ho, int Wo) {
-    blend_finish_unit(acc, Sy, Sx, C, mosaic, Ho, Wo, scale);
-}
-
-// one block per (chunk, row of its window): the n chosen frames' rows go through LDS as their covering aligned words, exactly as
-// scene_gather_at_kernel stages them (the same no-op tests, so support counts what the gather fed to the generator), then one
-// thread per pixel of the row counts the slots whose three samples are all non-zero and adds the count to the pixel's word of
-// support.  Integer atomics: overlapping chunks may arrive in any order.
+// one block per (chunk, row of its window): the n chosen frames' rows staged by stage_rows, as the gather beside it stages them,
+// then one thread per pixel of the row counts the slots whose three samples are all non-zero and adds the count to the pixel's word
+// of support.  Integer atomics: overlapping chunks may arrive in any order.
 __global__ __launch_bounds__(256) void scene_support_add_kernel(const uint8_t* __restrict__ scene, int T_, int H, int W,
                                                                 const int32_t* __restrict__ origins,
                                                                 const int32_t* __restrict__ frame_ids, int n,
                                                                 int32_t* __restrict__ support) {
-    extern __shared__ uint32_t roww[];                            // [n][ROWW] words, then [n] byte offsets
-    uint32_t* shift = roww + n * ROWW;
     const int b = blockIdx.x / CH, y = blockIdx.x - b * CH;
-    const int y0 = origins[2 * b], x0 = origins[2 * b + 1];
-    if (!origin_ok(y0, x0, H, W)) return;                         // block-uniform
-    for (int k = 0; k < n; ++k) {                                 // block-uniform: before any barrier
-        const int f = frame_ids[b * n + k];
-        if (f < 0 || f >= T_) return;
-    }
-    for (int e = threadIdx.x; e < n * ROWW; e += 256) {
-        const int k = e / ROWW, i = e - k * ROWW;
-        const long t = frame_ids[b * n + k];
-        const uint8_t* a = scene + ((t * H + y0 + y) * W + x0) * 3;
-        roww[e] = row_word<ROWB>(a, i);
-        if (i == 0) shift[k] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3);
-    }
-    __syncthreads();
+    StagedRows st;
+    if (!stage_rows<false>(scene, nullptr, 0, T_, H, W, origins, frame_ids, n, b, y, st)) return;
     if (threadIdx.x >= CH) return;                                // (after the only barrier)
-    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(roww);
     const int x = threadIdx.x;
     int count = 0;
     for (int k = 0; k < n; ++k) {
-        const uint8_t* px = bytes + k * (4 * ROWW) + shift[k] + 3 * x;
+        const uint8_t* px = st.bytes + k * (4 * ROWW) + st.shift[k] + 3 * x;
         count += (px[0] != 0) & (px[1] != 0) & (px[2] != 0);
     }
-    if (count) atomicAdd(support + (long)(y0 + y) * W + x0 + x, count);
+    if (count) atomicAdd(support + (long)(st.y0 + y) * W + st.x0 + x, count);
 }
 
 // one thread per aligned 4-byte unit of the mosaic (a row is Wo C bytes, Wo a multiple of 4), as scene_blend_finish_kernel stores:
@@ -627,9 +516,62 @@ __global__ __launch_bounds__(256) void scene_apply_nodata_kernel(uint32_t* __res
 
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
-}  // namespace
-
 #define ST(s) reinterpret_cast<hipStream_t>(s)
+
+// the gathers' launch switch: storage type x vector width V (16 bytes of channels per store when a pixel's C channels are a
+// multiple of that, else single elements); the four instantiations of a gather have one signature
+template <typename Kernel>
+Kernel pick_pack(int dtype, long C, Kernel f32x4, Kernel f32x1, Kernel bf16x8, Kernel bf16x1) {
+    return dtype == SSR_F32 ? (C % 4 == 0 ? f32x4 : f32x1) : (C % 8 == 0 ? bf16x8 : bf16x1);
+}
+
+// ssr_scene_gather_at (K = 0), ssr_scene_gather_bands and ssr_scene_gather_tf behind their own checks of bands, K and tf: the
+// checks the three share, in their order, and the launch
+template <bool BANDS, bool TF>
+int gather_at(const uint8_t* tci, const uint8_t* bands, int K, int T, int H, int W, const int32_t* origins, const int32_t* frame_ids,
+              const int32_t* tf, int B, int n, ssr_view dst, int dtype, void* stream) {
+    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
+    if (!tci || !origins || !frame_ids || !dst.p || T <= 0 || H <= 0 || W <= 0 || B <= 0 || n <= 0) return SSR_EINVAL;
+    const long C = (long)n * (3 + (long)K);
+    if (!aligned16(dst.p) || dst.cs % 8 || dst.coff % 8 || dst.coff < 0 || dst.coff + C > dst.cs || B > (1 << 20)) return SSR_EINVAL;
+    const size_t lds = ((size_t)n * (ROWW + 1) + (size_t)n * K * (BANDW + 1)) * 4;
+    if (H < CH || W < CH || n > T || n > 512 || lds > 65536 || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
+    const auto kernel = pick_pack(dtype, C, scene_gather_at_kernel<float, 4, BANDS, TF>, scene_gather_at_kernel<float, 1, BANDS, TF>,
+                                  scene_gather_at_kernel<__bf16, 8, BANDS, TF>, scene_gather_at_kernel<__bf16, 1, BANDS, TF>);
+    hipLaunchKernelGGL(kernel, dim3(B * CH), dim3(256), lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, tf, n, dst);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+// ssr_scene_blend_add and, behind its own check of tf, ssr_scene_blend_add_tf
+template <bool TF>
+int blend_add(ssr_view src, int dtype, const int32_t* origins, const int32_t* tf, int B, int C, const int32_t* window, uint32_t* acc,
+              int Ho, int Wo, int32_t* nonfinite, void* stream) {
+    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
+    if (!src.p || !origins || !window || !acc || !nonfinite || B <= 0 || C <= 0 || Ho <= 0 || Wo <= 0) return SSR_EINVAL;
+    if (!aligned4(src.p) || !aligned16(acc) || src.coff < 0 || src.coff + C > src.cs || C > MAX_C || B > (1 << 20)) return SSR_EINVAL;
+    if (Ho % 4 || Wo % 4 || Ho < SR || Wo < SR || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
+    const auto kernel = dtype == SSR_F32 ? scene_blend_add_kernel<float, TF> : scene_blend_add_kernel<__bf16, TF>;
+    hipLaunchKernelGGL(kernel, dim3(B * (SR / 4)), dim3(256), 0, ST(stream), src, origins, tf, B, C, window, acc, Ho, Wo, nonfinite);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+// ssr_scene_blend_finish (scale 65535) and, behind its own check of scale, ssr_scene_blend_finish_scaled
+int blend_finish(const uint32_t* acc, const int32_t* Sy, const int32_t* Sx, int C, uint32_t scale, uint8_t* mosaic, int Ho, int Wo,
+                 void* stream) {
+    if (!acc || !Sy || !Sx || !mosaic || C <= 0 || Ho <= 0 || Wo <= 0) return SSR_EINVAL;
+    if (!aligned16(acc) || !aligned4(mosaic) || C > MAX_C) return SSR_EINVAL;
+    if (Ho % 4 || Wo % 4 || Ho < SR || Wo < SR) return SSR_EUNSUP;
+    const long units = (long)Ho * Wo * C / 4, blocks = (units + 255) / 256;
+    if (blocks > 0x7fffffffl) return SSR_EUNSUP;
+    hipLaunchKernelGGL(scene_blend_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), acc, Sy, Sx, C, scale,
+                       reinterpret_cast<uint32_t*>(mosaic), Ho, Wo);
+    SSR_LAUNCH_CHECK();
+    return SSR_OK;
+}
+
+}  // namespace
 
 extern "C" int ssr_scene_zero_scan(const uint8_t* scene, int32_t T, int32_t H, int32_t W, uint8_t* has_zero, void* stream) {
     if (!scene || !has_zero || T <= 0 || H <= 0 || W <= 0 || !aligned16(scene)) return SSR_EINVAL;
@@ -649,20 +591,9 @@ extern "C" int ssr_scene_gather(const uint8_t* scene, int32_t T, int32_t H, int3
         B > (1 << 20))
         return SSR_EINVAL;
     if (H % CH || W % CH || n > T || n > 512 || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
-    const dim3 grid(B * CH), block(256);
-    const size_t lds = (size_t)n * CH * 3;
-    const int C = 3 * n;
-    if (dtype == SSR_F32) {
-        if (C % 4 == 0)
-            hipLaunchKernelGGL((scene_gather_kernel<float, 4>), grid, block, lds, ST(stream), scene, T, H, W, chunk_ids, frame_ids, n, dst);
-        else
-            hipLaunchKernelGGL((scene_gather_kernel<float, 1>), grid, block, lds, ST(stream), scene, T, H, W, chunk_ids, frame_ids, n, dst);
-    } else {
-        if (C % 8 == 0)
-            hipLaunchKernelGGL((scene_gather_kernel<__bf16, 8>), grid, block, lds, ST(stream), scene, T, H, W, chunk_ids, frame_ids, n, dst);
-        else
-            hipLaunchKernelGGL((scene_gather_kernel<__bf16, 1>), grid, block, lds, ST(stream), scene, T, H, W, chunk_ids, frame_ids, n, dst);
-    }
+    const auto kernel = pick_pack(dtype, 3 * n, scene_gather_kernel<float, 4>, scene_gather_kernel<float, 1>,
+                                  scene_gather_kernel<__bf16, 8>, scene_gather_kernel<__bf16, 1>);
+    hipLaunchKernelGGL(kernel, dim3(B * CH), dim3(256), (size_t)n * CH * 3, ST(stream), scene, T, H, W, chunk_ids, frame_ids, n, dst);
     SSR_LAUNCH_CHECK();
     return SSR_OK;
 }
@@ -699,52 +630,14 @@ extern "C" int ssr_scene_zero_scan_at(const uint8_t* scene, int32_t T, int32_t H
 
 extern "C" int ssr_scene_gather_at(const uint8_t* scene, int32_t T, int32_t H, int32_t W, const int32_t* origins,
                                    const int32_t* frame_ids, int32_t B, int32_t n, ssr_view dst, int32_t dtype, void* stream) {
-    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
-    if (!scene || !origins || !frame_ids || !dst.p || T <= 0 || H <= 0 || W <= 0 || B <= 0 || n <= 0) return SSR_EINVAL;
-    if (!aligned16(dst.p) || dst.cs % 8 || dst.coff % 8 || dst.coff < 0 || dst.coff + 3 * n > dst.cs || B > (1 << 20))
-        return SSR_EINVAL;
-    if (H < CH || W < CH || n > T || n > 512 || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
-    const dim3 grid(B * CH), block(256);
-    const size_t lds = (size_t)n * (ROWW + 1) * 4;
-    const int C = 3 * n;
-    if (dtype == SSR_F32) {
-        if (C % 4 == 0)
-            hipLaunchKernelGGL((scene_gather_at_kernel<float, 4>), grid, block, lds, ST(stream), scene, T, H, W, origins, frame_ids, n, dst);
-        else
-            hipLaunchKernelGGL((scene_gather_at_kernel<float, 1>), grid, block, lds, ST(stream), scene, T, H, W, origins, frame_ids, n, dst);
-    } else {
-        if (C % 8 == 0)
-            hipLaunchKernelGGL((scene_gather_at_kernel<__bf16, 8>), grid, block, lds, ST(stream), scene, T, H, W, origins, frame_ids, n, dst);
-        else
-            hipLaunchKernelGGL((scene_gather_at_kernel<__bf16, 1>), grid, block, lds, ST(stream), scene, T, H, W, origins, frame_ids, n, dst);
-    }
-    SSR_LAUNCH_CHECK();
-    return SSR_OK;
+    return gather_at<false, false>(scene, nullptr, 0, T, H, W, origins, frame_ids, nullptr, B, n, dst, dtype, stream);
 }
 
 extern "C" int ssr_scene_gather_bands(const uint8_t* tci, const uint8_t* bands, int32_t K, int32_t T, int32_t H, int32_t W,
                                       const int32_t* origins, const int32_t* frame_ids, int32_t B, int32_t n, ssr_view dst,
                                       int32_t dtype, void* stream) {
-    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
-    if (!tci || !bands || !origins || !frame_ids || !dst.p || K <= 0 || T <= 0 || H <= 0 || W <= 0 || B <= 0 || n <= 0) return SSR_EINVAL;
-    const long C = (long)n * (3 + (long)K);
-    if (!aligned16(dst.p) || dst.cs % 8 || dst.coff % 8 || dst.coff < 0 || dst.coff + C > dst.cs || B > (1 << 20)) return SSR_EINVAL;
-    const size_t lds = ((size_t)n * (ROWW + 1) + (size_t)n * K * (BANDW + 1)) * 4;
-    if (H < CH || W < CH || n > T || n > 512 || lds > 65536 || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
-    const dim3 grid(B * CH), block(256);
-    if (dtype == SSR_F32) {
-        if (C % 4 == 0)
-            hipLaunchKernelGGL((scene_gather_bands_kernel<float, 4>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, n, dst);
-        else
-            hipLaunchKernelGGL((scene_gather_bands_kernel<float, 1>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, n, dst);
-    } else {
-        if (C % 8 == 0)
-            hipLaunchKernelGGL((scene_gather_bands_kernel<__bf16, 8>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, n, dst);
-        else
-            hipLaunchKernelGGL((scene_gather_bands_kernel<__bf16, 1>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, n, dst);
-    }
-    SSR_LAUNCH_CHECK();
-    return SSR_OK;
+    if (!bands || K <= 0) return SSR_EINVAL;
+    return gather_at<true, false>(tci, bands, K, T, H, W, origins, frame_ids, nullptr, B, n, dst, dtype, stream);
 }
 
 extern "C" int ssr_scene_frame_keys(const uint8_t* scene, int32_t T, int32_t H, int32_t W, const int32_t* origins, int32_t n_chunks,
@@ -769,84 +662,31 @@ extern "C" int ssr_scene_rank_frames(const uint32_t* keys, int32_t n_chunks, int
 
 extern "C" int ssr_scene_blend_add(ssr_view src, int32_t dtype, const int32_t* origins, int32_t B, int32_t C, const int32_t* window,
                                    uint32_t* acc, int32_t Ho, int32_t Wo, int32_t* nonfinite, void* stream) {
-    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
-    if (!src.p || !origins || !window || !acc || !nonfinite || B <= 0 || C <= 0 || Ho <= 0 || Wo <= 0) return SSR_EINVAL;
-    if (!aligned4(src.p) || !aligned16(acc) || src.coff < 0 || src.coff + C > src.cs || C > MAX_C || B > (1 << 20)) return SSR_EINVAL;
-    if (Ho % 4 || Wo % 4 || Ho < SR || Wo < SR || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
-    const dim3 grid(B * (SR / 4)), block(256);
-    if (dtype == SSR_F32)
-        hipLaunchKernelGGL(scene_blend_add_kernel<float>, grid, block, 0, ST(stream), src, origins, B, C, window, acc, Ho, Wo, nonfinite);
-    else
-        hipLaunchKernelGGL(scene_blend_add_kernel<__bf16>, grid, block, 0, ST(stream), src, origins, B, C, window, acc, Ho, Wo, nonfinite);
-    SSR_LAUNCH_CHECK();
-    return SSR_OK;
+    return blend_add<false>(src, dtype, origins, nullptr, B, C, window, acc, Ho, Wo, nonfinite, stream);
 }
 
 extern "C" int ssr_scene_blend_finish(const uint32_t* acc, const int32_t* Sy, const int32_t* Sx, int32_t C, uint8_t* mosaic, int32_t Ho,
                                       int32_t Wo, void* stream) {
-    if (!acc || !Sy || !Sx || !mosaic || C <= 0 || Ho <= 0 || Wo <= 0) return SSR_EINVAL;
-    if (!aligned16(acc) || !aligned4(mosaic) || C > MAX_C) return SSR_EINVAL;
-    if (Ho % 4 || Wo % 4 || Ho < SR || Wo < SR) return SSR_EUNSUP;
-    const long units = (long)Ho * Wo * C / 4, blocks = (units + 255) / 256;
-    if (blocks > 0x7fffffffl) return SSR_EUNSUP;
-    hipLaunchKernelGGL(scene_blend_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), acc, Sy, Sx, C,
-                       reinterpret_cast<uint32_t*>(mosaic), Ho, Wo);
-    SSR_LAUNCH_CHECK();
-    return SSR_OK;
+    return blend_finish(acc, Sy, Sx, C, 65535u, mosaic, Ho, Wo, stream);
 }
 
 extern "C" int ssr_scene_gather_tf(const uint8_t* tci, const uint8_t* bands, int32_t K, int32_t T, int32_t H, int32_t W,
                                    const int32_t* origins, const int32_t* frame_ids, const int32_t* tf, int32_t B, int32_t n,
                                    ssr_view dst, int32_t dtype, void* stream) {
-    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
-    if (!tci || !origins || !frame_ids || !tf || !dst.p || K < 0 || (K > 0 && !bands) || T <= 0 || H <= 0 || W <= 0 || B <= 0 || n <= 0)
-        return SSR_EINVAL;
-    const long C = (long)n * (3 + (long)K);
-    if (!aligned16(dst.p) || dst.cs % 8 || dst.coff % 8 || dst.coff < 0 || dst.coff + C > dst.cs || B > (1 << 20)) return SSR_EINVAL;
-    const size_t lds = ((size_t)n * (ROWW + 1) + (size_t)n * K * (BANDW + 1)) * 4;
-    if (H < CH || W < CH || n > T || n > 512 || lds > 65536 || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
-    const dim3 grid(B * CH), block(256);
-    if (dtype == SSR_F32) {
-        if (C % 4 == 0)
-            hipLaunchKernelGGL((scene_gather_tf_kernel<float, 4>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, tf, n, dst);
-        else
-            hipLaunchKernelGGL((scene_gather_tf_kernel<float, 1>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, tf, n, dst);
-    } else {
-        if (C % 8 == 0)
-            hipLaunchKernelGGL((scene_gather_tf_kernel<__bf16, 8>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, tf, n, dst);
-        else
-            hipLaunchKernelGGL((scene_gather_tf_kernel<__bf16, 1>), grid, block, lds, ST(stream), tci, bands, K, T, H, W, origins, frame_ids, tf, n, dst);
-    }
-    SSR_LAUNCH_CHECK();
-    return SSR_OK;
+    if (!tf || K < 0 || (K > 0 && !bands)) return SSR_EINVAL;
+    return gather_at<true, true>(tci, bands, K, T, H, W, origins, frame_ids, tf, B, n, dst, dtype, stream);
 }
 
 extern "C" int ssr_scene_blend_add_tf(ssr_view src, int32_t dtype, const int32_t* origins, const int32_t* tf, int32_t B, int32_t C,
                                       const int32_t* window, uint32_t* acc, int32_t Ho, int32_t Wo, int32_t* nonfinite, void* stream) {
-    if (dtype == SSR_F32X3) dtype = SSR_F32;   // fp32 storage: only the matrix-core kernels differ
-    if (!src.p || !origins || !tf || !window || !acc || !nonfinite || B <= 0 || C <= 0 || Ho <= 0 || Wo <= 0) return SSR_EINVAL;
-    if (!aligned4(src.p) || !aligned16(acc) || src.coff < 0 || src.coff + C > src.cs || C > MAX_C || B > (1 << 20)) return SSR_EINVAL;
-    if (Ho % 4 || Wo % 4 || Ho < SR || Wo < SR || (dtype != SSR_F32 && dtype != SSR_BF16)) return SSR_EUNSUP;
-    const dim3 grid(B * (SR / 4)), block(256);
-    if (dtype == SSR_F32)
-        hipLaunchKernelGGL(scene_blend_add_tf_kernel<float>, grid, block, 0, ST(stream), src, origins, tf, B, C, window, acc, Ho, Wo, nonfinite);
-    else
-        hipLaunchKernelGGL(scene_blend_add_tf_kernel<__bf16>, grid, block, 0, ST(stream), src, origins, tf, B, C, window, acc, Ho, Wo, nonfinite);
-    SSR_LAUNCH_CHECK();
-    return SSR_OK;
+    if (!tf) return SSR_EINVAL;
+    return blend_add<true>(src, dtype, origins, tf, B, C, window, acc, Ho, Wo, nonfinite, stream);
 }
 
 extern "C" int ssr_scene_blend_finish_scaled(const uint32_t* acc, const int32_t* Sy, const int32_t* Sx, int32_t C, int32_t scale,
                                              uint8_t* mosaic, int32_t Ho, int32_t Wo, void* stream) {
-    if (!acc || !Sy || !Sx || !mosaic || C <= 0 || scale < 1 || Ho <= 0 || Wo <= 0) return SSR_EINVAL;
-    if (!aligned16(acc) || !aligned4(mosaic) || C > MAX_C) return SSR_EINVAL;
-    if (Ho % 4 || Wo % 4 || Ho < SR || Wo < SR) return SSR_EUNSUP;
-    const long units = (long)Ho * Wo * C / 4, blocks = (units + 255) / 256;
-    if (blocks > 0x7fffffffl) return SSR_EUNSUP;
-    hipLaunchKernelGGL(scene_blend_finish_scaled_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), acc, Sy, Sx, C,
-                       (uint32_t)scale, reinterpret_cast<uint32_t*>(mosaic), Ho, Wo);
-    SSR_LAUNCH_CHECK();
-    return SSR_OK;
+    if (scale < 1) return SSR_EINVAL;
+    return blend_finish(acc, Sy, Sx, C, (uint32_t)scale, mosaic, Ho, Wo, stream);
 }
 
 extern "C" int ssr_scene_support_add(const uint8_t* scene, int32_t T, int32_t H, int32_t W, const int32_t* origins,

@@ -383,12 +383,49 @@ def _ptr(t: torch.Tensor) -> int:
     return t.data_ptr()
 
 
+def _check_scene(scene: torch.Tensor, any_size: bool = False) -> Tuple[int, int, int]:
+    """a scene (the TCI) on the device, uint8 [T, H, W, 3] of a size the path takes -> (T, H, W)"""
+    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3, \
+        (scene.dtype, scene.shape)
+    T, H, W = scene.shape[:3]
+    check_scene_size(H, W, any_size)
+    return T, H, W
+
+
+def _check_origins(origins: torch.Tensor):
+    assert origins.is_cuda and origins.dtype == torch.int32 and origins.is_contiguous() and origins.dim() == 2 and origins.shape[1] == 2, \
+        (origins.dtype, origins.shape)
+
+
+def _check_frame_ids(frame_ids: torch.Tensor, origins: torch.Tensor) -> Tuple[int, int]:
+    """the chosen frames of the chunks at the origins, int32 [B, n] on the device -> (B, n)"""
+    _check_origins(origins)
+    assert frame_ids.is_cuda and frame_ids.dtype == torch.int32 and frame_ids.is_contiguous() and frame_ids.dim() == 2 \
+        and frame_ids.shape[0] == origins.shape[0], (frame_ids.dtype, frame_ids.shape, origins.shape)
+    return tuple(frame_ids.shape)
+
+
+def _check_bands_tensor(bands: Optional[torch.Tensor], T: int, H: int, W: int) -> int:
+    """the extra bands of a scene on the device, uint8 [K, T, H, W], or None -> K"""
+    if bands is None:
+        return 0
+    assert bands.is_cuda and bands.dtype == torch.uint8 and bands.is_contiguous() and bands.dim() == 4 and bands.shape[0] >= 1 \
+        and tuple(bands.shape[1:]) == (T, H, W), (bands.dtype, bands.shape, (T, H, W))
+    return bands.shape[0]
+
+
+def _check_tf(tf: torch.Tensor, B: int):
+    assert tf.is_cuda and tf.dtype == torch.int32 and tf.is_contiguous() and tuple(tf.shape) == (B,), (tf.dtype, tf.shape)
+
+
+def _check_acc(acc: torch.Tensor, C: int):
+    assert acc.is_cuda and acc.dtype == torch.int32 and acc.is_contiguous() and acc.dim() == 3 and acc.shape[2] == C, (acc.dtype, acc.shape)
+
+
 def scene_zero_scan(scene: torch.Tensor) -> torch.Tensor:
     """uint8 [T, H, W, 3] on the device -> uint8 [gh*gw, T] on the device: 1 where frame t of the chunk holds a zero sample"""
     from . import hip
-    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
-    T, H, W = scene.shape[:3]
-    check_scene_size(H, W)
+    T, H, W = _check_scene(scene)
     out = torch.empty((H // CHUNK) * (W // CHUNK), T, dtype=torch.uint8, device=scene.device)
     hip.check(hip.lib().ssr_scene_zero_scan(_ptr(scene), T, H, W, _ptr(out), hip.stream_ptr()), "ssr_scene_zero_scan")
     return out
@@ -398,11 +435,9 @@ def scene_gather(scene: torch.Tensor, chunk_ids: torch.Tensor, frame_ids: torch.
     """the chosen frames (int32 [B, n], device) of the chunks chunk_ids (int32 [B], device) -> dst, an NHWC generator input
     [B, 32, 32, >= 3n] of fp32 or bf16 storage (GeneratorPlan.xin); pad channels are left as they are"""
     from . import hip
-    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
     assert chunk_ids.dtype == torch.int32 and frame_ids.dtype == torch.int32 and chunk_ids.is_cuda and frame_ids.is_cuda
     assert chunk_ids.is_contiguous() and frame_ids.is_contiguous()
-    T, H, W = scene.shape[:3]
-    check_scene_size(H, W)
+    T, H, W = _check_scene(scene)
     B, n = frame_ids.shape
     assert chunk_ids.shape == (B,) and tuple(dst.shape[:3]) == (B, CHUNK, CHUNK) and dst.shape[3] >= 3 * n, (chunk_ids.shape, dst.shape)
     if dtype is None:
@@ -427,19 +462,12 @@ def scene_scatter_u8(src: torch.Tensor, chunk_ids: torch.Tensor, C: int, mosaic:
                                              mosaic.shape[1], _ptr(nonfinite), hip.stream_ptr()), "ssr_scene_scatter_u8")
 
 
-def _check_origins(origins: torch.Tensor):
-    assert origins.is_cuda and origins.dtype == torch.int32 and origins.is_contiguous() and origins.dim() == 2 and origins.shape[1] == 2, \
-        (origins.dtype, origins.shape)
-
-
 def scene_zero_scan_at(scene: torch.Tensor, origins: torch.Tensor) -> torch.Tensor:
     """uint8 [T, H, W, 3] (H, W >= 32) and int32 [chunks, 2] origins (y0, x0), both on the device -> uint8 [chunks, T] on the device:
     1 where frame t of the 32 x 32 window at the origin holds a zero sample; rows of origins outside the scene are not written"""
     from . import hip
-    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
+    T, H, W = _check_scene(scene, True)
     _check_origins(origins)
-    T, H, W = scene.shape[:3]
-    check_scene_size(H, W, True)
     out = torch.zeros(origins.shape[0], T, dtype=torch.uint8, device=scene.device)
     hip.check(hip.lib().ssr_scene_zero_scan_at(_ptr(scene), T, H, W, _ptr(origins), origins.shape[0], _ptr(out), hip.stream_ptr()),
               "ssr_scene_zero_scan_at")
@@ -452,10 +480,8 @@ def scene_frame_keys(scene: torch.Tensor, origins: torch.Tensor, out: Optional[t
     sample, s its pixels that are (255, 255, 255) (`rank_scene_frames`); rows of origins outside the scene are not written (they
     keep what `out` held, zeros without one)"""
     from . import hip
-    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
+    T, H, W = _check_scene(scene, True)
     _check_origins(origins)
-    T, H, W = scene.shape[:3]
-    check_scene_size(H, W, True)
     if out is None:
         out = torch.zeros(origins.shape[0], T, dtype=torch.int32, device=scene.device)
     assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (origins.shape[0], T), (out.dtype, out.shape)
@@ -479,41 +505,49 @@ def scene_rank_frames(keys: torch.Tensor, n: int) -> torch.Tensor:
     return out
 
 
-def scene_gather_at(scene: torch.Tensor, origins: torch.Tensor, frame_ids: torch.Tensor, dst: torch.Tensor, dtype: Optional[int] = None):
-    """`scene_gather` for chunks at the origins (int32 [B, 2], device) of a scene of any size >= 32 x 32"""
+def _gather_at(scene: torch.Tensor, bands: Optional[torch.Tensor], origins: torch.Tensor, frame_ids: torch.Tensor,
+               tf: Optional[torch.Tensor], dst: torch.Tensor, dtype: Optional[int]):
+    """the body of the three gathers at origins: `ssr_scene_gather_tf` with transform ids, else `ssr_scene_gather_bands` with bands,
+    else `ssr_scene_gather_at`"""
     from . import hip
-    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
-    _check_origins(origins)
-    assert frame_ids.dtype == torch.int32 and frame_ids.is_cuda and frame_ids.is_contiguous()
-    T, H, W = scene.shape[:3]
-    check_scene_size(H, W, True)
-    B, n = frame_ids.shape
-    assert origins.shape[0] == B and tuple(dst.shape[:3]) == (B, CHUNK, CHUNK) and dst.shape[3] >= 3 * n, (origins.shape, dst.shape)
+    T, H, W = _check_scene(scene, True)
+    K = _check_bands_tensor(bands, T, H, W)
+    B, n = _check_frame_ids(frame_ids, origins)
+    assert tuple(dst.shape[:3]) == (B, CHUNK, CHUNK) and dst.shape[3] >= (3 + K) * n, (origins.shape, dst.shape)
     if dtype is None:
         dtype = hip.dtype_code(dst.dtype)
-    hip.check(hip.lib().ssr_scene_gather_at(_ptr(scene), T, H, W, _ptr(origins), _ptr(frame_ids), B, n, hip.view(dst), dtype,
-                                            hip.stream_ptr()), "ssr_scene_gather_at")
+    tail = (B, n, hip.view(dst), dtype, hip.stream_ptr())
+    if tf is not None:
+        _check_tf(tf, B)
+        hip.check(hip.lib().ssr_scene_gather_tf(_ptr(scene), None if bands is None else _ptr(bands), K, T, H, W, _ptr(origins),
+                                                _ptr(frame_ids), _ptr(tf), *tail), "ssr_scene_gather_tf")
+    elif bands is not None:
+        hip.check(hip.lib().ssr_scene_gather_bands(_ptr(scene), _ptr(bands), K, T, H, W, _ptr(origins), _ptr(frame_ids), *tail),
+                  "ssr_scene_gather_bands")
+    else:
+        hip.check(hip.lib().ssr_scene_gather_at(_ptr(scene), T, H, W, _ptr(origins), _ptr(frame_ids), *tail), "ssr_scene_gather_at")
+
+
+def scene_gather_at(scene: torch.Tensor, origins: torch.Tensor, frame_ids: torch.Tensor, dst: torch.Tensor, dtype: Optional[int] = None):
+    """`scene_gather` for chunks at the origins (int32 [B, 2], device) of a scene of any size >= 32 x 32"""
+    _gather_at(scene, None, origins, frame_ids, None, dst, dtype)
 
 
 def scene_gather_bands(scene: torch.Tensor, bands: torch.Tensor, origins: torch.Tensor, frame_ids: torch.Tensor, dst: torch.Tensor,
                        dtype: Optional[int] = None):
     """`scene_gather_at` with the K extra bands (uint8 [K, T, H, W], device) behind the TCI of every chosen frame: 3 + K channels
     per frame, dst [B, 32, 32, >= n (3 + K)]"""
-    from . import hip
-    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
-    T, H, W = scene.shape[:3]
-    assert bands.is_cuda and bands.dtype == torch.uint8 and bands.is_contiguous() and bands.dim() == 4 and bands.shape[0] >= 1 \
-        and tuple(bands.shape[1:]) == (T, H, W), (bands.dtype, bands.shape, scene.shape)
-    _check_origins(origins)
-    assert frame_ids.dtype == torch.int32 and frame_ids.is_cuda and frame_ids.is_contiguous()
-    check_scene_size(H, W, True)
-    K = bands.shape[0]
-    B, n = frame_ids.shape
-    assert origins.shape[0] == B and tuple(dst.shape[:3]) == (B, CHUNK, CHUNK) and dst.shape[3] >= (3 + K) * n, (origins.shape, dst.shape)
-    if dtype is None:
-        dtype = hip.dtype_code(dst.dtype)
-    hip.check(hip.lib().ssr_scene_gather_bands(_ptr(scene), _ptr(bands), K, T, H, W, _ptr(origins), _ptr(frame_ids), B, n,
-                                               hip.view(dst), dtype, hip.stream_ptr()), "ssr_scene_gather_bands")
+    assert bands is not None
+    _gather_at(scene, bands, origins, frame_ids, None, dst, dtype)
+
+
+def scene_gather_tf(scene: torch.Tensor, bands: Optional[torch.Tensor], origins: torch.Tensor, frame_ids: torch.Tensor,
+                    tf: torch.Tensor, dst: torch.Tensor, dtype: Optional[int] = None):
+    """`ensemble_transform` on the device: row b of dst is the transform tf[b] (int32 [B], device) of the chunk `scene_gather_at`
+    (bands None) or `scene_gather_bands` writes for origins[b] and frame_ids[b] - with tf[b] == 0 their bytes.  A row whose tf lies
+    outside 0 .. 7 is left as it is, as a row they skip."""
+    assert tf is not None
+    _gather_at(scene, bands, origins, frame_ids, tf, dst, dtype)
 
 
 def scene_support_add(scene: torch.Tensor, origins: torch.Tensor, frame_ids: torch.Tensor, support: torch.Tensor):
@@ -522,13 +556,8 @@ def scene_support_add(scene: torch.Tensor, origins: torch.Tensor, frame_ids: tor
     has data (no zero sample) is ADDED to support (int32 [H, W], device; the caller zeroes it once per scene).  Chunks the gathers
     skip (origin outside the scene, a frame id outside 0 .. T - 1) add nothing."""
     from . import hip
-    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
-    _check_origins(origins)
-    assert frame_ids.dtype == torch.int32 and frame_ids.is_cuda and frame_ids.is_contiguous() and frame_ids.dim() == 2
-    T, H, W = scene.shape[:3]
-    check_scene_size(H, W, True)
-    B, n = frame_ids.shape
-    assert origins.shape[0] == B, (origins.shape, frame_ids.shape)
+    T, H, W = _check_scene(scene, True)
+    B, n = _check_frame_ids(frame_ids, origins)
     assert support.is_cuda and support.dtype == torch.int32 and support.is_contiguous() and tuple(support.shape) == (H, W), \
         (support.dtype, support.shape)
     hip.check(hip.lib().ssr_scene_support_add(_ptr(scene), T, H, W, _ptr(origins), _ptr(frame_ids), B, n, _ptr(support),
@@ -555,8 +584,24 @@ def scene_apply_nodata(mosaic: torch.Tensor, support: torch.Tensor, min_support:
               "ssr_scene_apply_nodata")
 
 
-def _check_acc(acc: torch.Tensor, C: int):
-    assert acc.is_cuda and acc.dtype == torch.int32 and acc.is_contiguous() and acc.dim() == 3 and acc.shape[2] == C, (acc.dtype, acc.shape)
+def _blend_add(src: torch.Tensor, origins: torch.Tensor, tf: Optional[torch.Tensor], C: int, window: torch.Tensor, acc: torch.Tensor,
+               nonfinite: torch.Tensor, dtype: Optional[int]):
+    """the body of the two blend-adds: `ssr_scene_blend_add_tf` with transform ids, else `ssr_scene_blend_add`"""
+    from . import hip
+    B = origins.shape[0]
+    _check_origins(origins)
+    _check_acc(acc, C)
+    assert tuple(src.shape[:3]) == (B, SR_CHUNK, SR_CHUNK) and src.shape[3] >= C, src.shape
+    assert window.is_cuda and window.dtype == torch.int32 and window.is_contiguous() and tuple(window.shape) == (SR_CHUNK,)
+    assert nonfinite.dtype == torch.int32 and nonfinite.is_cuda
+    if dtype is None:
+        dtype = hip.dtype_code(src.dtype)
+    tail = (B, C, _ptr(window), _ptr(acc), acc.shape[0], acc.shape[1], _ptr(nonfinite), hip.stream_ptr())
+    if tf is not None:
+        _check_tf(tf, B)
+        hip.check(hip.lib().ssr_scene_blend_add_tf(hip.view(src), dtype, _ptr(origins), _ptr(tf), *tail), "ssr_scene_blend_add_tf")
+    else:
+        hip.check(hip.lib().ssr_scene_blend_add(hip.view(src), dtype, _ptr(origins), *tail), "ssr_scene_blend_add")
 
 
 def scene_blend_add(src: torch.Tensor, origins: torch.Tensor, C: int, window: torch.Tensor, acc: torch.Tensor,
@@ -564,92 +609,42 @@ def scene_blend_add(src: torch.Tensor, origins: torch.Tensor, C: int, window: to
     """src, an NHWC generator output [B, 128, 128, >= C], in 16-bit fixed point times the window weights (int32 [128], device) is
     added to acc (int32 storage [Ho, Wo, C] on the device, read as uint32) at 4 x the origins; adds the number of non-finite
     samples to the int32 device counter"""
-    from . import hip
-    B = origins.shape[0]
-    _check_origins(origins)
-    _check_acc(acc, C)
-    assert tuple(src.shape[:3]) == (B, SR_CHUNK, SR_CHUNK) and src.shape[3] >= C, src.shape
-    assert window.is_cuda and window.dtype == torch.int32 and window.is_contiguous() and tuple(window.shape) == (SR_CHUNK,)
-    assert nonfinite.dtype == torch.int32 and nonfinite.is_cuda
-    if dtype is None:
-        dtype = hip.dtype_code(src.dtype)
-    hip.check(hip.lib().ssr_scene_blend_add(hip.view(src), dtype, _ptr(origins), B, C, _ptr(window), _ptr(acc), acc.shape[0],
-                                            acc.shape[1], _ptr(nonfinite), hip.stream_ptr()), "ssr_scene_blend_add")
-
-
-def scene_blend_finish(acc: torch.Tensor, Sy: torch.Tensor, Sx: torch.Tensor, mosaic: torch.Tensor):
-    """acc [Ho, Wo, C] over the weight sums Sy (int32 [Ho]) and Sx (int32 [Wo]) -> mosaic, uint8 [Ho, Wo, C], truncating"""
-    from . import hip
-    Ho, Wo, C = acc.shape
-    _check_acc(acc, C)
-    assert mosaic.is_cuda and mosaic.dtype == torch.uint8 and mosaic.is_contiguous() and tuple(mosaic.shape) == (Ho, Wo, C)
-    for S, L in ((Sy, Ho), (Sx, Wo)):
-        assert S.is_cuda and S.dtype == torch.int32 and S.is_contiguous() and tuple(S.shape) == (L,)
-    hip.check(hip.lib().ssr_scene_blend_finish(_ptr(acc), _ptr(Sy), _ptr(Sx), C, _ptr(mosaic), Ho, Wo, hip.stream_ptr()),
-              "ssr_scene_blend_finish")
-
-
-def _check_tf(tf: torch.Tensor, B: int):
-    assert tf.is_cuda and tf.dtype == torch.int32 and tf.is_contiguous() and tuple(tf.shape) == (B,), (tf.dtype, tf.shape)
-
-
-def scene_gather_tf(scene: torch.Tensor, bands: Optional[torch.Tensor], origins: torch.Tensor, frame_ids: torch.Tensor,
-                    tf: torch.Tensor, dst: torch.Tensor, dtype: Optional[int] = None):
-    """`ensemble_transform` on the device: row b of dst is the transform tf[b] (int32 [B], device) of the chunk `scene_gather_at`
-    (bands None) or `scene_gather_bands` writes for origins[b] and frame_ids[b] - with tf[b] == 0 their bytes.  A row whose tf lies
-    outside 0 .. 7 is left as it is, as a row they skip."""
-    from . import hip
-    assert scene.is_cuda and scene.dtype == torch.uint8 and scene.is_contiguous() and scene.dim() == 4 and scene.shape[3] == 3
-    T, H, W = scene.shape[:3]
-    K = 0
-    if bands is not None:
-        assert bands.is_cuda and bands.dtype == torch.uint8 and bands.is_contiguous() and bands.dim() == 4 and bands.shape[0] >= 1 \
-            and tuple(bands.shape[1:]) == (T, H, W), (bands.dtype, bands.shape, scene.shape)
-        K = bands.shape[0]
-    _check_origins(origins)
-    assert frame_ids.dtype == torch.int32 and frame_ids.is_cuda and frame_ids.is_contiguous()
-    check_scene_size(H, W, True)
-    B, n = frame_ids.shape
-    _check_tf(tf, B)
-    assert origins.shape[0] == B and tuple(dst.shape[:3]) == (B, CHUNK, CHUNK) and dst.shape[3] >= (3 + K) * n, (origins.shape, dst.shape)
-    if dtype is None:
-        dtype = hip.dtype_code(dst.dtype)
-    hip.check(hip.lib().ssr_scene_gather_tf(_ptr(scene), None if bands is None else _ptr(bands), K, T, H, W, _ptr(origins),
-                                            _ptr(frame_ids), _ptr(tf), B, n, hip.view(dst), dtype, hip.stream_ptr()),
-              "ssr_scene_gather_tf")
+    _blend_add(src, origins, None, C, window, acc, nonfinite, dtype)
 
 
 def scene_blend_add_tf(src: torch.Tensor, origins: torch.Tensor, tf: torch.Tensor, C: int, window: torch.Tensor, acc: torch.Tensor,
                        nonfinite: torch.Tensor, dtype: Optional[int] = None):
     """`scene_blend_add` of `ensemble_inverse(src[b], tf[b])` (tf int32 [B], device) in 13-bit fixed point (`ENSEMBLE_ONE`): the
     eight rows of a chunk add up in acc, which `scene_blend_finish_scaled` divides by 8 x 8191 x the weight sums"""
-    from . import hip
-    B = origins.shape[0]
-    _check_origins(origins)
-    _check_tf(tf, B)
-    _check_acc(acc, C)
-    assert tuple(src.shape[:3]) == (B, SR_CHUNK, SR_CHUNK) and src.shape[3] >= C, src.shape
-    assert window.is_cuda and window.dtype == torch.int32 and window.is_contiguous() and tuple(window.shape) == (SR_CHUNK,)
-    assert nonfinite.dtype == torch.int32 and nonfinite.is_cuda
-    if dtype is None:
-        dtype = hip.dtype_code(src.dtype)
-    hip.check(hip.lib().ssr_scene_blend_add_tf(hip.view(src), dtype, _ptr(origins), _ptr(tf), B, C, _ptr(window), _ptr(acc),
-                                               acc.shape[0], acc.shape[1], _ptr(nonfinite), hip.stream_ptr()), "ssr_scene_blend_add_tf")
+    assert tf is not None
+    _blend_add(src, origins, tf, C, window, acc, nonfinite, dtype)
 
 
-def scene_blend_finish_scaled(acc: torch.Tensor, Sy: torch.Tensor, Sx: torch.Tensor, mosaic: torch.Tensor, scale: int):
-    """`scene_blend_finish` with the denominator's scale given: mosaic = acc * 255 // (Sy Sx scale); ENSEMBLE * ENSEMBLE_ONE under
-    the self-ensemble"""
+def _blend_finish(acc: torch.Tensor, Sy: torch.Tensor, Sx: torch.Tensor, mosaic: torch.Tensor, scale: Optional[int]):
+    """the body of the two finishes: `ssr_scene_blend_finish_scaled` with a scale, else `ssr_scene_blend_finish`"""
     from . import hip
     Ho, Wo, C = acc.shape
     _check_acc(acc, C)
     assert mosaic.is_cuda and mosaic.dtype == torch.uint8 and mosaic.is_contiguous() and tuple(mosaic.shape) == (Ho, Wo, C)
     for S, L in ((Sy, Ho), (Sx, Wo)):
         assert S.is_cuda and S.dtype == torch.int32 and S.is_contiguous() and tuple(S.shape) == (L,)
-    scale = int(scale)
-    assert 1 <= scale < 1 << 31, scale
-    hip.check(hip.lib().ssr_scene_blend_finish_scaled(_ptr(acc), _ptr(Sy), _ptr(Sx), C, scale, _ptr(mosaic), Ho, Wo, hip.stream_ptr()),
-              "ssr_scene_blend_finish_scaled")
+    tail = (_ptr(mosaic), Ho, Wo, hip.stream_ptr())
+    if scale is not None:
+        assert 1 <= scale < 1 << 31, scale
+        hip.check(hip.lib().ssr_scene_blend_finish_scaled(_ptr(acc), _ptr(Sy), _ptr(Sx), C, scale, *tail), "ssr_scene_blend_finish_scaled")
+    else:
+        hip.check(hip.lib().ssr_scene_blend_finish(_ptr(acc), _ptr(Sy), _ptr(Sx), C, *tail), "ssr_scene_blend_finish")
+
+
+def scene_blend_finish(acc: torch.Tensor, Sy: torch.Tensor, Sx: torch.Tensor, mosaic: torch.Tensor):
+    """acc [Ho, Wo, C] over the weight sums Sy (int32 [Ho]) and Sx (int32 [Wo]) -> mosaic, uint8 [Ho, Wo, C], truncating"""
+    _blend_finish(acc, Sy, Sx, mosaic, None)
+
+
+def scene_blend_finish_scaled(acc: torch.Tensor, Sy: torch.Tensor, Sx: torch.Tensor, mosaic: torch.Tensor, scale: int):
+    """`scene_blend_finish` with the denominator's scale given: mosaic = acc * 255 // (Sy Sx scale); ENSEMBLE * ENSEMBLE_ONE under
+    the self-ensemble"""
+    _blend_finish(acc, Sy, Sx, mosaic, int(scale))
 
 
 class _Pending:
@@ -745,135 +740,89 @@ def _frames_T(frames) -> Optional[int]:
 
 
 def _enqueue_scene(model, frames, n_lr_images: int, batch: int, host: Optional[torch.Tensor] = None, bands=None,
-                   frame_select: str = "random", nodata: str = "fill", min_support: int = 1, self_ensemble: bool = False) -> _Pending:
-    """upload, zero scan, frame choice (the one host round trip: chunks x T flags down, chunks x n ids up), then every batch of
-    chunks through gather -> generator -> scatter and the download of mosaic + counter; returns without waiting for them.
-    With bands the gather is `scene_gather_bands` at the chunks' origins (32 i, 32 j); everything else is the same.
-    frame_select "clearest": the frame choice is keys -> rank on the current stream instead, and nothing comes back to the host
-    before the mosaic does.
-    nodata "keep": a zeroed support map, `scene_support_add` beside every gather (at the origins (32 i, 32 j)), `scene_apply_nodata`
-    behind the last scatter, and the support map behind the counter in the same download; nothing comes back earlier than before.
-    self_ensemble: the accumulator path with overlap 0 (`_enqueue_scene_blended`: the same chunks in the same order, so the same
-    frame choice) under this path's refusal of sizes that are no multiples of 32."""
-    if check_self_ensemble(self_ensemble):
-        return _enqueue_scene_blended(model, frames, n_lr_images, 0, batch, host, bands=bands, frame_select=frame_select,
-                                      nodata=nodata, min_support=min_support, self_ensemble=True, any_size=False)
+                   frame_select: str = "random", nodata: str = "fill", min_support: int = 1, self_ensemble: bool = False,
+                   blended: bool = False, overlap: int = 0) -> _Pending:
+    """Everything a scene queues, without waiting for it: upload, frame choice, every batch of generator rows through gather ->
+    generator -> write-out, and the one download of mosaic + counter.
+    The frame choice: under frame_select "random" a zero scan and the one host round trip (chunks x T flags down, chunks x n ids
+    up); under "clearest" keys -> rank on the current stream, and nothing comes back to the host before the mosaic does.
+    The write-out is the one difference between the two paths.  The grid path (not blended: H and W multiples of 32, the chunks at
+    (32 i, 32 j) in row-major order) gathers with `scene_gather` (with bands: `scene_gather_bands` at those origins) and writes
+    straight into the mosaic with `scene_scatter_u8`; it allocates no accumulator.  The accumulator path (blended: any size >= 32 x
+    32, chunks that overlap by `overlap`) gathers at the origins, adds into a zeroed uint32 accumulator of this scene's own
+    (`scene_blend_add`) and divides by the weight sums (`scene_blend_finish`).
+    nodata "keep": a zeroed support map, `scene_support_add` beside the gather, once per chunk, `scene_apply_nodata` behind the last
+    write-out, and the support map behind the counter in the same download; nothing comes back earlier than without it.
+    self_ensemble: always the accumulator path - not blended it is overlap 0, the same chunks in the same order and so the same
+    frame choice, under the grid path's refusal of sizes that are no multiples of 32.  The generator's rows are the (chunk, tf)
+    pairs, chunk-major with tf 0 .. 7 inside a chunk, and `batch` slices THAT list: gather_tf -> generator -> blend_add_tf per
+    slice, then `scene_blend_finish_scaled`.  The frames are chosen once per chunk as without it, and `scene_support_add` runs
+    beside the slice that holds the chunk's tf 0 row."""
+    self_ensemble = check_self_ensemble(self_ensemble)          # (the refusals, in this order, before anything is uploaded)
     if getattr(model, "scale", SCALE) != SCALE:
         raise NotImplementedError(f"scene inference runs scale {SCALE} generators only (scale = {model.scale})")
     n, batch = int(n_lr_images), int(batch)
     if batch < 1:
         raise ValueError(f"batch = {batch}")
-    check_frame_select(frame_select, _frames_T(frames), n)          # (before anything is uploaded)
-    nodata, min_support = check_nodata(nodata, min_support)
-    keep = nodata == "keep"
-    scene, C_out, bands = _upload_scene(model, frames, n, bands=bands)
-    dev = scene.device
-    T, H, W = scene.shape[:3]
-    gw, n_chunks = W // CHUNK, (H // CHUNK) * (W // CHUNK)
-    if frame_select == "clearest":
-        origins = torch.from_numpy(scene_chunk_grid(H, W, 0)).to(dev, non_blocking=True)    # (32 i, 32 j) in row-major order
-        frame_ids = scene_rank_frames(scene_frame_keys(scene, origins), n)
-    else:
-        has_zero = scene_zero_scan(scene).cpu().numpy()
-        frame_ids = torch.from_numpy(select_scene_frames(has_zero, n)).to(dev, non_blocking=True)
-    chunk_ids = torch.arange(n_chunks, dtype=torch.int32, device=dev)
-    if (bands is not None or keep) and frame_select != "clearest":
-        origins = torch.from_numpy(scene_chunk_grid(H, W, 0)).to(dev, non_blocking=True)    # (32 i, 32 j) in row-major order
-    Ho, Wo = SCALE * H, SCALE * W
-    buf, mosaic, counter, support_u8, support_off = _download_buffer(dev, Ho, Wo, C_out, keep)      # one download
-    support = torch.zeros(H, W, dtype=torch.int32, device=dev) if keep else None
-    with torch.no_grad():
-        for c0 in range(0, n_chunks, batch):
-            ids = chunk_ids[c0:c0 + batch]
-            plan = model.plan_for_inference(ids.shape[0], CHUNK, CHUNK)
-            if bands is None:
-                scene_gather(scene, ids, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
-            else:
-                scene_gather_bands(scene, bands, origins[c0:c0 + batch], frame_ids[c0:c0 + batch], plan.xin, plan.dt)
-            if keep:
-                scene_support_add(scene, origins[c0:c0 + batch], frame_ids[c0:c0 + batch], support)
-            model.run_forward(plan)
-            scene_scatter_u8(plan.out, ids, C_out, mosaic, counter, plan.dt)
-        if keep:
-            scene_apply_nodata(mosaic, support, min_support, support_u8)
-    if host is None or host.numel() != buf.numel():
-        host = torch.empty(buf.shape, dtype=torch.uint8, pin_memory=True)
-    host.copy_(buf, non_blocking=True)
-    ev = torch.cuda.Event()
-    ev.record()
-    return _Pending(host, ev, (Ho, Wo, C_out), getattr(model, "compute_dtype", None), n_chunks, support_off)
-
-
-def _enqueue_scene_blended(model, frames, n_lr_images: int, overlap: int, batch: int, host: Optional[torch.Tensor] = None,
-                           bands=None, frame_select: str = "random", nodata: str = "fill", min_support: int = 1,
-                           self_ensemble: bool = False, any_size: bool = True) -> _Pending:
-    """`_enqueue_scene` for a scene of any size >= 32 x 32 cut into chunks that overlap: upload, zero scan at the origins, frame
-    choice (the one host round trip; with frame_select "clearest" keys -> rank on the device, no round trip), a zeroed accumulator,
-    every batch of chunks through gather -> generator -> blend-add, the division by the weight sums and the download of mosaic +
-    counter; nodata "keep" as in `_enqueue_scene`, with `scene_apply_nodata` behind `scene_blend_finish`.
-    self_ensemble: the generator's rows are the (chunk, tf) pairs, chunk-major with tf 0 .. 7 inside a chunk, and `batch` slices THAT
-    list: gather_tf -> generator -> blend_add_tf per slice, then `scene_blend_finish_scaled`.  The frames are chosen once per chunk
-    as without it, and `scene_support_add` runs once per chunk (beside the launch that holds the chunk's tf 0 row)."""
-    self_ensemble = check_self_ensemble(self_ensemble)          # (before anything is uploaded)
-    if getattr(model, "scale", SCALE) != SCALE:
-        raise NotImplementedError(f"scene inference runs scale {SCALE} generators only (scale = {model.scale})")
-    n, batch = int(n_lr_images), int(batch)
-    if batch < 1:
-        raise ValueError(f"batch = {batch}")
-    window = blend_window(overlap)                  # (refuses a bad overlap before anything is uploaded)
+    accumulate = blended or self_ensemble
+    if not blended:
+        overlap = 0
+    if accumulate:
+        window = blend_window(overlap)
     check_frame_select(frame_select, _frames_T(frames), n)
     nodata, min_support = check_nodata(nodata, min_support)
     keep = nodata == "keep"
-    scene, C_out, bands = _upload_scene(model, frames, n, any_size=any_size, bands=bands)
+    scene, C_out, bands = _upload_scene(model, frames, n, any_size=blended, bands=bands)
     dev = scene.device
     T, H, W = scene.shape[:3]
-    grid = scene_chunk_grid(H, W, overlap)
+    grid = scene_chunk_grid(H, W, overlap)          # on the grid path (32 i, 32 j) in row-major order
     n_chunks = grid.shape[0]
-    origins = torch.from_numpy(grid).to(dev, non_blocking=True)
-    window = torch.from_numpy(window).to(dev, non_blocking=True)
-    Sy = torch.from_numpy(blend_weight_sums(H, overlap)).to(dev, non_blocking=True)
-    Sx = torch.from_numpy(blend_weight_sums(W, overlap)).to(dev, non_blocking=True)
+    origins = None
+    if accumulate or bands is not None or keep or frame_select == "clearest":
+        origins = torch.from_numpy(grid).to(dev, non_blocking=True)
+    if accumulate:
+        window = torch.from_numpy(window).to(dev, non_blocking=True)
+        Sy = torch.from_numpy(blend_weight_sums(H, overlap)).to(dev, non_blocking=True)
+        Sx = torch.from_numpy(blend_weight_sums(W, overlap)).to(dev, non_blocking=True)
     if frame_select == "clearest":
         frame_ids = scene_rank_frames(scene_frame_keys(scene, origins), n)
     else:
-        has_zero = scene_zero_scan_at(scene, origins).cpu().numpy()
+        has_zero = (scene_zero_scan_at(scene, origins) if accumulate else scene_zero_scan(scene)).cpu().numpy()
         frame_ids = torch.from_numpy(select_scene_frames(has_zero, n)).to(dev, non_blocking=True)
     Ho, Wo = SCALE * H, SCALE * W
     buf, mosaic, counter, support_u8, support_off = _download_buffer(dev, Ho, Wo, C_out, keep)      # one download
     support = torch.zeros(H, W, dtype=torch.int32, device=dev) if keep else None
-    acc = torch.zeros(Ho, Wo, C_out, dtype=torch.int32, device=dev)  # 4 bytes per output sample, this scene's own
+    if accumulate:
+        acc = torch.zeros(Ho, Wo, C_out, dtype=torch.int32, device=dev)  # 4 bytes per output sample, this scene's own
+    else:
+        chunk_ids = torch.arange(n_chunks, dtype=torch.int32, device=dev)
+    per = ENSEMBLE if self_ensemble else 1          # generator rows per chunk
+    row_org, row_ids, row_tf = origins, frame_ids, None
+    if self_ensemble:                               # the rows: (chunk, tf), chunk-major
+        row_org, row_ids = origins.repeat_interleave(ENSEMBLE, dim=0), frame_ids.repeat_interleave(ENSEMBLE, dim=0)
+        row_tf = torch.arange(ENSEMBLE, dtype=torch.int32, device=dev).repeat(n_chunks)
     with torch.no_grad():
-        if self_ensemble:
-            row_org = origins.repeat_interleave(ENSEMBLE, dim=0)              # the rows: (chunk, tf), chunk-major
-            row_ids = frame_ids.repeat_interleave(ENSEMBLE, dim=0)
-            row_tf = torch.arange(ENSEMBLE, dtype=torch.int32, device=dev).repeat(n_chunks)
-            for r0 in range(0, ENSEMBLE * n_chunks, batch):
-                r1 = min(r0 + batch, ENSEMBLE * n_chunks)
-                org, tf = row_org[r0:r1], row_tf[r0:r1]
-                plan = model.plan_for_inference(r1 - r0, CHUNK, CHUNK)
-                scene_gather_tf(scene, bands, org, row_ids[r0:r1], tf, plan.xin, plan.dt)
-                c0, c1 = -(-r0 // ENSEMBLE), -(-r1 // ENSEMBLE)              # the chunks whose tf 0 row lies in this slice
-                if keep and c1 > c0:
-                    scene_support_add(scene, origins[c0:c1], frame_ids[c0:c1], support)
-                model.run_forward(plan)
-                scene_blend_add_tf(plan.out, org, tf, C_out, window, acc, counter, plan.dt)
-            scene_blend_finish_scaled(acc, Sy, Sx, mosaic, ENSEMBLE * ENSEMBLE_ONE)
-        else:
-            for c0 in range(0, n_chunks, batch):
-                org = origins[c0:c0 + batch]
-                plan = model.plan_for_inference(org.shape[0], CHUNK, CHUNK)
-                if bands is None:
-                    scene_gather_at(scene, org, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
-                else:
-                    scene_gather_bands(scene, bands, org, frame_ids[c0:c0 + batch], plan.xin, plan.dt)
-                if keep:
-                    scene_support_add(scene, org, frame_ids[c0:c0 + batch], support)
-                model.run_forward(plan)
-                scene_blend_add(plan.out, org, C_out, window, acc, counter, plan.dt)
-            scene_blend_finish(acc, Sy, Sx, mosaic)
+        for r0 in range(0, per * n_chunks, batch):
+            r1 = min(r0 + batch, per * n_chunks)
+            plan = model.plan_for_inference(r1 - r0, CHUNK, CHUNK)
+            tf = None if row_tf is None else row_tf[r0:r1]
+            if accumulate or bands is not None:
+                _gather_at(scene, bands, row_org[r0:r1], row_ids[r0:r1], tf, plan.xin, plan.dt)
+            else:
+                scene_gather(scene, chunk_ids[r0:r1], row_ids[r0:r1], plan.xin, plan.dt)
+            c0, c1 = -(-r0 // per), -(-r1 // per)   # the chunks whose first row lies in this slice
+            if keep and c1 > c0:
+                scene_support_add(scene, origins[c0:c1], frame_ids[c0:c1], support)
+            model.run_forward(plan)
+            if accumulate:
+                _blend_add(plan.out, row_org[r0:r1], tf, C_out, window, acc, counter, plan.dt)
+            else:
+                scene_scatter_u8(plan.out, chunk_ids[r0:r1], C_out, mosaic, counter, plan.dt)
+        if accumulate:
+            _blend_finish(acc, Sy, Sx, mosaic, ENSEMBLE * ENSEMBLE_ONE if self_ensemble else None)
+            del acc
         if keep:
             scene_apply_nodata(mosaic, support, min_support, support_u8)
-    del acc
     if host is None or host.numel() != buf.numel():
         host = torch.empty(buf.shape, dtype=torch.uint8, pin_memory=True)
     host.copy_(buf, non_blocking=True)
@@ -919,9 +868,9 @@ def super_resolve_scene_blended(model, frames, n_lr_images: int, overlap: int = 
     outputs.  With `frame_select="clearest"` the mosaic of a flipped or transposed scene is the flipped or transposed mosaic, byte
     for byte, when the chunk origins are symmetric about the centre."""
     _check_return_support(nodata, min_support, return_support)
-    return _finish(_enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, bands=bands, frame_select=frame_select,
-                                          nodata=nodata, min_support=min_support, self_ensemble=check_self_ensemble(self_ensemble)),
-                   return_support)
+    return _finish(_enqueue_scene(model, frames, n_lr_images, batch, bands=bands, frame_select=frame_select, nodata=nodata,
+                                  min_support=min_support, self_ensemble=check_self_ensemble(self_ensemble), blended=True,
+                                  overlap=overlap), return_support)
 
 
 def super_resolve_scene(model, frames, n_lr_images: int, batch: int = 64, bands=None, frame_select: str = "random",
@@ -1058,13 +1007,9 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
             if k < len(mine):
                 name, blk, frames, bands = finish_read(reading)
                 reading = start_read(k + 1) if k + 1 < len(mine) else None
-                if blended:
-                    pending = _enqueue_scene_blended(model, frames, n_lr_images, overlap, batch, hosts[k & 1], bands=bands,
-                                                     frame_select=frame_select, nodata=nodata, min_support=min_support,
-                                                     self_ensemble=self_ensemble)
-                else:
-                    pending = _enqueue_scene(model, frames, n_lr_images, batch, hosts[k & 1], bands=bands, frame_select=frame_select,
-                                             nodata=nodata, min_support=min_support, self_ensemble=self_ensemble)
+                pending = _enqueue_scene(model, frames, n_lr_images, batch, hosts[k & 1], bands=bands, frame_select=frame_select,
+                                         nodata=nodata, min_support=min_support, self_ensemble=self_ensemble, blended=blended,
+                                         overlap=overlap)
                 hosts[k & 1] = pending.host
                 first = np.array(frames[0])
                 del frames, bands

@@ -136,4 +136,9 @@ def test_the_entry_point_refuses_bad_arguments_without_a_launch():
     assert g(p, p, 1, 2, 64, 20, p, p, 1, 1, v, hip.F32, None) == -2
     assert g(p, p, 1, 2, 40, 50, p, p, 1, 1, v, 7, None) == -2                      # a dtype the converters do not know
     assert g(p, p, 1, 2, 40, 50, p, p, 1, 1, v, hip.F32H3, None) == -2
+    # an invalid argument beside an unsupported shape: the invalid argument wins
+    assert g(p, None, 1, 2, 64, 20, p, p, 1, 1, v, hip.F32, None) == -1             # no bands, narrower than a chunk
+    assert g(p, p, 0, 2, 40, 50, p, p, 1, 3, v, 7, None) == -1                      # K < 1, n > T and an unknown dtype
+    assert g(p, p, 1, 2, 64, 20, None, p, 1, 1, v, hip.F32, None) == -1             # no origins, narrower than a chunk
+    assert g(p, p, 1, 4, 64, 20, p, p, 1, 3, v, hip.F32, None) == -1                # 12 channels in a pixel of 8, narrower than a chunk
     assert lib.ssr_abi_version() == 3

@@ -224,6 +224,9 @@ def test_blend_entry_points_refuse_bad_geometry_without_a_launch():
     assert lib.ssr_scene_gather_at(p, 2, 40, 50, p, p, 1, 1, v, hip.F32H3, None) == -2
     assert lib.ssr_scene_gather_at(p, 4, 40, 50, p, p, 1, 3, v, hip.F32, None) == -1         # 9 channels do not fit a pixel of 8
     assert lib.ssr_scene_gather_at(p, 2, 40, 50, None, p, 1, 1, v, hip.F32, None) == -1
+    # an invalid argument beside an unsupported shape: the invalid argument wins
+    assert lib.ssr_scene_gather_at(p, 2, 64, 20, None, p, 1, 1, v, hip.F32, None) == -1      # no origins, narrower than a chunk
+    assert lib.ssr_scene_gather_at(p, 4, 64, 20, p, p, 1, 3, v, 7, None) == -1               # 9 channels in a pixel of 8, W and dtype
     assert lib.ssr_scene_blend_add(v, 7, p, 1, 3, p, p, 160, 200, p, None) == -2
     assert lib.ssr_scene_blend_add(v, hip.F32, p, 1, 3, p, p, 160, 202, p, None) == -2       # not 4 x a width
     assert lib.ssr_scene_blend_add(v, hip.F32, p, 1, 3, p, p, 124, 200, p, None) == -2       # lower than a chunk
@@ -232,9 +235,13 @@ def test_blend_entry_points_refuse_bad_geometry_without_a_launch():
     assert lib.ssr_scene_blend_add(v, hip.F32, p, 1, 3, p, p + 4, 160, 200, p, None) == -1   # accumulator not 16-byte aligned
     assert lib.ssr_scene_blend_add(hip.View(p, 16, 0), hip.F32, p, 1, 9, p, p, 160, 200, p, None) == -1    # more than 8 channels
     assert lib.ssr_scene_blend_add(hip.View(p, 8, 8), hip.F32, p, 1, 3, p, p, 160, 200, p, None) == -1     # channels outside the pixel
+    assert lib.ssr_scene_blend_add(v, 7, p, 1, 3, p, p, 160, 202, None, None) == -1          # no counter, an unknown dtype and width
+    assert lib.ssr_scene_blend_add(v, hip.F32, p, 1, 3, p, p + 4, 124, 200, p, None) == -1   # accumulator alignment, lower than a chunk
     assert lib.ssr_scene_blend_finish(p, p, p, 3, p, 160, 202, None) == -2
     assert lib.ssr_scene_blend_finish(p, p, p, 3, p, 100, 200, None) == -2
     assert lib.ssr_scene_blend_finish(p, None, p, 3, p, 160, 200, None) == -1
     assert lib.ssr_scene_blend_finish(p, p, p, 3, p + 2, 160, 200, None) == -1               # mosaic not 4-byte aligned
     assert lib.ssr_scene_blend_finish(p, p, p, 9, p, 160, 200, None) == -1
+    assert lib.ssr_scene_blend_finish(p, None, p, 3, p, 160, 202, None) == -1                # no row sums, not 4 x a width
+    assert lib.ssr_scene_blend_finish(p, p, p, 9, p, 100, 200, None) == -1                   # 9 channels, lower than a chunk
     assert lib.ssr_abi_version() == 3

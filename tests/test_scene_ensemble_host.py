@@ -229,6 +229,11 @@ def test_ensemble_entry_points_refuse_bad_geometry_without_a_launch():
     assert lib.ssr_scene_gather_tf(p, p, 2, 4, 40, 50, p, p, p, 1, 2, v, hip.F32, None) == -1             # 10 channels, a pixel of 8
     assert lib.ssr_scene_gather_tf(p, None, 0, 4, 40, 50, p, p, p, 1, 3, v, hip.F32, None) == -1          # 9 channels, a pixel of 8
     assert lib.ssr_scene_gather_tf(None, None, 0, 2, 40, 50, p, p, p, 1, 1, v, hip.F32, None) == -1
+    # an invalid argument beside an unsupported shape: the invalid argument wins
+    assert lib.ssr_scene_gather_tf(p, None, 0, 2, 64, 20, p, p, None, 1, 1, v, hip.F32, None) == -1       # no transform ids, W < 32
+    assert lib.ssr_scene_gather_tf(p, None, 1, 2, 40, 50, p, p, p, 1, 3, v, 7, None) == -1                # K without bands, n > T, dtype
+    assert lib.ssr_scene_gather_tf(p, None, 0, 2, 64, 20, None, p, p, 1, 1, v, hip.F32, None) == -1       # no origins, W < 32
+    assert lib.ssr_scene_gather_tf(p, None, 0, 4, 64, 20, p, p, p, 1, 3, v, hip.F32, None) == -1          # 9 channels, a pixel of 8, W < 32
     assert lib.ssr_scene_blend_add_tf(v, 7, p, p, 1, 3, p, p, 160, 200, p, None) == -2
     assert lib.ssr_scene_blend_add_tf(v, hip.F32, p, p, 1, 3, p, p, 160, 202, p, None) == -2              # not 4 x a width
     assert lib.ssr_scene_blend_add_tf(v, hip.F32, p, p, 1, 3, p, p, 124, 200, p, None) == -2              # lower than a chunk
@@ -237,6 +242,9 @@ def test_ensemble_entry_points_refuse_bad_geometry_without_a_launch():
     assert lib.ssr_scene_blend_add_tf(v, hip.F32, p, p, 1, 3, p, p + 4, 160, 200, p, None) == -1          # accumulator not 16-byte aligned
     assert lib.ssr_scene_blend_add_tf(hip.View(p, 16, 0), hip.F32, p, p, 1, 9, p, p, 160, 200, p, None) == -1          # more than 8 channels
     assert lib.ssr_scene_blend_add_tf(hip.View(p, 8, 8), hip.F32, p, p, 1, 3, p, p, 160, 200, p, None) == -1           # channels outside the pixel
+    assert lib.ssr_scene_blend_add_tf(v, 7, p, None, 1, 3, p, p, 160, 202, p, None) == -1                 # no transform ids, dtype, width
+    assert lib.ssr_scene_blend_add_tf(v, 7, p, p, 1, 3, p, p, 160, 202, None, None) == -1                 # no counter, dtype, width
+    assert lib.ssr_scene_blend_add_tf(v, hip.F32, p, p, 1, 3, p, p + 4, 124, 200, p, None) == -1          # accumulator alignment, height
     assert lib.ssr_scene_blend_finish_scaled(p, p, p, 3, 8 * 8191, p, 160, 202, None) == -2
     assert lib.ssr_scene_blend_finish_scaled(p, p, p, 3, 8 * 8191, p, 100, 200, None) == -2
     assert lib.ssr_scene_blend_finish_scaled(p, p, p, 3, 0, p, 160, 200, None) == -1                      # no scale
@@ -244,4 +252,7 @@ def test_ensemble_entry_points_refuse_bad_geometry_without_a_launch():
     assert lib.ssr_scene_blend_finish_scaled(p, None, p, 3, 8 * 8191, p, 160, 200, None) == -1
     assert lib.ssr_scene_blend_finish_scaled(p, p, p, 3, 8 * 8191, p + 2, 160, 200, None) == -1           # mosaic not 4-byte aligned
     assert lib.ssr_scene_blend_finish_scaled(p, p, p, 9, 8 * 8191, p, 160, 200, None) == -1
+    assert lib.ssr_scene_blend_finish_scaled(p, p, p, 3, 0, p, 160, 202, None) == -1                      # no scale, not 4 x a width
+    assert lib.ssr_scene_blend_finish_scaled(p, None, p, 3, 8 * 8191, p, 160, 202, None) == -1            # no row sums, not 4 x a width
+    assert lib.ssr_scene_blend_finish_scaled(p, p, p, 9, 8 * 8191, p, 100, 200, None) == -1               # 9 channels, lower than a chunk
     assert lib.ssr_abi_version() == 3
