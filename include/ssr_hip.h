@@ -606,6 +606,33 @@ int ssr_gram_l1(const float* gx, const float* gt, void* sgn, int32_t dtype, int6
 int ssr_gram_bwd(ssr_view f, const void* sgn, ssr_view gf, int32_t dtype, int32_t N, int32_t HW, int32_t C, float coef,
                  int32_t accumulate, void* stream);
 
+/* ---- LPIPS validation metric (csrc/lpips.hip; `calculate_lpips`, lpips_model 'vgg'; additive: the ABI version stays 3).  The VGG16
+ *      convolutions run through ssr_conv2d in SSR_F32 with SSR_ACT_RELU, the pooling behind a tap through ssr_relu_maxpool2_fwd ----
+ * ssr_lpips_input: the scaling layer.  u is uint8 [npix][3]; y an NHWC fp32 view (SSR_F32 / SSR_F32X3 storage) of npix pixels with
+ *   at least coff + 8 channels, 16-byte aligned (cs % 4 == 0, coff % 4 == 0).  Network channel c = 0, 1, 2 receives, every step
+ *   rounded to fp32 in this order (IEEE division, so a numpy float32 restatement gives the same bits),
+ *       v = (float)u[p][perm[c]] / 255.0f;   if (normalize) v = 2.0f * v - 1.0f;   y[p][coff + c] = (v - shift[c]) / scale[c];
+ *   channels coff + 3 .. coff + 7 are written as 0.  shift, scale (3 floats, scale != 0) and perm (3 ints in 0 .. 2; {2, 1, 0}
+ *   feeds an RGB image as BGR) are host arrays, copied into the launch.  A null pointer, npix <= 0, a bad perm or scale, a view
+ *   narrower than coff + 8 or misaligned: SSR_EINVAL; bf16 storage: SSR_EUNSUP; no launch in either case.
+ * ssr_lpips_layer: one tap.  fa, fb are NHWC fp32 views of N x HW pixels with C valid channels (the features of the two images,
+ *   taken BEFORE the ReLU when relu = 1, which the kernel then applies; 16-byte aligned as above), w holds C floats on the device
+ *   (16-byte aligned).  With a^[p][c] = a[p][c] / (sqrt(sum_c a[p][c]^2) + 1e-10), the norm in fp64 (a pixel that is all zero
+ *   gives 0 / 1e-10 = 0),
+ *       partial[n][b] = block b's share of (1 / HW) sum_p sum_c w[c] * (a^[p][c] - b^[p][c])^2        (double, b < nblk)
+ *   where the difference is formed directly in fp64 from the two normalised values (never from the expanded square, which
+ *   cancels for similar images) and rounded to fp32, d * d and then w[c] * (d * d) are fp32 products, and all sums are fp64.
+ *   Every partial is written (no atomics, no zeroing needed); the caller adds partial[n][0 .. nblk) in index order.  Identical
+ *   fa and fb give exactly 0.0; two launches on the same inputs give the same bytes.
+ *   SSR_EUNSUP: bf16 storage, C % 64 != 0 or C > 512.  SSR_EINVAL: a null pointer, N, HW or C <= 0, N > 65535, a view narrower
+ *   than coff + C or misaligned.  No launch in any of these cases.
+ * ssr_lpips_layer_blocks: nblk for this shape (>= 1; SSR_EINVAL for a size <= 0). */
+int ssr_lpips_input(const uint8_t* u, ssr_view y, int32_t dtype, int64_t npix, const float* shift, const float* scale,
+                    const int32_t* perm, int32_t normalize, void* stream);
+int ssr_lpips_layer_blocks(int32_t N, int32_t HW, int32_t C);
+int ssr_lpips_layer(ssr_view fa, ssr_view fb, const float* w, int32_t dtype, int32_t N, int32_t HW, int32_t C, int32_t relu,
+                    double* partial, void* stream);
+
 /* SSR_F32X3 weight gradients: split an fp32 buffer (n % 4 == 0 elements) into bf16 planes hi = bf16(x), lo = bf16(x - hi); the
  * bf16 wgrad kernel then accumulates (x_hi, dy_hi) + (x_hi, dy_lo) + (x_lo, dy_hi) into the fp32 gradient. */
 int ssr_split_bf16(const float* x, void* hi, void* lo, int64_t n, void* stream);

@@ -134,6 +134,7 @@ ABI_SYMBOLS = [
     "ssr_scene_frame_keys", "ssr_scene_rank_frames",
     "ssr_scene_support_add", "ssr_scene_apply_nodata",
     "ssr_scene_gather_tf", "ssr_scene_blend_add_tf", "ssr_scene_blend_finish_scaled",
+    "ssr_lpips_input", "ssr_lpips_layer_blocks", "ssr_lpips_layer",
     "ssr_device_info", "ssr_abi_version",
 ]
 SCAN_MAX_RANGES = 8           # SSR_SCAN_MAX_RANGES: ranges per ssr_nonfinite_scan call
@@ -224,6 +225,9 @@ def lib() -> C.CDLL:
     l.ssr_scene_gather_tf.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, View, i32, vp]
     l.ssr_scene_blend_add_tf.argtypes = [View, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp]
     l.ssr_scene_blend_finish_scaled.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp]
+    l.ssr_lpips_input.argtypes = [vp, View, i32, i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(i32), i32, vp]
+    l.ssr_lpips_layer_blocks.argtypes = [i32, i32, i32]
+    l.ssr_lpips_layer.argtypes = [View, View, vp, i32, i32, i32, i32, i32, vp, vp]
     l.ssr_device_info.argtypes = [C.c_char_p, i32]
     l.ssr_abi_version.argtypes = []
     for s in ABI_SYMBOLS:

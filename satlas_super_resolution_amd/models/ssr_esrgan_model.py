@@ -403,7 +403,7 @@ class SSRESRGANModel:
             o.step.fill_(step)
         self.ts.iter = int(resume_state.get("iter", 0))
 
-    # ---- validation (ssr_esrgan_model.py:269-352; metrics: psnr / ssim as BasicSR, cpsnr as ssr/metrics/cpsnr.py) ----
+    # ---- validation (ssr_esrgan_model.py:269-352; metrics: psnr / ssim as BasicSR, cpsnr as ssr/metrics/cpsnr.py, lpips as ssr/metrics/lpips.py) ----
     def validation(self, dataloader, current_iter, tb_logger, save_img=False):
         """BaseModel.validation -> nondist_validation on every rank's own loader (the reference's dist_validation only runs
         on rank 0)."""
@@ -421,6 +421,8 @@ class SSRESRGANModel:
             if mo.get("type") not in M.METRICS:
                 raise NotImplementedError(f"metric {name}: type {mo.get('type')!r} is outside the MI355X path "
                                           f"(have {sorted(M.METRICS)})")
+            if mo["type"] in M.METRIC_CHECKS:      # calculate_lpips: its keys and its weights file, before the first forward
+                M.METRIC_CHECKS[mo["type"]](**{k: v for k, v in mo.items() if k not in ("type", "better")})
         self.metric_results = {m: 0.0 for m in metrics2run}
         rec = self.best_metric_results.setdefault(dataset_name, {})
         for m, mo in metrics2run.items():
