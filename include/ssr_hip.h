@@ -424,6 +424,44 @@ int ssr_axpby_f32(float a, const float* x, float b, float* y, int64_t n, void* s
 int ssr_nonfinite_scan(const float* const* srcs, const int64_t* ns, int32_t n_ranges, int32_t* flag, void* stream);
 int ssr_adam_step_guarded(const ssr_adam_args* a, int32_t* flag, int32_t* skipped, void* stream);
 
+/* ---- BasicSR's other optimizers (csrc/optim.hip): the single-tensor arithmetic of torch.optim.Adam / AdamW / SGD / RMSprop over a
+ *      flat fp32 arena, with what ssr_adam_step has (grad_scale folded in, lr and step on the device, the model_ema blend fused).
+ * kind SSR_OPT_ADAM    g += weight_decay p (coupled); exp_avg, exp_avg_sq; SSR_OPT_AMSGRAD: max_exp_avg_sq = max(max_exp_avg_sq,
+ *                      exp_avg_sq) takes exp_avg_sq's place in the denominator.  With weight_decay 0 and no amsgrad the call IS
+ *                      ssr_adam_step[_guarded] (forwarded: the same bits).
+ *      SSR_OPT_ADAMW   p *= 1 - lr weight_decay first (decoupled), then Adam's update; amsgrad as above.
+ *      SSR_OPT_SGD     g += weight_decay p; momentum != 0: momentum_buffer = g while *step == 0 (the first applied step), afterwards
+ *                      momentum buf + (1 - dampening) g; SSR_OPT_NESTEROV: g += momentum buf, otherwise g = buf; p -= lr g.
+ *      SSR_OPT_RMSPROP g += weight_decay p; square_avg = alpha square_avg + (1 - alpha) g^2; SSR_OPT_CENTERED: grad_avg lerps to g by
+ *                      1 - alpha and avg = sqrt(square_avg - grad_avg^2) (not clamped, as torch), otherwise avg = sqrt(square_avg);
+ *                      avg += eps; momentum > 0: momentum_buffer = momentum buf + g / avg, p -= lr buf; otherwise p -= lr g / avg.
+ * A state arena is needed exactly when its option is on (max_exp_avg_sq: amsgrad; momentum_buffer: momentum != 0; grad_avg: centered)
+ * and is neither read nor written otherwise (pass NULL).  SSR_EINVAL without a launch: a null param / grad / lr / step or a needed arena,
+ * n <= 0, a flag of another kind, momentum < 0, nesterov without momentum or with dampening.  SSR_EUNSUP: another kind.
+ * Both launches end with *step += 1.  ssr_optim_step_guarded reads *flag on the device like ssr_adam_step_guarded: non-zero leaves
+ * param, every state arena and *step as they are, moves only the EMA (toward the unchanged p), *skipped += 1; *flag is 0 afterwards. */
+#define SSR_OPT_ADAM 0
+#define SSR_OPT_ADAMW 1
+#define SSR_OPT_SGD 2
+#define SSR_OPT_RMSPROP 3
+#define SSR_OPT_AMSGRAD 1
+#define SSR_OPT_NESTEROV 2
+#define SSR_OPT_CENTERED 4
+typedef struct ssr_optim_args {
+    float* param; const float* grad;
+    float* exp_avg; float* exp_avg_sq; float* max_exp_avg_sq;      /* Adam, AdamW */
+    float* momentum_buffer;                                        /* SGD, RMSprop */
+    float* square_avg; float* grad_avg;                            /* RMSprop */
+    float* ema;               /* NULL or EMA arena: ema = ema*decay + p*(1-decay) */
+    int64_t n;
+    const float* lr;          /* device scalar */
+    int32_t* step;            /* device counter of applied steps, incremented by the launch */
+    int32_t kind, flags;
+    float beta1, beta2, eps, weight_decay, momentum, dampening, alpha, ema_decay, grad_scale;
+} ssr_optim_args;
+int ssr_optim_step(const ssr_optim_args* a, void* stream);
+int ssr_optim_step_guarded(const ssr_optim_args* a, int32_t* flag, int32_t* skipped, void* stream);
+
 /* ---- image quantisation and validation metrics (csrc/metrics.hip) ----
  * ssr_quantize_u8: fp32 NCHW -> uint8 NHWC, clamp(0,1) * 255 then mode 0: round half to even (basicsr tensor2img as called at
  *   /root/reference/ssr/models/ssr_esrgan_model.py:302-305), mode 1: truncate (astype(uint8) at /root/reference/ssr/infer_grid.py:60-64,

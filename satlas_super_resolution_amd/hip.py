@@ -120,6 +120,19 @@ class AdamArgs(C.Structure):
                 ("grad_scale", C.c_float)]
 
 
+OPTIM_KINDS = {"Adam": 0, "AdamW": 1, "SGD": 2, "RMSprop": 3}      # `kind` of ssr_optim_step (SSR_OPT_*)
+OPT_AMSGRAD, OPT_NESTEROV, OPT_CENTERED = 1, 2, 4                 # `flags` of ssr_optim_step
+
+
+class OptimArgs(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("max_exp_avg_sq", C.c_void_p), ("momentum_buffer", C.c_void_p), ("square_avg", C.c_void_p), ("grad_avg", C.c_void_p),
+                ("ema", C.c_void_p), ("n", C.c_int64), ("lr", C.c_void_p), ("step", C.c_void_p),
+                ("kind", C.c_int32), ("flags", C.c_int32),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("momentum", C.c_float),
+                ("dampening", C.c_float), ("alpha", C.c_float), ("ema_decay", C.c_float), ("grad_scale", C.c_float)]
+
+
 # every symbol include/ssr_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "ssr_conv2d", "ssr_conv2d_fixup", "ssr_conv2d_batch", "ssr_conv2d_impl", "ssr_conv2d_variant", "ssr_conv2d_symbol", "ssr_conv2d_chain", "ssr_conv2d_chain_ok", "ssr_conv2d_chain_state_bytes", "ssr_conv2d_ck", "ssr_conv2d_s2d_ok", "ssr_rdb_forward", "ssr_rdb_backward", "ssr_rdb_tile_of", "ssr_conv2d_wgrad", "ssr_wgrad_reduce", "ssr_wgrad_tiles", "ssr_wgrad_ci_tile", "ssr_wgrad_co_tile", "ssr_pack_weights", "ssr_pack_dgrad_gather", "ssr_add_views", "ssr_nchw_to_nhwc", "ssr_nhwc_to_nchw",
@@ -128,6 +141,7 @@ ABI_SYMBOLS = [
     "ssr_quantize_u8", "ssr_metric_shift_sums", "ssr_metric_ssim_sums", "ssr_split_bf16", "ssr_split_bf16_multi", "ssr_channel_affine", "ssr_relu_maxpool2_fwd", "ssr_relu_maxpool2_bwd",
     "ssr_gram_splits", "ssr_gram_fwd", "ssr_gram_l1", "ssr_gram_bwd",
     "ssr_nonfinite_scan", "ssr_adam_step_guarded", "ssr_quantize_u8_checked",
+    "ssr_optim_step", "ssr_optim_step_guarded",
     "ssr_scene_zero_scan", "ssr_scene_gather", "ssr_scene_scatter_u8",
     "ssr_scene_zero_scan_at", "ssr_scene_gather_at", "ssr_scene_blend_add", "ssr_scene_blend_finish",
     "ssr_scene_gather_bands",
@@ -209,6 +223,8 @@ def lib() -> C.CDLL:
     l.ssr_gram_bwd.argtypes = [View, vp, View, i32, i32, i32, i32, f32, i32, vp]
     l.ssr_nonfinite_scan.argtypes = [C.POINTER(vp), C.POINTER(i64), i32, vp, vp]
     l.ssr_adam_step_guarded.argtypes = [C.POINTER(AdamArgs), vp, vp, vp]
+    l.ssr_optim_step.argtypes = [C.POINTER(OptimArgs), vp]
+    l.ssr_optim_step_guarded.argtypes = [C.POINTER(OptimArgs), vp, vp, vp]
     l.ssr_quantize_u8_checked.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
     l.ssr_scene_zero_scan.argtypes = [vp, i32, i32, i32, vp, vp]
     l.ssr_scene_gather.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, View, i32, vp]

@@ -9,17 +9,18 @@
 Same registry name and the same `opt` dictionary (YAML) keys.  Instead of autograd over ~41k ATen ops per
 step, optimize_parameters() replays the fused HIP-graph step of train_step.ESRGANTrainStep.
 Scope: BasicSR's pixel (L1 / MSE / Charbonnier) and GAN (vanilla / lsgan / wgan / wgan_softplus / hinge) losses (+ VGG19 perceptual: feature and Gram-style terms; + SSIM) losses, USM-sharpened ground truth,
-`feed_disc_lr` and `old_hr` discriminator inputs.  Anything this path does not implement raises NotImplementedError naming the
-option (clip / ldl losses, other optimizers or schedulers, weight decay) — nothing is silently ignored."""
+`feed_disc_lr` and `old_hr` discriminator inputs, BasicSR's optimizers (Adam / AdamW / SGD / RMSprop with their options) and
+schedulers (MultiStepRestartLR, CosineAnnealingRestartLR; optimizers.py).  Anything this path does not implement raises
+NotImplementedError naming the option (clip / ldl losses, Adamax / ASGD / Rprop, other schedulers) — nothing is silently ignored."""
 from __future__ import annotations
 
 import math
 import os
-from collections import Counter, OrderedDict
+from collections import OrderedDict
 
 import torch
 
-from .. import hip
+from .. import hip, optimizers
 from ..dp import init_distributed
 from ..registry import MODEL_REGISTRY
 from ..train_step import ESRGANTrainStep, StepConfig
@@ -88,7 +89,13 @@ def train_config_from_opt(opt: dict) -> StepConfig:
 
     ssim_opt holds `type: SSIMLoss` and optionally `loss_weight` (default 1.0, as SSIMLoss.__init__); the window (5 x 5) is fixed in
     the reference's forward.  pixel_opt holds `type`, `loss_weight`, `reduction: mean` and, for CharbonnierLoss, `eps` (default 1e-12) -
-    the constructors' arguments.  Any other type or key raises NotImplementedError naming it."""
+    the constructors' arguments.  Any other type or key raises NotImplementedError naming it.
+
+    The same pattern for `optim_g` / `optim_d` (BasicSR get_optimizer: Adam, AdamW, SGD, RMSprop with the numeric and boolean arguments
+    of the torch.optim constructors - optimizers.normalize_optim) and for `scheduler` (restarts / restart_weights of MultiStepRestartLR,
+    CosineAnnealingRestartLR - optimizers.Schedule, which SSRESRGANModel evaluates): step_config_from_opt sees plain Adam blocks
+    and no scheduler where it would refuse; StepConfig.optim_g / .optim_d carry the full description unless the block IS plain Adam
+    (weight_decay 0, no amsgrad), which stays on the launches it always had."""
     train_opt = opt.get("train", {}) or {}
     rest_train = dict(train_opt)
     ssim = None
@@ -124,10 +131,22 @@ def train_config_from_opt(opt: dict) -> StepConfig:
         if gan_type not in ("vanilla",) + tuple(hip.GAN_TYPES):
             raise NotImplementedError(f"train.gan_opt.gan_type={gan_type!r}: only vanilla, lsgan, wgan, wgan_softplus, hinge")
         rest_train["gan_opt"] = dict(gan, gan_type="vanilla")
+    specs = {}
+    for name in ("optim_g", "optim_d"):
+        spec = optimizers.normalize_optim(name, train_opt.get(name))
+        if optimizers.is_plain_adam(spec) and not spec.get("decoupled_weight_decay"):
+            specs[name] = None          # step_config_from_opt reads the block itself, as ever
+            continue
+        specs[name] = spec
+        rest_train[name] = {"type": "Adam", "lr": spec["lr"], "betas": spec.get("betas", (0.9, 0.999)), "eps": spec.get("eps", 1e-8)}
+    sched = optimizers.Schedule(train_opt.get("scheduler"), train_opt.get("total_iter"))     # validates; the model builds its own
+    if not sched.plain_multistep:
+        rest_train.pop("scheduler", None)
     rest = dict(opt)
     rest["train"] = rest_train
     cfg = step_config_from_opt(rest)
     cfg.ssim, cfg.pixel_type, cfg.pixel_eps, cfg.gan_type = ssim, pixel_type, pixel_eps, gan_type
+    cfg.optim_g, cfg.optim_d = specs["optim_g"], specs["optim_d"]
     return cfg
 
 
@@ -154,9 +173,8 @@ class SSRESRGANModel:
             self.cfg = train_config_from_opt(opt)
         else:
             self.d_kwargs, self.cfg = None, StepConfig()
-        sch = opt.get("train", {}).get("scheduler", {})
-        self.milestones = list(sch.get("milestones", []))
-        self.gamma = float(sch.get("gamma", 0.1)) if sch else 1.0
+        train_opt = opt.get("train", {}) or {}
+        self.schedule = optimizers.Schedule(train_opt.get("scheduler"), train_opt.get("total_iter") if self.is_train else None)
         self.ts = None
         self._pending_state = None         # resume_training() before the first batch built the step (train.py:64-65)
         self._infer = None                 # (store, plan) of test()
@@ -175,7 +193,7 @@ class SSRESRGANModel:
         carry = None
         if old is not None:     # a ragged last batch / another tile size: carry every piece of state over, then free the old step
             carry = dict(g=old.g_store.state_dict(), d=old.d_store.state_dict(),
-                         opt=[(o.exp_avg.clone(), o.exp_avg_sq.clone(), o.step.clone(), o.skipped.clone()) for o in (old.opt_g, old.opt_d)],
+                         opt=[({k: t.clone() for k, t in o.arenas.items()}, o.step.clone(), o.skipped.clone()) for o in (old.opt_g, old.opt_d)],
                          ema=None if old.opt_g.ema is None else old.opt_g.ema.clone(), it=old.iter)
             del old
             import gc
@@ -186,8 +204,10 @@ class SSRESRGANModel:
             self._init_params()
         else:
             self.ts.load_state(carry["g"], carry["d"], reset_ema=False)
-            for o, (m, v, s, k) in zip((self.ts.opt_g, self.ts.opt_d), carry["opt"]):
-                o.exp_avg.copy_(m); o.exp_avg_sq.copy_(v); o.step.copy_(s); o.skipped.copy_(k)
+            for o, (arenas, s, k) in zip((self.ts.opt_g, self.ts.opt_d), carry["opt"]):
+                for key, t in arenas.items():          # every state arena of the optimizer (exp_avg, ..., momentum_buffer, ...)
+                    o.arenas[key].copy_(t)
+                o.step.copy_(s); o.skipped.copy_(k)
             if carry["ema"] is not None:
                 self.ts.opt_g.ema.copy_(carry["ema"])
             self.ts.iter = carry["it"]
@@ -275,12 +295,9 @@ class SSRESRGANModel:
     def update_learning_rate(self, current_iter: int, warmup_iter: int = -1):
         """BasicSR BaseModel.update_learning_rate: the schedulers are stepped once per call from the second call on
         (last_epoch = current_iter - 1), MultiStepRestartLR multiplies by gamma when last_epoch reaches a milestone
-        (esrgan_s2naip_urban.yml:109-112); during warm-up the LR is base * current_iter / warmup_iter."""
-        k = sum(1 for m in self.milestones if current_iter - 1 >= m)
-        f = self.gamma ** k
-        if warmup_iter > 0 and current_iter < warmup_iter:
-            f = current_iter / warmup_iter
-        self.current_lrs = [self.cfg.lr_g * f, self.cfg.lr_d * f]
+        (esrgan_s2naip_urban.yml:109-112); during warm-up the LR is base * current_iter / warmup_iter.  The closed forms, restarts and
+        CosineAnnealingRestartLR: optimizers.Schedule."""
+        self.current_lrs = [self.schedule.lr(self.cfg.lr_g, current_iter, warmup_iter), self.schedule.lr(self.cfg.lr_d, current_iter, warmup_iter)]
         if self.ts is not None:
             self.ts.opt_g.set_lr(self.current_lrs[0])
             self.ts.opt_d.set_lr(self.current_lrs[1])
@@ -331,9 +348,13 @@ class SSRESRGANModel:
 
     # ---- checkpoints (BasicSR layout, loadable by either side) ----
     def _optimizer_state_dict(self, o, lr, betas):
-        """torch.optim.Adam.state_dict() over the parameters in named_parameters() order (BasicSR setup_optimizers)."""
+        """torch.optim.Adam.state_dict() over the parameters in named_parameters() order (BasicSR setup_optimizers); the other
+        optimizers (o.spec): optimizers.optimizer_state_dict."""
         st = o.store
         keys = list(st.offsets)
+        if o.spec is not None:
+            per = [{a: st.tensor(k, t) for a, t in o.arenas.items()} for k in keys]
+            return optimizers.optimizer_state_dict(o.spec, lr, per, int(o.step.item()))
         step = float(o.step.item())
         state = {i: {"step": torch.tensor(step), "exp_avg": st.tensor(k, o.exp_avg).detach().cpu().clone(),
                      "exp_avg_sq": st.tensor(k, o.exp_avg_sq).detach().cpu().clone()} for i, k in enumerate(keys)}
@@ -343,11 +364,8 @@ class SSRESRGANModel:
         return {"state": state, "param_groups": [group]}
 
     def _scheduler_state_dict(self, base_lr, lr, current_iter):
-        """basicsr MultiStepRestartLR.state_dict() (= the scheduler's __dict__ minus the optimizer)."""
-        last = max(int(current_iter) - 1, 0)
-        return {"milestones": Counter(self.milestones), "gamma": self.gamma, "restarts": [0], "restart_weights": [1],
-                "base_lrs": [base_lr], "last_epoch": last, "_step_count": last + 1, "verbose": False,
-                "_get_lr_called_within_step": False, "_last_lr": [lr]}
+        """basicsr MultiStepRestartLR / CosineAnnealingRestartLR .state_dict() (= the scheduler's __dict__ minus the optimizer)."""
+        return self.schedule.state_dict(base_lr, lr, current_iter)
 
     def save(self, epoch: int, current_iter: int):
         """BasicSR layout: net_g_{iter}.pth = {'params', 'params_ema'}, net_d_{iter}.pth = {'params'},
@@ -387,11 +405,20 @@ class SSRESRGANModel:
             self.update_learning_rate(it)
 
     def _apply_resume_state(self, resume_state: dict):
-        for o, s in zip((self.ts.opt_g, self.ts.opt_d), resume_state["optimizers"]):
+        for o, s, name in zip((self.ts.opt_g, self.ts.opt_d), resume_state["optimizers"], ("optim_g", "optim_d")):
             st = o.store
             keys = list(st.offsets)
             per = s["state"]
             assert len(per) in (0, len(keys)), f"optimizer state has {len(per)} entries, network has {len(keys)} parameters"
+            spec = o.spec if o.spec is not None else dict(optimizers.OPTIM_DEFAULTS["Adam"], type="Adam")
+            optimizers.check_resume_type(name, spec, s)      # another optimizer type's state: refused by name
+            if o.spec is not None:
+                for i, k in enumerate(keys):
+                    if i in per:
+                        for a, t in o.arenas.items():
+                            st.tensor(k, t).copy_(per[i][a].to(self.device, torch.float32))
+                o.step.fill_(optimizers.resumed_step(o.spec, s))
+                continue
             step = 0
             for i, k in enumerate(keys):
                 if i not in per:

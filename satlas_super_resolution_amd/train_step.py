@@ -43,6 +43,10 @@ class StepConfig:
     gan_type: str = "vanilla"      # gan_opt.gan_type: vanilla | lsgan | wgan | wgan_softplus | hinge (basicsr GANLoss; hip.GAN_TYPES)
     pixel_type: str = "L1Loss"     # pixel_opt.type: L1Loss | MSELoss | CharbonnierLoss (basicsr basic_loss.py; hip.PIXEL_KINDS)
     pixel_eps: float = 1e-12       # pixel_opt.eps of CharbonnierLoss
+    # train.optim_g / optim_d beyond plain Adam (optimizers.normalize_optim: {"type": Adam | AdamW | SGD | RMSprop, every constructor
+    # argument}); None: torch.optim.Adam from lr_g / lr_d, betas, eps above - the launches of ssr_adam_step, as ever
+    optim_g: Optional[Dict] = None
+    optim_d: Optional[Dict] = None
     deterministic: bool = False    # fixed-order reductions only: two runs give bit-identical parameters (engine.deterministic; SSR_DETERMINISTIC=1)
 
 
@@ -62,6 +66,8 @@ class AdamState:
         self.store = store
         self.exp_avg = torch.zeros_like(store.data)
         self.exp_avg_sq = torch.zeros_like(store.data)
+        self.arenas = OrderedDict(exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq)     # by torch state key, as optimizers.OptimState
+        self.spec = None                                                                # plain Adam (optimizers.is_plain_adam)
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
         self.lr = torch.full((1,), lr, dtype=torch.float32, device=dev)
         self.ema = store.data.clone() if ema_decay > 0 else None      # model_ema(0): copy of net_g
@@ -87,6 +93,17 @@ class AdamState:
         hip.check(L.ssr_nonfinite_scan(self._scan_src, self._scan_n, 1, self.flag.data_ptr(), st), "ssr_nonfinite_scan")
         hip.check(L.ssr_adam_step_guarded(C.byref(self.args), self.flag.data_ptr(), self.skipped.data_ptr(), st),
                   "ssr_adam_step_guarded")
+
+
+def make_optimizer(store: engine.ParamStore, spec: Optional[Dict], lr: float, betas, eps: float, ema_decay: float, guard: bool):
+    """AdamState (ssr_adam_step) for plain Adam - `spec` None, or Adam without weight decay and amsgrad - and optimizers.OptimState
+    (ssr_optim_step) for everything else StepConfig.optim_g / optim_d can describe."""
+    from . import optimizers
+    if spec is None:
+        return AdamState(store, lr, betas, eps, ema_decay, guard=guard)
+    if optimizers.is_plain_adam(spec):
+        return AdamState(store, spec["lr"], spec["betas"], spec["eps"], ema_decay, guard=guard)
+    return optimizers.OptimState(store, spec, ema_decay, guard=guard)
 
 
 class ESRGANTrainStep:
@@ -183,8 +200,8 @@ class ESRGANTrainStep:
             # runs inside update(), i.e. after every writer of the arena in every path, and under data parallelism after the
             # exchange: NaN / Inf survives the sum, so every rank sees the same flag without a collective of its own
             self.nonfinite_guard = os.environ.get("SSR_NONFINITE_GUARD", "1") != "0"
-            self.opt_g = AdamState(self.g_store, cfg.lr_g, cfg.betas, cfg.eps, cfg.ema_decay, guard=self.nonfinite_guard)
-            self.opt_d = AdamState(self.d_store, cfg.lr_d, cfg.betas_d or cfg.betas, cfg.eps, 0.0, guard=self.nonfinite_guard)
+            self.opt_g = make_optimizer(self.g_store, cfg.optim_g, cfg.lr_g, cfg.betas, cfg.eps, cfg.ema_decay, self.nonfinite_guard)
+            self.opt_d = make_optimizer(self.d_store, cfg.optim_d, cfg.lr_d, cfg.betas_d or cfg.betas, cfg.eps, 0.0, self.nonfinite_guard)
         self._graphs: Dict[str, torch.cuda.CUDAGraph] = {}
         self._warm = set()
         self._side = None
