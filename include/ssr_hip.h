@@ -684,6 +684,84 @@ typedef struct ssr_split_item {
 } ssr_split_item;
 int ssr_split_bf16_multi(const ssr_split_item* items_dev, int32_t n_items, int64_t max_n, void* stream);
 
+/* ---- L2Model's networks: SRCNN and HighResNet (csrc/l2net.hip; additive: the ABI version stays 3) ----
+ * What lies between the convolutions of ssr/archs/srcnn_arch.py and highresnet_arch.py.  The 3 x 3 reflect-padded convolutions
+ * themselves (arch_util.py:89-96,105-112,229-236: padding='same', padding_mode='reflect') run through ssr_conv2d / ssr_conv2d_wgrad
+ * with pad 0 over an (H+2) x (W+2) buffer whose border these kernels fill; their data gradient is the pad-2 full correlation onto
+ * that grid.  SSR_F32 storage only; every view is 16-byte aligned (cs % 4 == 0, coff % 4 == 0) and C % 4 == 0.
+ *
+ * Image mapping (`group`, `fold`; 1, 1 = none): image n = b * group + r of the layer lands in image b * fold + r % fold of the output
+ * buffer, at channels out.coff + (r / fold) * C.  fold 1: the revisits-as-channels view of SRCNN (srcnn_arch.py:183-185); fold =
+ * half the revisits: torch.cat([first_half, second_half], dim=-3) of FusionBlock (arch_util.py:285-297).  Nothing is materialised.
+ *
+ * ssr_prelu_reflect_fwd (arch_util.py:100-102,116-118,171,240: PReLU, Dropout(0.5), x + DoubleConv(x)), per element, each step
+ *   rounded to fp32 in this order:
+ *       v = pre;  v = v > 0 ? v : a * v  (a = slope[0], read on the device);  mask: v = keep ? v * 2 : 0;  res: v = res + v
+ *   written to pixel (y + out_pad, x + out_pad) of the [.., H + 2 out_pad, W + 2 out_pad, out.cs] buffer and, with out_pad = 1, to the
+ *   border pixels that reflect it (edge not repeated: padded row 0 = interior row 1, padded row H + 1 = interior row H - 2), in the
+ *   same launch.  mask: NULL or packed keep bits, bit (e & 31) of word (e >> 5) for element e = ((n H + y) W + x) C + c of `pre`.
+ *   res: optional residual, [N, H + 2 res_pad, W + 2 res_pad, res.cs] read at the interior, image n (not mapped).
+ * ssr_prelu_reflect_bwd: g (and the optional g2, the residual branch's gradient) are gradients laid out like `out` (own pad flags,
+ *   the same image mapping).  Per element, fp32:  t = ONE running sum, started with its first term, of the interior sample and the
+ *   border samples that reflected it, rows in increasing padded row index and, inside a row, columns in increasing padded column
+ *   index (at most 3 x 3 terms, 2 x 2 where H, W >= 4), all of g's terms first, then g2's;  mask: t = keep ? t * 2 : 0;  dpre = pre > 0 ? t : a * t (0 counts as
+ *   negative, as torch);  dslope[0] += sum over all elements of (pre > 0 ? 0 : pre * t): fp64 per-block partials in `partial`
+ *   (SSR_L2_SLOTS doubles of scratch) added in block order by a second launch - no float atomics, the same bytes every run.
+ * SSR_EINVAL without a launch: a null desc / pre / slope / out (fwd) / g, dpre, dslope, partial (bwd), N, C <= 0, H or W < 2, C % 4,
+ *   a misaligned view, a view narrower than coff + C (out / g / g2: coff + ceil(group / fold) * C), group or fold < 1, N % group,
+ *   a pad flag other than 0 | 1. */
+#define SSR_L2_SLOTS 1024
+typedef struct ssr_prelu_reflect_desc {
+    int32_t N, H, W, C;
+    ssr_view pre;
+    const float* slope;
+    const uint32_t* mask;
+    int32_t group, fold;
+    ssr_view out; int32_t out_pad;            /* forward */
+    ssr_view res; int32_t res_pad;
+    ssr_view g; int32_t g_pad;                /* backward */
+    ssr_view g2; int32_t g2_pad;
+    ssr_view dpre;
+    float* dslope;
+    double* partial;
+    ssr_view tsum;                            /* optional [N, H, W, tsum.cs]: receives t before the mask (a chain of residual blocks
+                                                 passes the total gradient of a block's output on to the block before it) */
+} ssr_prelu_reflect_desc;
+int ssr_prelu_reflect_fwd(const ssr_prelu_reflect_desc* d, void* stream);
+int ssr_prelu_reflect_bwd(const ssr_prelu_reflect_desc* d, void* stream);
+/* PixelShuffleBlock (arch_util.py:564-598) with sr_kernel_size 1: PixelShuffle(zoom), conv 1x1 Cm -> Cm (Cm = hidden / zoom^2), PReLU,
+ * conv 1x1 Cm -> Cout, PReLU ('same' reflect padding of a 1 x 1 kernel pads nothing).  x: [N, H, W, hidden]; y, gy: [N, zoom H,
+ * zoom W, cs] with Cout valid channels (the others are never written / read); the shuffle is an index computation:
+ *       u[c] = x[n, Y / zoom, X / zoom, c zoom^2 + (Y % zoom) zoom + X % zoom]
+ * w1 [Cm][Cm], b1 [Cm], s1 [1], w2 [Cout][Cm], b2 [Cout], s2 [1] as the state_dict holds them.  fp32 arithmetic, sums in channel order.
+ * ssr_sr_tail_bwd recomputes the forward from x, writes dx [N, H, W, hidden] (every element exactly once) and ADDS the six parameter
+ * gradients to dw1 .. ds2 (dx.cs must equal x.cs): per-block fp64 partials in `scratch`, added in block order by a second launch (no float atomics).
+ * scratch: ssr_sr_tail_scratch_bytes() bytes, 16-byte aligned, nothing to zero.
+ * SSR_EINVAL: a null pointer, a size <= 0, hidden % zoom^2, a view narrower than its channels; SSR_EUNSUP: Cm > 32 or Cout > 8. */
+typedef struct ssr_sr_tail_desc {
+    int32_t N, H, W, hidden, zoom, Cout;
+    ssr_view x;
+    const float *w1, *b1, *s1, *w2, *b2, *s2;
+    ssr_view y;                               /* forward */
+    ssr_view gy, dx;                          /* backward */
+    float *dw1, *db1, *ds1, *dw2, *db2, *ds2;
+    void* scratch;
+} ssr_sr_tail_desc;
+int ssr_sr_tail_fwd(const ssr_sr_tail_desc* d, void* stream);
+int ssr_sr_tail_bwd(const ssr_sr_tail_desc* d, void* stream);
+int64_t ssr_sr_tail_scratch_bytes(int32_t N, int32_t H, int32_t W, int32_t hidden, int32_t zoom, int32_t Cout);
+/* Dropout(p = 0.5) keep bits (arch_util.py:102,118; torch's own stream is not reproduced, this generator is the promise):
+ * Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (j & 0xffffffff, j >> 32, step[0], layer) gives words 4j .. 4j+3
+ * of `bits`; n_words % 4 == 0.  step is a DEVICE counter (a captured launch replays with the current value); advance = 1 adds 1 to
+ * it behind the mask launch (the last dropout site of a forward).  A null pointer, n_words <= 0 or n_words % 4: SSR_EINVAL. */
+int ssr_dropout_mask(uint32_t* bits, int64_t n_words, uint64_t seed, int32_t* step, int32_t layer, int32_t advance, void* stream);
+/* L2Model's pixel terms in one pass (ssr/models/ssr_l2_model.py:60-84 builds 0.3 mse + 0.4 mae + 0.3 ssim): over npix pixels with C valid
+ * channels, d = a - b, n = npix C:  sums[0] += sum d^2 / n,  sums[1] += sum |d| / n  (fp64 per-block partials in `partial`,
+ * SSR_L2_SLOTS x 2 doubles, added in block order by a second launch);  grad (optional) = w_mse * 2 d / n + w_l1 * sign(d) / n over the
+ * C valid channels, written, not added.  ssr_ssim_loss then adds its term with accumulate = 1. */
+int ssr_mse_l1_loss(ssr_view a, ssr_view b, ssr_view grad, int64_t npix, int32_t C, float w_mse, float w_l1, float* sums,
+                    double* partial, void* stream);
+
 /* library / device info: writes "gfx950 CUs=256 ..." style text */
 int ssr_device_info(char* buf, int32_t buflen);
 int ssr_abi_version(void);

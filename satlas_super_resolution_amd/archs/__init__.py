@@ -5,3 +5,4 @@ import os
 _here = os.path.dirname(os.path.abspath(__file__))
 _arch_modules = [importlib.import_module(f"{__name__}.{f[:-3]}") for f in sorted(os.listdir(_here))
                  if f.endswith("_arch.py")]
+from . import l2_archs  # noqa: E402,F401  SRCNN and HighResNet (one file for both; the name does not end in _arch.py)

@@ -133,6 +133,23 @@ class OptimArgs(C.Structure):
                 ("dampening", C.c_float), ("alpha", C.c_float), ("ema_decay", C.c_float), ("grad_scale", C.c_float)]
 
 
+L2_SLOTS = 1024               # SSR_L2_SLOTS: fp64 partial slots of the L2Model kernels (csrc/l2net.hip)
+
+
+class PreluReflectDesc(C.Structure):
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("pre", View), ("slope", C.c_void_p),
+                ("mask", C.c_void_p), ("group", C.c_int32), ("fold", C.c_int32), ("out", View), ("out_pad", C.c_int32),
+                ("res", View), ("res_pad", C.c_int32), ("g", View), ("g_pad", C.c_int32), ("g2", View), ("g2_pad", C.c_int32),
+                ("dpre", View), ("dslope", C.c_void_p), ("partial", C.c_void_p), ("tsum", View)]
+
+
+class SrTailDesc(C.Structure):
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("hidden", C.c_int32), ("zoom", C.c_int32), ("Cout", C.c_int32),
+                ("x", View), ("w1", C.c_void_p), ("b1", C.c_void_p), ("s1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
+                ("s2", C.c_void_p), ("y", View), ("gy", View), ("dx", View), ("dw1", C.c_void_p), ("db1", C.c_void_p),
+                ("ds1", C.c_void_p), ("dw2", C.c_void_p), ("db2", C.c_void_p), ("ds2", C.c_void_p), ("scratch", C.c_void_p)]
+
+
 # every symbol include/ssr_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "ssr_conv2d", "ssr_conv2d_fixup", "ssr_conv2d_batch", "ssr_conv2d_impl", "ssr_conv2d_variant", "ssr_conv2d_symbol", "ssr_conv2d_chain", "ssr_conv2d_chain_ok", "ssr_conv2d_chain_state_bytes", "ssr_conv2d_ck", "ssr_conv2d_s2d_ok", "ssr_rdb_forward", "ssr_rdb_backward", "ssr_rdb_tile_of", "ssr_conv2d_wgrad", "ssr_wgrad_reduce", "ssr_wgrad_tiles", "ssr_wgrad_ci_tile", "ssr_wgrad_co_tile", "ssr_pack_weights", "ssr_pack_dgrad_gather", "ssr_add_views", "ssr_nchw_to_nhwc", "ssr_nhwc_to_nchw",
@@ -149,6 +166,8 @@ ABI_SYMBOLS = [
     "ssr_scene_support_add", "ssr_scene_apply_nodata",
     "ssr_scene_gather_tf", "ssr_scene_blend_add_tf", "ssr_scene_blend_finish_scaled",
     "ssr_lpips_input", "ssr_lpips_layer_blocks", "ssr_lpips_layer",
+    "ssr_prelu_reflect_fwd", "ssr_prelu_reflect_bwd", "ssr_sr_tail_fwd", "ssr_sr_tail_bwd", "ssr_sr_tail_scratch_bytes",
+    "ssr_dropout_mask", "ssr_mse_l1_loss",
     "ssr_device_info", "ssr_abi_version",
 ]
 SCAN_MAX_RANGES = 8           # SSR_SCAN_MAX_RANGES: ranges per ssr_nonfinite_scan call
@@ -244,10 +263,17 @@ def lib() -> C.CDLL:
     l.ssr_lpips_input.argtypes = [vp, View, i32, i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(i32), i32, vp]
     l.ssr_lpips_layer_blocks.argtypes = [i32, i32, i32]
     l.ssr_lpips_layer.argtypes = [View, View, vp, i32, i32, i32, i32, i32, vp, vp]
+    l.ssr_prelu_reflect_fwd.argtypes = [C.POINTER(PreluReflectDesc), vp]
+    l.ssr_prelu_reflect_bwd.argtypes = [C.POINTER(PreluReflectDesc), vp]
+    l.ssr_sr_tail_fwd.argtypes = [C.POINTER(SrTailDesc), vp]
+    l.ssr_sr_tail_bwd.argtypes = [C.POINTER(SrTailDesc), vp]
+    l.ssr_sr_tail_scratch_bytes.argtypes = [i32, i32, i32, i32, i32, i32]
+    l.ssr_dropout_mask.argtypes = [vp, i64, C.c_uint64, vp, i32, i32, vp]
+    l.ssr_mse_l1_loss.argtypes = [View, View, View, i64, i32, f32, f32, vp, vp, vp]
     l.ssr_device_info.argtypes = [C.c_char_p, i32]
     l.ssr_abi_version.argtypes = []
     for s in ABI_SYMBOLS:
-        getattr(l, s).restype = i64 if s == "ssr_conv2d_chain_state_bytes" else i32
+        getattr(l, s).restype = i64 if s in ("ssr_conv2d_chain_state_bytes", "ssr_sr_tail_scratch_bytes") else i32
     _lib = l
     return l
 
