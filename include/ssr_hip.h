@@ -762,6 +762,41 @@ int ssr_dropout_mask(uint32_t* bits, int64_t n_words, uint64_t seed, int32_t* st
 int ssr_mse_l1_loss(ssr_view a, ssr_view b, ssr_view grad, int64_t npix, int32_t C, float w_mse, float w_l1, float* sums,
                     double* partial, void* stream);
 
+/* ---- SelfAttentionBlock of OSMObjDiscriminator (ssr/archs/osm_obj_discriminator_arch.py:8-31; used at :51,:53,:76,:78) ----
+ * NHWC fp32 views of Bo images of N tokens (token i = h * W + w: the reference's view(B, -1, W * H), :20-21,:25) and C channels,
+ * dk = C / 8.  Weights as the state_dict holds them: wq, wk [dk][C] (query_conv / key_conv .weight, 1x1), wv [C][C], biases, gamma [1].
+ * csrc/attention.hip; exact fp32 arithmetic (plain FMA) whatever the arithmetic mode of the network around it.
+ *   ssr_self_attention_fwd (:16-31):  q = Wq x + bq, k = Wk x + bk, v = Wv x + bv;  e[i][j] = q_i . k_j;  a = softmax_j(e), max-subtracted;
+ *       out_i = sum_j a[i][j] v_j;  y = fma(gamma, out, x).  With `save` set it also stores, per image, a [N][N], q [N][dk], k [N][dk],
+ *       v [N][C], out [N][C] (ssr_self_attention_save_floats(N, C) floats per image): what the backward reads instead of recomputing.
+ *   ssr_self_attention_bwd (autograd's backward of :16-31), from dy and the saved tensors: dx = dy + dq Wq + dk Wk + dv Wv (the residual
+ *       path included), multiplied by relu'(x) = (x > 0) when relu_mask is set (x is the output of the ReLU at :75,:77: dx is then the
+ *       gradient of that layer's pre-activation); and, when the seven gradient pointers are set (all or none), dWq, dbq, dWk, dbk, dWv,
+ *       dbv, dgamma are ADDED to, summed over tokens and images in index order by one writer per element: no float atomics, two runs
+ *       give the same bytes.  dbk is zero in exact arithmetic (a constant added to every key shifts a softmax row uniformly); what is
+ *       added is rounding residue.  scratch: ssr_self_attention_scratch_floats(Bo, N, C) floats, nothing to zero.
+ * SSR_EINVAL without a launch: a null descriptor or required pointer, Bo <= 0, C % 8 != 0, N not in {4, 8, 16, 32, 64}, a view that is
+ * not 16-byte aligned (p, cs % 4, coff % 4) or narrower than coff + C, a weight matrix / save / scratch that is not 16-byte aligned,
+ * some but not all gradient pointers.  SSR_EUNSUP: C % 32 != 0 or C > 256.  Nothing may alias except y == x. */
+typedef struct ssr_attn_desc {
+    int32_t Bo, N, C;
+    ssr_view x;
+    const float *wq, *bq, *wk, *bk, *wv, *bv, *gamma;
+    ssr_view y;                               /* forward */
+    float* save;                              /* forward: optional, written; backward: required, read */
+    ssr_view dy, dx;                          /* backward */
+    int32_t relu_mask;
+    float *dwq, *dbq, *dwk, *dbk, *dwv, *dbv, *dgamma;
+    float* scratch;
+} ssr_attn_desc;
+int ssr_self_attention_fwd(const ssr_attn_desc* d, void* stream);
+int ssr_self_attention_bwd(const ssr_attn_desc* d, void* stream);
+int64_t ssr_self_attention_save_floats(int32_t N, int32_t C);
+int64_t ssr_self_attention_scratch_floats(int32_t Bo, int32_t N, int32_t C);
+/* dst[p, c] = y[p, c] > 0 ? g[p, c] : 0 over C channels of npix pixels of three fp32 views: the gradient of a ReLU's pre-activation
+ * from its output (torch.relu at osm_obj_discriminator_arch.py:79, whose input gradient arrives from outside the plan) */
+int ssr_relu_bwd(ssr_view g, ssr_view y, ssr_view dst, int64_t npix, int32_t C, void* stream);
+
 /* library / device info: writes "gfx950 CUs=256 ..." style text */
 int ssr_device_info(char* buf, int32_t buflen);
 int ssr_abi_version(void);

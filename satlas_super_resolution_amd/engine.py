@@ -3,6 +3,7 @@
 A *plan* is a static list of C-ABI calls (include/ssr_hip.h) over preallocated NHWC device buffers:
   GeneratorPlan      SSR_RRDBNet forward / backward        (/root/reference/ssr/archs/rrdbnet_arch.py:116-137)
   DiscriminatorPlan  SSR_UNetDiscriminatorSN fwd / bwd     (/root/reference/ssr/archs/discriminator_arch.py:42-71)
+  ObjectBranchPlan   OSMObjDiscriminator's object branch   (/root/reference/ssr/archs/osm_obj_discriminator_arch.py:74-79)
 Because shapes are static, a whole plan (or the whole train step built from plans) can be captured in
 one hipGraph.  Dense blocks are concat-free: every RDB owns one [B,H,W,nf+4*gc] buffer, conv_k reads the
 channel prefix and writes its own 32-channel slice; the matching gradient buffer receives dgrad
@@ -52,7 +53,9 @@ class ParamStore:
     Reference key layout: `<conv>.weight`/`.bias`, or `.weight_orig` (+ buffers
     `.weight_u`, `.weight_v`) for spectral-normalised layers."""
 
-    def __init__(self, specs: List[ConvSpec], dtype: int, device="cuda"):
+    def __init__(self, specs: List[ConvSpec], dtype: int, device="cuda", extras=()):
+        """`extras`: (key, shape) of parameters that are not convolutions of the launch plans (the object branch's attention
+        projections and gammas): they get a 16-byte aligned slot behind the convolutions in both arenas and nothing else."""
         self.specs = OrderedDict((s.name, s) for s in specs)
         # modes hip.F32F / hip.F32H: forward convolutions exact fp32 / fp16-split, everything else (storage, backward convolutions, weight gradients) as fp32x3;
         # `dtype` is what the C ABI sees for tensors and backward launches, `fwd_dtype` what forward conv descriptors and the forward
@@ -73,6 +76,9 @@ class ParamStore:
             if s.bias:
                 self.offsets[s.name + ".bias"] = (off, (s.cout,))
                 off += rup(s.cout, 4)
+        for key, shape in extras:
+            self.offsets[key] = (off, tuple(shape))
+            off += rup(math.prod(shape), 4)
         self.numel = off
         self.data = torch.zeros(off, dtype=torch.float32, device=self.device)
         self.grad = torch.zeros(off, dtype=torch.float32, device=self.device)
@@ -1342,5 +1348,142 @@ class DiscriminatorPlan:
         wg3.finalize(); wg4.finalize()
         wg3.launch(L); wg4.launch(L)
         self._keep = getattr(self, "_keep", []) + [wg3, wg4]
+        self._bwd_cache[key] = L
+        return L
+
+
+# =====================================================================================================
+# Object branch of OSMObjDiscriminator
+# =====================================================================================================
+OBJ_ATTENTION = (("o_attention1", 128), ("o_attention2", 256))      # (module, channels): osm_obj_discriminator_arch.py:51,53
+OBJ_SIZES = (16, 32)                                                 # supported H, W of osm_objs
+
+
+def object_branch_specs() -> List[ConvSpec]:
+    """osm_obj_discriminator_arch.py:49-54: biased 4x4 stride-2 convolutions of fixed widths, no spectral norm.  Never the
+    space-to-depth form: the grids are 16 x 16 and smaller."""
+    return [ConvSpec("o_conv1", 64, 3, 4, 2, True, False, s2d=False), ConvSpec("o_conv2", 128, 64, 4, 2, True, False, s2d=False),
+            ConvSpec("o_conv3", 256, 128, 4, 2, True, False, s2d=False), ConvSpec("o_conv4", 1, 256, 4, 2, True, False, s2d=False)]
+
+
+def object_branch_extras():
+    """the parameters of the two SelfAttentionBlocks (:11-14) in state_dict order: ParamStore `extras`"""
+    out = []
+    for name, c in OBJ_ATTENTION:
+        out.append((f"{name}.gamma", (1,)))
+        for conv, co in (("query_conv", c // 8), ("key_conv", c // 8), ("value_conv", c)):
+            out.append((f"{name}.{conv}.weight", (co, c, 1, 1)))
+            out.append((f"{name}.{conv}.bias", (co,)))
+    return out
+
+
+class ObjectBranchPlan:
+    """The object branch of OSMObjDiscriminator (osm_obj_discriminator_arch.py:74-79) on NHWC fp32 buffers for a fixed (Bo, H, W):
+    relu(o_conv1), relu(o_conv2), o_attention1, relu(o_conv3), o_attention2, relu(o_conv4).
+
+    `store` is a ParamStore(object_branch_specs(), hip.F32, extras=object_branch_extras()): the branch runs in exact fp32 in every
+    arithmetic mode of the network around it.  It is a few MFLOP per crop - launches and latency, not arithmetic - and the ReLU
+    epilogue and the ReLU' mask exist in the pipelined fp32 convolution kernel (csrc/conv_epilogue.h), which serves all four
+    shapes (3 input channels padded to 8, one output channel padded to 32) without a change to the dispatch.
+    fwd: 4 convolutions + 2 ssr_self_attention_fwd.  bwd (from d_out, the NHWC gradient of o_out): ssr_relu_bwd, then per layer
+    the data gradient (four parity classes, ssr_conv2d_batch) and, with param_grads, ssr_self_attention_bwd's parameter part and
+    ONE batched ssr_conv2d_wgrad at the end.  g_in receives the gradient w.r.t. osm_objs (the generator phase needs it)."""
+
+    def __init__(self, store: ParamStore, Bo: int, H: int, W: int, training=True):
+        if H not in OBJ_SIZES or W not in OBJ_SIZES:
+            raise ValueError(f"osm_objs of {H} x {W}: the object branch supports H, W in {OBJ_SIZES}")
+        assert store.dtype == hip.F32 and store.fwd_dtype == hip.F32, "the object branch's store is exact fp32"
+        self.store, self.Bo, self.H, self.W, self.dt = store, Bo, H, W, hip.F32
+        self.det = deterministic()
+        dev = store.device
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        hs = [(H >> k, W >> k) for k in range(5)]
+        self.hs = hs
+        self.xin = z(Bo, H, W, 8)
+        self.o1, self.o2, self.a1 = z(Bo, *hs[1], 64), z(Bo, *hs[2], 128), z(Bo, *hs[2], 128)
+        self.o3, self.a2, self.out = z(Bo, *hs[3], 256), z(Bo, *hs[3], 256), z(Bo, *hs[4], 8)
+        lib = hip.lib()
+        self.training = training
+        self._cb = cb = _ConvBuilder(store, Bo)
+        self._attn = []
+        F = Launcher()
+        RELU = hip.ACT_RELU
+        cb.conv(F, "o_conv1", view(self.xin), H, W, view(self.o1), act=RELU, cin=8)
+        cb.conv(F, "o_conv2", view(self.o1), *hs[1], view(self.o2), act=RELU)
+        d1 = self._attention(F, "o_attention1", 128, self.o2, self.a1, hs[2][0] * hs[2][1])
+        cb.conv(F, "o_conv3", view(self.a1), *hs[2], view(self.o3), act=RELU)
+        d2 = self._attention(F, "o_attention2", 256, self.o3, self.a2, hs[3][0] * hs[3][1])
+        cb.conv(F, "o_conv4", view(self.a2), *hs[3], view(self.out), act=RELU)
+        self.fwd = F
+        self._bwd_cache: Dict[Tuple[bool, bool], Launcher] = {}
+        if not training:
+            return
+        self.d_out = z(Bo, *hs[4], 8)                    # dL/d o_out, channel 0 (the caller fills it)
+        self.g_out = z(Bo, *hs[4], 8)
+        self.g_a2, self.g_o3 = z(Bo, *hs[3], 256), z(Bo, *hs[3], 256)
+        self.g_a1, self.g_o2 = z(Bo, *hs[2], 128), z(Bo, *hs[2], 128)
+        self.g_o1, self.g_in = z(Bo, *hs[1], 64), z(Bo, H, W, 8)
+        for d, dy, dx in ((d1, self.g_a1, self.g_o2), (d2, self.g_a2, self.g_o3)):
+            d.dy, d.dx, d.relu_mask = view(dy), view(dx), 1          # x is a ReLU's output: dx is its pre-activation's gradient
+            d._scratch = z(int(lib.ssr_self_attention_scratch_floats(Bo, d.N, d.C)))
+            d.scratch = d._scratch.data_ptr()
+
+    def _attention(self, L: Launcher, name: str, c: int, x: torch.Tensor, y: torch.Tensor, n: int):
+        st, lib = self.store, hip.lib()
+        d = hip.AttnDesc()
+        d.Bo, d.N, d.C, d.x, d.y = self.Bo, n, c, view(x), view(y)
+        d.wq, d.bq = st.ptr(f"{name}.query_conv.weight"), st.ptr(f"{name}.query_conv.bias")
+        d.wk, d.bk = st.ptr(f"{name}.key_conv.weight"), st.ptr(f"{name}.key_conv.bias")
+        d.wv, d.bv = st.ptr(f"{name}.value_conv.weight"), st.ptr(f"{name}.value_conv.bias")
+        d.gamma = st.ptr(f"{name}.gamma")
+        if self.training:
+            d._save = torch.zeros(self.Bo * int(lib.ssr_self_attention_save_floats(n, c)), dtype=torch.float32, device=st.device)
+            d.save = d._save.data_ptr()
+        d._name = name
+        self._attn.append(d)
+        L.add(lib.ssr_self_attention_fwd, C.byref(d), what=f"self-attention fwd {name}")
+        return d
+
+    def backward_plan(self, param_grads: bool, input_grad: bool) -> Launcher:
+        key = (bool(param_grads), bool(input_grad))
+        if key in self._bwd_cache:
+            return self._bwd_cache[key]
+        cb, st, Bo, hs, lib = self._cb, self.store, self.Bo, self.hs, hip.lib()
+        L = Launcher()
+        wg = WgradBatch(hip.F32, 4, 2, det=self.det)
+
+        def add_wg(name, x, dy, hw_in, hw_out, cin=None):
+            if not param_grads:
+                return
+            s = st.specs[name]
+            wg.add(x, dy, Bo, hw_in[0], hw_in[1], 1, rup(s.cin, 8) if cin is None else cin, s.cout, hw_out[0], hw_out[1], 1.0,
+                   st.ptr(name + ".weight", st.grad), s.cin, st.ptr(name + ".bias", st.grad))
+
+        def attention_bwd(d):
+            e = hip.AttnDesc()
+            C.memmove(C.byref(e), C.byref(d), C.sizeof(hip.AttnDesc))
+            if param_grads:
+                g = lambda k: st.ptr(f"{d._name}.{k}", st.grad)
+                e.dwq, e.dbq, e.dwk, e.dbk = g("query_conv.weight"), g("query_conv.bias"), g("key_conv.weight"), g("key_conv.bias")
+                e.dwv, e.dbv, e.dgamma = g("value_conv.weight"), g("value_conv.bias"), g("gamma")
+            cb.keep.append(e)
+            L.add(lib.ssr_self_attention_bwd, C.byref(e), what=f"self-attention bwd {d._name}")
+
+        d1, d2 = self._attn
+        L.add(lib.ssr_relu_bwd, view(self.d_out), view(self.out), view(self.g_out), Bo * hs[4][0] * hs[4][1], 1, what="relu bwd o_out")
+        add_wg("o_conv4", view(self.a2), view(self.g_out), hs[3], hs[4])
+        cb.dgrad(L, "o_conv4", view(self.g_out), *hs[4], view(self.g_a2))
+        attention_bwd(d2)
+        add_wg("o_conv3", view(self.a1), view(self.g_o3), hs[2], hs[3])
+        cb.dgrad(L, "o_conv3", view(self.g_o3), *hs[3], view(self.g_a1))
+        attention_bwd(d1)
+        add_wg("o_conv2", view(self.o1), view(self.g_o2), hs[1], hs[2])
+        cb.dgrad(L, "o_conv2", view(self.g_o2), *hs[2], view(self.g_o1), m=view(self.o1), m_c0=0, m_c1=64, m_relu=1)
+        add_wg("o_conv1", view(self.xin), view(self.g_o1), hs[0], hs[1], cin=8)
+        if input_grad:
+            cb.dgrad(L, "o_conv1", view(self.g_o1), *hs[1], view(self.g_in), cout=8, cin_dy=64)
+        wg.finalize()
+        wg.launch(L)
+        self._keep = getattr(self, "_keep", []) + [wg]
         self._bwd_cache[key] = L
         return L

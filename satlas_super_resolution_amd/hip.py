@@ -150,6 +150,14 @@ class SrTailDesc(C.Structure):
                 ("ds1", C.c_void_p), ("dw2", C.c_void_p), ("db2", C.c_void_p), ("ds2", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class AttnDesc(C.Structure):
+    _fields_ = [("Bo", C.c_int32), ("N", C.c_int32), ("C", C.c_int32), ("x", View),
+                ("wq", C.c_void_p), ("bq", C.c_void_p), ("wk", C.c_void_p), ("bk", C.c_void_p), ("wv", C.c_void_p), ("bv", C.c_void_p),
+                ("gamma", C.c_void_p), ("y", View), ("save", C.c_void_p), ("dy", View), ("dx", View), ("relu_mask", C.c_int32),
+                ("dwq", C.c_void_p), ("dbq", C.c_void_p), ("dwk", C.c_void_p), ("dbk", C.c_void_p), ("dwv", C.c_void_p), ("dbv", C.c_void_p),
+                ("dgamma", C.c_void_p), ("scratch", C.c_void_p)]
+
+
 # every symbol include/ssr_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "ssr_conv2d", "ssr_conv2d_fixup", "ssr_conv2d_batch", "ssr_conv2d_impl", "ssr_conv2d_variant", "ssr_conv2d_symbol", "ssr_conv2d_chain", "ssr_conv2d_chain_ok", "ssr_conv2d_chain_state_bytes", "ssr_conv2d_ck", "ssr_conv2d_s2d_ok", "ssr_rdb_forward", "ssr_rdb_backward", "ssr_rdb_tile_of", "ssr_conv2d_wgrad", "ssr_wgrad_reduce", "ssr_wgrad_tiles", "ssr_wgrad_ci_tile", "ssr_wgrad_co_tile", "ssr_pack_weights", "ssr_pack_dgrad_gather", "ssr_add_views", "ssr_nchw_to_nhwc", "ssr_nhwc_to_nchw",
@@ -168,6 +176,7 @@ ABI_SYMBOLS = [
     "ssr_lpips_input", "ssr_lpips_layer_blocks", "ssr_lpips_layer",
     "ssr_prelu_reflect_fwd", "ssr_prelu_reflect_bwd", "ssr_sr_tail_fwd", "ssr_sr_tail_bwd", "ssr_sr_tail_scratch_bytes",
     "ssr_dropout_mask", "ssr_mse_l1_loss",
+    "ssr_self_attention_fwd", "ssr_self_attention_bwd", "ssr_self_attention_save_floats", "ssr_self_attention_scratch_floats", "ssr_relu_bwd",
     "ssr_device_info", "ssr_abi_version",
 ]
 SCAN_MAX_RANGES = 8           # SSR_SCAN_MAX_RANGES: ranges per ssr_nonfinite_scan call
@@ -270,10 +279,16 @@ def lib() -> C.CDLL:
     l.ssr_sr_tail_scratch_bytes.argtypes = [i32, i32, i32, i32, i32, i32]
     l.ssr_dropout_mask.argtypes = [vp, i64, C.c_uint64, vp, i32, i32, vp]
     l.ssr_mse_l1_loss.argtypes = [View, View, View, i64, i32, f32, f32, vp, vp, vp]
+    l.ssr_self_attention_fwd.argtypes = [C.POINTER(AttnDesc), vp]
+    l.ssr_self_attention_bwd.argtypes = [C.POINTER(AttnDesc), vp]
+    l.ssr_self_attention_save_floats.argtypes = [i32, i32]
+    l.ssr_self_attention_scratch_floats.argtypes = [i32, i32, i32]
+    l.ssr_relu_bwd.argtypes = [View, View, View, i64, i32, vp]
     l.ssr_device_info.argtypes = [C.c_char_p, i32]
     l.ssr_abi_version.argtypes = []
     for s in ABI_SYMBOLS:
-        getattr(l, s).restype = i64 if s in ("ssr_conv2d_chain_state_bytes", "ssr_sr_tail_scratch_bytes") else i32
+        getattr(l, s).restype = i64 if s in ("ssr_conv2d_chain_state_bytes", "ssr_sr_tail_scratch_bytes", "ssr_self_attention_save_floats",
+                                              "ssr_self_attention_scratch_floats") else i32
     _lib = l
     return l
 
