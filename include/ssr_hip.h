@@ -162,7 +162,7 @@ int ssr_conv2d_chain(const ssr_conv_desc* ds, int32_t n, void* state, void* stre
 int ssr_conv2d_chain_ok(const ssr_conv_desc* ds, int32_t n);
 int64_t ssr_conv2d_chain_state_bytes(int32_t N, int32_t Gh, int32_t Gw);
 /* The kernel symbol ssr_conv2d launches for this descriptor as rocprofv3 prints it (without the "void (anonymous namespace)::" prefix and
- * the argument list), e.g. "conv_x3r_kernel<1, 0>": the key under which bench.py, tools/pmc_traffic.py, tools/pmc_sq.py and
+ * the argument list), e.g. "conv_x3r_kernel<1, 1, 0, 8, 2>" (NTW, NU, EP, TH, AM): the key under which bench.py, tools/pmc_traffic.py, tools/pmc_sq.py and
  * tools/roofline_check.py file a launch, so that roofline.kernel can be found in profiles/ by name.  buflen >= 48. */
 int ssr_conv2d_symbol(const ssr_conv_desc* d, char* buf, int32_t buflen);
 /* input channels per packed weight chunk for a KHxKH kernel in `dtype` */

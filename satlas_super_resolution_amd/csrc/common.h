@@ -107,6 +107,14 @@ inline int ssr_device_ordinal() {
     return dev;
 }
 
+// environment switches.  ssr_env_off / _on / _int: for `static const` initialisers, a switch read ONCE per process;
+// ssr_env_now: a test hook read on EVERY call (tests set SSR_CONV_BIG_G, SSR_CONV_BIGTILE2, SSR_X3_BIGTILE2 in-process)
+#include <cstdlib>
+inline bool ssr_env_off(const char* name) { const char* e = getenv(name); return e && e[0] == '0'; }
+inline bool ssr_env_on(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
+inline int ssr_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline const char* ssr_env_now(const char* name) { return getenv(name); }
+
 #define SSR_LAUNCH_CHECK()                       \
     do {                                         \
         hipError_t e__ = hipGetLastError();      \

@@ -20,8 +20,7 @@
 // nearest x2 upsampling (:127-128), the U-Net skip adds (discriminator_arch.py:53-64) and the
 // corresponding backward masks / gradient fan-in sums folded into the load and the epilogue.
 #include "conv_epilogue.h"
-#include <cstdlib>
-#include <cstdio>
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -284,20 +283,31 @@ int launch_conv(const ssr_conv_desc& d, hipStream_t st) {
     return SSR_OK;
 }
 
-// BN = 64 when the padded output width allows it; small problems use 4x16-pixel tiles (MW = 2) so
-// that there are at least as many workgroups as CUs.
-inline void pick_tile(const ssr_conv_desc& d, bool& nt2, bool& small) {
-    nt2 = (d.CoutPad % 64) == 0;
-    const long tiles4 = (long)((d.Gw + 15) / 16) * ((d.Gh + 7) / 8) * d.N * (d.CoutPad / (nt2 ? 64 : 32));
-    small = tiles4 < 384;
+// The pipelined family's one pick, for its launches, ssr_conv2d_batch and the reports.  nt2: BN = 64 when the padded output width
+// allows it.  small: 4x16-pixel tiles (MW = 2) when the `nlaunch` descriptors of the launch make fewer than 384 8x16 tiles (at least
+// as many workgroups as CUs); the split kernels keep the 8x16 tile - their weight slab (hi + lo planes, converted by every workgroup)
+// costs as much to stage as 288 pixel rows: r02m, fp32x3 step at B = 32, 45.3 ms with that threshold, 38.1 ms without small tiles,
+// 60.0 ms with them everywhere (SSR_X3_SMALL = their threshold, tuning hook).  deep: 0, or the chunks per stage of the opt-in
+// conv_x3p_kernel (2 at 32 output channels, SSR_X3_PIPE=1; 1 at 64, SSR_X3_PIPE2=1 as well: r05b 10.4 vs 9.6 ms per step).
+struct conv_tile_pick { bool nt2, small; int deep; };
+bool x3p_ok(const ssr_conv_desc& d, int cps);
+inline conv_tile_pick pick_tile(const ssr_conv_desc& d, int nlaunch = 1) {
+    static const long x3_small = ssr_env_int("SSR_X3_SMALL", 0);
+    static const bool p2 = ssr_env_on("SSR_X3_PIPE2");
+    const bool split = d.dtype == SSR_F32X3 || d.dtype == SSR_F32H;
+    conv_tile_pick p;
+    p.nt2 = (d.CoutPad % 64) == 0;
+    const long tiles4 = (long)((d.Gw + 15) / 16) * ((d.Gh + 7) / 8) * d.N * (d.CoutPad / (p.nt2 ? 64 : 32)) * nlaunch;
+    p.small = tiles4 < (split ? x3_small : 384L);
+    p.deep = (d.dtype != SSR_F32X3 || p.small) ? 0 : (p.nt2 && p2 && x3p_ok(d, 1)) ? 1 : (!p.nt2 && x3p_ok(d, 2)) ? 2 : 0;
+    return p;
 }
 
 template <typename T, int KH, int KW, int S>
 int dispatch_tile(const ssr_conv_desc& d, hipStream_t st) {
-    bool nt2, small;
-    pick_tile(d, nt2, small);
-    if (nt2) return small ? launch_conv<T, KH, KW, S, 2, 2, 2>(d, st) : launch_conv<T, KH, KW, S, 2, 4, 2>(d, st);
-    return small ? launch_conv<T, KH, KW, S, 1, 2, 2>(d, st) : launch_conv<T, KH, KW, S, 1, 4, 2>(d, st);
+    const conv_tile_pick p = pick_tile(d);
+    if (p.nt2) return p.small ? launch_conv<T, KH, KW, S, 2, 2, 2>(d, st) : launch_conv<T, KH, KW, S, 2, 4, 2>(d, st);
+    return p.small ? launch_conv<T, KH, KW, S, 1, 2, 2>(d, st) : launch_conv<T, KH, KW, S, 1, 4, 2>(d, st);
 }
 
 template <typename T>
@@ -839,7 +849,7 @@ bool x3p_ok(const ssr_conv_desc& d, int cps) {
     // MFMA phase takes 2.7 k ticks for 1.7 k of MFMAs, the split + LDS store 1.2 k, the barrier 0.7 k, and neither deeper load
     // prefetch nor riding the store inside the MFMA stream changes the sum (a wave's VALU / LDS-store work does not overlap its own
     // MFMAs); a launch carries ~11.7 k ticks of fixed parts (set-up 1.7 k, first loads 4.8 k, reduce + epilogue 5.2 k).
-    static const bool on = [] { const char* e = getenv("SSR_X3_PIPE"); return e && e[0] == '1'; }();
+    static const bool on = ssr_env_on("SSR_X3_PIPE");
     if (!on) return false;
     const long lim = 0x7fffff00L, npx = (long)d.N * d.Hi * d.Wi * 4;
     if (npx * d.x.cs > lim || (d.x2.p && npx * d.x2.cs > lim)) return false;
@@ -849,58 +859,90 @@ bool x3p_ok(const ssr_conv_desc& d, int cps) {
 
 template <int KH, int KW, bool H = false>
 int dispatch_tile_x3(const ssr_conv_desc& d, hipStream_t st) {
-    bool nt2, small;
-    pick_tile(d, nt2, small);
-    // The split kernel always takes the 8x16-pixel workgroup tile: its weight slab (hi + lo planes, converted by every workgroup)
-    // costs as much to stage as 288 pixel rows, so halving the pixels per workgroup the way the plain kernels do for small
-    // grids doubles that share.  r02m, whole fp32x3 step at B = 32: 45.3 ms with the plain kernels' threshold (384 tiles),
-    // 38.1 ms without small tiles, 60.0 ms with small tiles everywhere.  SSR_X3_SMALL = threshold in 8x16 tiles (tuning hook).
-    static const long thr = [] { const char* e = getenv("SSR_X3_SMALL"); return e ? atol(e) : 0L; }();
-    small = (long)((d.Gw + 15) / 16) * ((d.Gh + 7) / 8) * d.N * (d.CoutPad / (nt2 ? 64 : 32)) < thr;
-    if (!small && !H) {      // round 5: deep load pipeline (two chunks per stage at 32 output channels, three register stages at 64)
-        static const bool p2 = [] { const char* e = getenv("SSR_X3_PIPE2"); return e && e[0] == '1'; }();   // 64 output channels: measured slower than the plain pipeline (r05b: 10.4 vs 9.6 ms per step), opt-in
-        if (nt2 && p2 && x3p_ok(d, 1)) return launch_conv_x3p<KH, KW, 2, 4, 2, 1, 3>(d, st);
-        if (!nt2 && x3p_ok(d, 2)) return launch_conv_x3p<KH, KW, 1, 4, 2, 2, 2>(d, st);
-    }
-    if (nt2) return small ? launch_conv_x3<KH, KW, 2, 2, 2, H>(d, st) : launch_conv_x3<KH, KW, 2, 4, 2, H>(d, st);
-    return small ? launch_conv_x3<KH, KW, 1, 2, 2, H>(d, st) : launch_conv_x3<KH, KW, 1, 4, 2, H>(d, st);
+    const conv_tile_pick p = pick_tile(d);
+    if (p.deep == 1) return launch_conv_x3p<KH, KW, 2, 4, 2, 1, 3>(d, st);
+    if (p.deep == 2) return launch_conv_x3p<KH, KW, 1, 4, 2, 2, 2>(d, st);
+    if (p.nt2) return p.small ? launch_conv_x3<KH, KW, 2, 2, 2, H>(d, st) : launch_conv_x3<KH, KW, 2, 4, 2, H>(d, st);
+    return p.small ? launch_conv_x3<KH, KW, 1, 2, 2, H>(d, st) : launch_conv_x3<KH, KW, 1, 4, 2, H>(d, st);
 }
+
+// ---- the pipelined family: the kernels of this file, the end of every candidate list ----
+bool pipe_shape_ok(const ssr_conv_desc& d) {
+    const bool s1 = (d.KH == 3 && d.KW == 3 && d.stride == 1) || (d.KH == 2 && d.KW == 2 && d.stride == 1);
+    if (d.dtype == SSR_F32X3 || d.dtype == SSR_F32H) return s1;          // (their 4x4 stride-2 layers arrive as SSR_F32: select)
+    return (d.dtype == SSR_F32 || d.dtype == SSR_BF16) && (s1 || (d.KH == 4 && d.KW == 4 && d.stride == 2));
+}
+int pipe_launch(const ssr_conv_desc& d, hipStream_t st) {
+    if (d.dtype == SSR_F32H) return d.KH == 3 ? dispatch_tile_x3<3, 3, true>(d, st) : dispatch_tile_x3<2, 2, true>(d, st);
+    if (d.dtype == SSR_F32) return dispatch_geom<float>(d, st);
+    if (d.dtype == SSR_F32X3) return d.KH == 3 ? dispatch_tile_x3<3, 3>(d, st) : dispatch_tile_x3<2, 2>(d, st);
+    return dispatch_geom<__bf16>(d, st);
+}
+int pipe_code(const ssr_conv_desc& d) {
+    const conv_tile_pick p = pick_tile(d);
+    return (p.nt2 ? 2 : 1) * 10 + (p.small ? 2 : 4);
+}
+void pipe_symbol(const ssr_conv_desc& d, int v, char* buf, int buflen) {
+    const char* kernel = pick_tile(d).deep ? "conv_x3p_kernel" : d.dtype == SSR_F32X3 ? "conv_x3_kernel" : d.dtype == SSR_F32H ? "conv_h3_kernel" : "conv_kernel";
+    ssr_conv_symbol_coded(kernel, d, v, buf, buflen);
+}
+ssr_conv_family conv_pipelined = {"pipelined", 3, pipe_shape_ok, pipe_shape_ok, pipe_launch, pipe_code, pipe_symbol};
 
 bool view_ok(const ssr_view& v, bool required) {
     if (!v.p) return !required;
     return (v.cs % 8) == 0 && (v.coff % 8) == 0 && ((uintptr_t)v.p % 16) == 0;
 }
 
+bool desc_valid(const ssr_conv_desc& d) {
+    if (d.act < SSR_ACT_NONE || d.act > SSR_ACT_RELU || !view_ok(d.x, true) || !d.w || ((uintptr_t)d.w % 16) != 0 || !d.y.p || d.y.cs <= 0) return false;
+    if (d.Cin <= 0 || (d.Cin % 8) != 0 || d.CoutPad <= 0 || (d.CoutPad % 32) != 0 || d.Cout > d.CoutPad) return false;
+    if (!(d.up == 1 || d.up == 2) || d.N <= 0 || d.Gh <= 0 || d.Gw <= 0) return false;
+    if (d.x2.p && (d.Cin2 <= 0 || (d.Cin2 % 8) != 0 || !view_ok(d.x2, true))) return false;
+    return d.x2.p || d.Cin2 == 0;
+}
+
+// ---- the dispatch table: per dtype class the families in the order they are tried; the first that qualifies runs ----
+// (every list ends with the pipelined family; ws and big refuse fp32 by shape, so that forcing them there stays SSR_EUNSUP)
+const ssr_conv_family* const LIST_F32H[] = {&ssr_conv_thin, &ssr_conv_bigx3, &ssr_conv_x3r, &conv_pipelined};
+const ssr_conv_family* const LIST_F32X3[] = {&ssr_conv_thin, &ssr_conv_bigx3, &ssr_conv_x3r, &ssr_conv_x3q, &conv_pipelined};
+const ssr_conv_family* const LIST_F32[] = {&ssr_conv_thin, &ssr_conv_ws, &ssr_conv_big, &ssr_conv_x3r, &ssr_conv_res, &conv_pipelined};
+const ssr_conv_family* const LIST_BF16[] = {&ssr_conv_thin, &ssr_conv_ws, &ssr_conv_big, &ssr_conv_res, &conv_pipelined};
+
+// The family that runs `in` under ssr_conv2d_impl code `impl`, and the descriptor `d` it is launched with.  SSR_OK, or the code
+// ssr_conv2d returns without a launch.
+int select(const ssr_conv_desc& in, int impl, const ssr_conv_family*& fam, ssr_conv_desc& d) {
+    d = in;
+    const bool split = d.dtype == SSR_F32X3 || d.dtype == SSR_F32H;
+    if (d.s2d) {   // 4x4 stride 2 through the space-to-depth view: a 2x2 stride-1 layer of 4*Cin channels on the big-tile kernel
+        if (!(d.KH == 4 && d.KW == 4 && d.stride == 2 && d.pad_y == 1 && d.pad_x == 1 && d.up == 1 && !d.x2.p)) return SSR_EINVAL;
+        if (!ssr_conv2d_s2d_ok(d.dtype, d.Cin, d.Cout, d.CoutPad) || (d.Hi % 2) || (d.Wi % 2) || d.Gh != d.Hi / 2 || d.Gw != d.Wi / 2)
+            return SSR_EINVAL;
+        d.KH = d.KW = 2; d.stride = 1; d.pad_y = d.pad_x = 0; d.Cin = 4 * in.Cin;
+        fam = split ? &ssr_conv_bigx3 : &ssr_conv_big;
+        return fam->shape_ok(d) ? SSR_OK : SSR_EUNSUP;
+    }
+    if (d.dtype == SSR_F32H && d.fix_list) return SSR_EUNSUP;          // (the fix-up belongs to the split-bf16 mode)
+    // ReLU epilogues (the VGG19 layers) exist only in the pipelined kernel outside the split modes (conv_epilogue.h)
+    if (!split && (d.act == SSR_ACT_RELU || d.m_relu)) impl = 3;
+    const ssr_conv_family* const* list = d.dtype == SSR_F32H ? LIST_F32H : d.dtype == SSR_F32X3 ? LIST_F32X3 : d.dtype == SSR_F32 ? LIST_F32 : LIST_BF16;
+    if (impl != 0 && impl != 3)                                       // a code that names a family of the list forces it
+        for (const ssr_conv_family* const* f = list; *f != &conv_pipelined; ++f)
+            if ((fam = *f)->impl == impl) return fam->shape_ok(d) ? SSR_OK : SSR_EUNSUP;
+    // 0: the first family that qualifies; 3: the pipelined kernel; any other code: of the families that cannot be forced
+    for (const ssr_conv_family* const* f = list; *f != &conv_pipelined; ++f)
+        if ((impl == 0 || (impl != 3 && (*f)->impl < 0)) && (fam = *f)->qualifies(d)) return SSR_OK;
+    fam = &conv_pipelined;
+    // 4x4 stride 2 in a split mode without the space-to-depth view: rows of 8 are plain fp32 (misc.hip put_packed), the exact kernel
+    if (split && !((d.KH == 3 && d.KW == 3 && d.stride == 1) || (d.KH == 2 && d.KW == 2 && d.stride == 1))) d.dtype = SSR_F32;
+    return fam->shape_ok(d) ? SSR_OK : SSR_EUNSUP;
+}
+
 }  // namespace
 
-// K-resident LDS-DMA kernel for the small generator-body layers (conv_res.hip)
-bool ssr_conv_res_try(const ssr_conv_desc& d, hipStream_t st, int* rc);
-bool ssr_conv_res_qualifies(const ssr_conv_desc& d);
-// weight-stationary persistent kernel for the large-spatial layers (conv_ws.hip)
-bool ssr_conv_ws_try(const ssr_conv_desc& d, hipStream_t st, int* rc, bool force);
-bool ssr_conv_ws_qualifies(const ssr_conv_desc& d);
-// thin-output VALU kernel for the logit / RGB heads (conv_thin.hip)
-bool ssr_conv_thin_try(const ssr_conv_desc& d, hipStream_t st, int* rc, bool force);
-bool ssr_conv_thin_qualifies(const ssr_conv_desc& d);
-// big-tile kernel for the wide discriminator layers (conv_big.hip)
-bool ssr_conv_big_try(const ssr_conv_desc& d, hipStream_t st, int* rc, bool force);
-bool ssr_conv_big_qualifies(const ssr_conv_desc& d);
-bool ssr_conv_big_batch_try(const ssr_conv_desc* ds, int n, hipStream_t st, int* rc);
-// big-tile kernel of the split-bf16 mode (conv_big_x3.hip)
-bool ssr_conv_bigx3_try(const ssr_conv_desc& d, hipStream_t st, int* rc, bool force);
-bool ssr_conv_bigx3_qualifies(const ssr_conv_desc& d);
-bool ssr_conv_bigx3_batch_try(const ssr_conv_desc* ds, int n, hipStream_t st, int* rc);
-// producer / MFMA-wave ring kernel of the split-bf16 mode for small grids (conv_x3q.hip)
-bool ssr_conv_x3q_try(const ssr_conv_desc& d, hipStream_t st, int* rc, bool force);
-bool ssr_conv_x3q_qualifies(const ssr_conv_desc& d);
-// register-tiled kernel of the split-bf16 mode for small grids, round 6 (conv_x3r.hip): takes the ring kernel's layers
-bool ssr_conv_x3r_try(const ssr_conv_desc& d, hipStream_t st, int* rc, bool force);
-bool ssr_conv_x3r_qualifies(const ssr_conv_desc& d);
-
 extern "C" int ssr_conv2d_s2d_ok(int32_t dtype, int32_t Cin, int32_t Cout, int32_t CoutPad) {
-    static const bool off = [] { const char* e = getenv("SSR_CONV_S2D"); return e && e[0] == '0'; }();
+    static const bool off = ssr_env_off("SSR_CONV_S2D");
     if (dtype == SSR_F32X3 || dtype == SSR_F32H) {   // split modes: 16-channel chunks (conv_big_x3.hip)
-        static const bool offx = [] { const char* e = getenv("SSR_X3_BIGTILE"); return e && e[0] == '0'; }();
+        static const bool offx = ssr_env_off("SSR_X3_BIGTILE");
         const int cpx = Cin / 16;
         return !off && !offx && Cin >= 16 && (Cin % 16) == 0 && (cpx & (cpx - 1)) == 0 && (CoutPad % 64) == 0 && (Cout % 8) == 0;
     }
@@ -910,56 +952,21 @@ extern "C" int ssr_conv2d_s2d_ok(int32_t dtype, int32_t Cin, int32_t Cout, int32
 
 extern "C" int ssr_conv2d_variant(const ssr_conv_desc* dp) {
     if (!dp) return SSR_EINVAL;
-    if (dp->s2d) return dp->KH * 1000 + dp->stride * 100 + 2 * 10 + 9;
-    // ReLU epilogues (the VGG19 layers) exist only in the pipelined kernel outside the split-bf16 mode: conv2d_impl forces it (impl = 3)
-    const bool split = dp->dtype == SSR_F32X3 || dp->dtype == SSR_F32H;
-    const bool pipelined_only = !split && (dp->act == SSR_ACT_RELU || dp->m_relu);
-    if (!pipelined_only) {
-        if (dp->dtype != SSR_BF16 && ssr_conv_thin_qualifies(*dp)) return dp->KH * 1000 + dp->stride * 100 + 1 * 10 + 7;        // digit 7 = thin-output VALU kernel
-        if (split && ssr_conv_bigx3_qualifies(*dp)) return dp->KH * 1000 + dp->stride * 100 + 2 * 10 + 9;   // digit 9 = big tile
-        if (split && ssr_conv_x3r_qualifies(*dp))
-            return dp->KH * 1000 + dp->stride * 100 + ((dp->CoutPad % 64) == 0 ? 2 : 1) * 10 + 5;                              // digit 5 = register-tiled, K split over four waves (conv_x3r.hip)
-        if (dp->dtype == SSR_F32X3 && ssr_conv_x3q_qualifies(*dp))
-            return dp->KH * 1000 + dp->stride * 100 + ((dp->CoutPad % 64) == 0 ? 2 : 1) * 10 + 6;                              // digit 6 = twelve-wave ring (conv_x3q.hip)
-        if (!split) {
-            if (ssr_conv_thin_qualifies(*dp)) return dp->KH * 1000 + dp->stride * 100 + 1 * 10 + 7;  // digit 7 = thin-output VALU kernel
-            if (ssr_conv_ws_qualifies(*dp)) return dp->KH * 1000 + dp->stride * 100 + 1 * 10 + 8;    // digit 8 = weight-stationary
-            if (ssr_conv_big_qualifies(*dp)) return dp->KH * 1000 + dp->stride * 100 + 2 * 10 + 9;   // digit 9 = big tile
-            if (dp->dtype == SSR_F32 && ssr_conv_x3r_qualifies(*dp))
-                return dp->KH * 1000 + dp->stride * 100 + ((dp->CoutPad % 64) == 0 ? 2 : 1) * 10 + 5;   // digit 5 = register-tiled (exact fp32 form)
-            if (ssr_conv_res_qualifies(*dp)) return dp->KH * 1000 + dp->stride * 100 + 1 * 10 + 1;   // WAVES digit 1 = resident
-        }
-    }
-    bool nt2, small;
-    pick_tile(*dp, nt2, small);
-    return dp->KH * 1000 + dp->stride * 100 + (nt2 ? 2 : 1) * 10 + (small ? 2 : 4);
+    const ssr_conv_family* fam;
+    ssr_conv_desc d;
+    const int rc = select(*dp, 0, fam, d);
+    return rc != SSR_OK ? rc : dp->KH * 1000 + dp->stride * 100 + fam->code(d);
 }
 
-void ssr_conv_x3r_instance(const ssr_conv_desc& d, int* ntw, int* nu, int* ep);
-int ssr_conv_x3r_tile_height(const ssr_conv_desc& d);
-
-// The kernel symbol ssr_conv2d launches for this descriptor, as rocprofv3 prints it (without the "void (anonymous namespace)::"
-// prefix and the argument list): what bench.py files a launch under, so that roofline.kernel can be looked up in
-// profiles/*_kernel_stats*.csv, *_pmc_sq.json and traffic_*.json by the same name.  Exact for the kernels that carry the step
-// (register-tiled / ring body kernels, big-tile, thin-output); for the older pipelined / resident / weight-stationary families
-// the family name with the ssr_conv2d_variant code (their template lists depend on internal tile choices).
+// The kernel symbol ssr_conv2d launches for this descriptor, as rocprofv3 prints it: the key of profiles/*_kernel_stats*.csv,
+// *_pmc_sq.json and traffic_*.json.  Exact for the kernels that carry the step, name + variant code for the older families.
 extern "C" int ssr_conv2d_symbol(const ssr_conv_desc* dp, char* buf, int32_t buflen) {
     if (!dp || !buf || buflen < 48) return SSR_EINVAL;
-    const ssr_conv_desc& d = *dp;
-    const int v = ssr_conv2d_variant(dp);
-    if (v < 0) return v;
-    const int w = v % 10, nt = (v / 10) % 10;
-    const bool f32m = d.dtype != SSR_BF16;
-    if (d.dtype != SSR_BF16 && w == 5) {
-        int ntw = 1, nu = 1, ep = 3;
-        ssr_conv_x3r_instance(d, &ntw, &nu, &ep);
-        snprintf(buf, buflen, "conv_x3r_kernel<%d, %d, %d, %d, %d>", ntw, nu, ep, ssr_conv_x3r_tile_height(d), d.dtype == SSR_F32 ? 1 : d.dtype == SSR_F32H ? 2 : 0);
-    } else if (d.dtype == SSR_F32X3 && w == 6) snprintf(buf, buflen, "conv_x3q_kernel<%d>", nt);
-    else if (d.dtype == SSR_F32X3 && w == 9) snprintf(buf, buflen, "conv_bigx3_kernel4<%d>", (d.s2d || d.KH == 2) ? 2 : 3);
-    else if (d.dtype == SSR_F32H && w == 9) snprintf(buf, buflen, "conv_bigh3_kernel4<%d>", (d.s2d || d.KH == 2) ? 2 : 3);
-    else if (f32m && w == 7) snprintf(buf, buflen, "conv_thin_f32_kernel<%d, %d>", d.Cout == 1 ? 1 : d.Cout <= 3 ? 3 : d.Cout == 4 ? 4 : 8, d.dtype == SSR_F32X3 ? 1 : d.dtype == SSR_F32H ? 2 : 0);
-    else snprintf(buf, buflen, "%s<%s,K%d,S%d,NT%d,W%d>", w == 7 ? "conv_thin_kernel" : w == 8 ? "conv_ws_kernel" : w == 9 ? "conv_big_kernel" : w == 1 ? "conv_res_kernel" : d.dtype == SSR_F32X3 ? "conv_x3_kernel" : d.dtype == SSR_F32H ? "conv_h3_kernel" : "conv_kernel",
-                  d.dtype == SSR_BF16 ? "bf16" : d.dtype == SSR_F32 ? "fp32" : d.dtype == SSR_F32H ? "fp32h" : "fp32x3", v / 1000, (v / 100) % 10, nt, w);
+    const ssr_conv_family* fam;
+    ssr_conv_desc d;
+    const int rc = select(*dp, 0, fam, d);
+    if (rc != SSR_OK) return rc;
+    fam->symbol(d, dp->KH * 1000 + dp->stride * 100 + fam->code(d), buf, buflen);
     return SSR_OK;
 }
 
@@ -968,73 +975,15 @@ extern "C" int ssr_conv2d_ck(int32_t dtype, int32_t KH) {
     return (KH == 4 ? 1 : 2) * 2 * vec;
 }
 
-static int conv2d_impl(const ssr_conv_desc* dp, void* stream, int impl) {
-    if (!dp) return SSR_EINVAL;
-    const ssr_conv_desc& d = *dp;
-    if (d.act < SSR_ACT_NONE || d.act > SSR_ACT_RELU) return SSR_EINVAL;
-    if (!view_ok(d.x, true) || !d.w || ((uintptr_t)d.w % 16) != 0) return SSR_EINVAL;
-    if (!d.y.p || d.y.cs <= 0) return SSR_EINVAL;
-    if (d.Cin <= 0 || (d.Cin % 8) != 0 || d.CoutPad <= 0 || (d.CoutPad % 32) != 0 || d.Cout > d.CoutPad)
-        return SSR_EINVAL;
-    if (!(d.up == 1 || d.up == 2) || d.N <= 0 || d.Gh <= 0 || d.Gw <= 0) return SSR_EINVAL;
-    if (d.x2.p && (d.Cin2 <= 0 || (d.Cin2 % 8) != 0 || !view_ok(d.x2, true))) return SSR_EINVAL;
-    if (!d.x2.p && d.Cin2 != 0) return SSR_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int rc = 0;
-    if (d.s2d) {   // 4x4 stride 2 through the space-to-depth view: a 2x2 stride-1 layer of 4*Cin channels on the big-tile kernel
-        if (!(d.KH == 4 && d.KW == 4 && d.stride == 2 && d.pad_y == 1 && d.pad_x == 1 && d.up == 1 && !d.x2.p)) return SSR_EINVAL;
-        if (!ssr_conv2d_s2d_ok(d.dtype, d.Cin, d.Cout, d.CoutPad) || (d.Hi % 2) || (d.Wi % 2) || d.Gh != d.Hi / 2 || d.Gw != d.Wi / 2)
-            return SSR_EINVAL;
-        ssr_conv_desc e = d;
-        e.KH = e.KW = 2; e.stride = 1; e.pad_y = e.pad_x = 0; e.Cin = 4 * d.Cin;
-        if (d.dtype == SSR_F32X3 || d.dtype == SSR_F32H) return ssr_conv_bigx3_try(e, st, &rc, true) ? rc : SSR_EUNSUP;
-        return ssr_conv_big_try(e, st, &rc, true) ? rc : SSR_EUNSUP;
-    }
-    if (d.dtype == SSR_F32H) {    // fp16-split FORWARD arithmetic (include/ssr_hip.h): the split-bf16 mode's kernels with the H flag
-        if (d.fix_list) return SSR_EUNSUP;
-        if (impl == 4) return ssr_conv_bigx3_try(d, st, &rc, true) ? rc : SSR_EUNSUP;
-        if (impl == 5) return ssr_conv_thin_try(d, st, &rc, true) ? rc : SSR_EUNSUP;
-        if (impl == 7) return ssr_conv_x3r_try(d, st, &rc, true) ? rc : SSR_EUNSUP;
-        if (impl == 0 && ssr_conv_thin_try(d, st, &rc, false)) return rc;
-        if (impl == 0 && ssr_conv_bigx3_try(d, st, &rc, false)) return rc;
-        if (impl == 0 && ssr_conv_x3r_try(d, st, &rc, false)) return rc;
-        if (d.KH == 3 && d.KW == 3 && d.stride == 1) return dispatch_tile_x3<3, 3, true>(d, st);
-        if (d.KH == 2 && d.KW == 2 && d.stride == 1) return dispatch_tile_x3<2, 2, true>(d, st);
-        ssr_conv_desc e = d;      // 4x4 stride 2 without the space-to-depth view: rows of 8 are plain fp32 (misc.hip put_packed), the exact kernel
-        e.dtype = SSR_F32;
-        return dispatch_geom<float>(e, st);
-    }
-    if (d.dtype == SSR_F32X3) {   // fp32 storage, split-bf16 matrix math (stride-1 2x2 / 3x3); 4x4 stride 2 without s2d: the exact fp32 kernel
-        if (impl == 4) return ssr_conv_bigx3_try(d, st, &rc, true) ? rc : SSR_EUNSUP;
-        if (impl == 5) return ssr_conv_thin_try(d, st, &rc, true) ? rc : SSR_EUNSUP;
-        if (impl == 6) return ssr_conv_x3q_try(d, st, &rc, true) ? rc : SSR_EUNSUP;
-        if (impl == 7) return ssr_conv_x3r_try(d, st, &rc, true) ? rc : SSR_EUNSUP;
-        if (impl == 0 && ssr_conv_thin_try(d, st, &rc, false)) return rc;
-        if (impl == 0 && ssr_conv_bigx3_try(d, st, &rc, false)) return rc;
-        if (impl == 0 && ssr_conv_x3r_try(d, st, &rc, false)) return rc;
-        if (impl == 0 && ssr_conv_x3q_try(d, st, &rc, false)) return rc;
-        if (d.KH == 3 && d.KW == 3 && d.stride == 1) return dispatch_tile_x3<3, 3>(d, st);
-        if (d.KH == 2 && d.KW == 2 && d.stride == 1) return dispatch_tile_x3<2, 2>(d, st);
-        ssr_conv_desc e = d;
-        e.dtype = SSR_F32;
-        return dispatch_geom<float>(e, st);
-    }
-    if (d.act == SSR_ACT_RELU || d.m_relu) impl = 3;   // ReLU epilogues exist only in the pipelined kernel (conv_epilogue.h)
-    if (impl == 1) return ssr_conv_ws_try(d, st, &rc, true) ? rc : SSR_EUNSUP;
-    if (impl == 4) return ssr_conv_big_try(d, st, &rc, true) ? rc : SSR_EUNSUP;
-    if (impl == 5) return ssr_conv_thin_try(d, st, &rc, true) ? rc : SSR_EUNSUP;
-    if (impl == 0 && ssr_conv_thin_try(d, st, &rc, false)) return rc;
-    if (impl == 0 && ssr_conv_ws_try(d, st, &rc, false)) return rc;
-    if (impl == 0 && ssr_conv_big_try(d, st, &rc, false)) return rc;
-    if (d.dtype == SSR_F32 && impl == 7) return ssr_conv_x3r_try(d, st, &rc, true) ? rc : SSR_EUNSUP;
-    if (d.dtype == SSR_F32 && impl == 0 && ssr_conv_x3r_try(d, st, &rc, false)) return rc;     // exact fp32 on the register-tiled body kernel (round 6)
-    if (impl != 3 && ssr_conv_res_try(d, st, &rc)) return rc;
-    if (d.dtype == SSR_F32) return dispatch_geom<float>(d, st);
-    if (d.dtype == SSR_BF16) return dispatch_geom<__bf16>(d, st);
-    return SSR_EUNSUP;
+extern "C" int ssr_conv2d_impl(const ssr_conv_desc* dp, void* stream, int32_t impl) {
+    if (!dp || !desc_valid(*dp)) return SSR_EINVAL;
+    const ssr_conv_family* fam;
+    ssr_conv_desc d;
+    const int rc = select(*dp, impl, fam, d);
+    return rc != SSR_OK ? rc : fam->launch(d, reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" int ssr_conv2d(const ssr_conv_desc* dp, void* stream) { return conv2d_impl(dp, stream, 0); }
+extern "C" int ssr_conv2d(const ssr_conv_desc* dp, void* stream) { return ssr_conv2d_impl(dp, stream, 0); }
 
 // ---- LeakyReLU decision fix-up of the split-bf16 mode (include/ssr_hip.h, ssr_conv_desc.fix_*) ----
 // One wave per listed output: the K = Cin * KH * KW products of the reference's convolution (ssr/archs/rrdbnet_arch.py:39-42,
@@ -1101,41 +1050,29 @@ extern "C" int ssr_conv2d_fixup(const ssr_conv_desc* dp, void* stream) {
 // bf16 layers of identical geometry (the parity classes of a 4x4 stride-2 dgrad), otherwise n launches.
 extern "C" int ssr_conv2d_batch(const ssr_conv_desc* ds, int32_t n, void* stream) {
     if (!ds || n <= 0 || n > 4) return SSR_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     bool same = ds[0].dtype == SSR_BF16 && ds[0].KH == 2 && ds[0].KW == 2 && ds[0].stride == 1;
     for (int k = 1; k < n && same; ++k)
         same = ds[k].dtype == ds[0].dtype && ds[k].KH == 2 && ds[k].KW == 2 && ds[k].stride == 1 && ds[k].N == ds[0].N &&
                ds[k].Gh == ds[0].Gh && ds[k].Gw == ds[0].Gw && ds[k].CoutPad == ds[0].CoutPad && ds[k].Cin == ds[0].Cin &&
                ds[k].Cin2 == ds[0].Cin2 && ds[k].Hi == ds[0].Hi && ds[k].Wi == ds[0].Wi && ds[k].up == ds[0].up;
-    static const bool off = [] { const char* e = getenv("SSR_CONV_BATCH"); return e && e[0] == '0'; }();
-    if (!off && ds[0].dtype == SSR_F32X3 && ds[0].KH == 2 && ds[0].KW == 2 && ds[0].stride == 1) {   // split-bf16 mode: the classes in one big-tile launch
-        int rcx = 0;
-        if (ssr_conv_bigx3_batch_try(ds, n, reinterpret_cast<hipStream_t>(stream), &rcx)) return rcx;
-    }
+    static const bool off = ssr_env_off("SSR_CONV_BATCH");
+    int rc = 0;
+    if (!off && ds[0].dtype == SSR_F32X3 && ds[0].KH == 2 && ds[0].KW == 2 && ds[0].stride == 1 &&
+        ssr_conv_bigx3_batch_try(ds, n, st, &rc))                        // split-bf16 mode: the classes in one big-tile launch
+        return rc;
     if (same && !off) {
-        for (int k = 0; k < n; ++k) {
-            const ssr_conv_desc& d = ds[k];
-            if (!view_ok(d.x, true) || !d.w || ((uintptr_t)d.w % 16) != 0 || !d.y.p || d.y.cs <= 0 || d.Cin <= 0 || (d.Cin % 8) != 0 ||
-                d.CoutPad <= 0 || (d.CoutPad % 32) != 0 || d.Cout > d.CoutPad || !(d.up == 1 || d.up == 2) || d.N <= 0 || d.Gh <= 0 ||
-                d.Gw <= 0 || (d.x2.p && (d.Cin2 <= 0 || (d.Cin2 % 8) != 0 || !view_ok(d.x2, true))) || (!d.x2.p && d.Cin2 != 0))
-                return SSR_EINVAL;
-        }
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        int rcb = 0;
-        if (ssr_conv_big_batch_try(ds, n, st, &rcb)) return rcb;   // 512-pixel tiles (conv_big.hip) when the grid is large enough
-        bool nt2, small;
-        pick_tile(ds[0], nt2, small);
-        // the class launches together fill the chip: use the tile shape the 4x larger grid would get
-        const long tiles4 = (long)((ds[0].Gw + 15) / 16) * ((ds[0].Gh + 7) / 8) * ds[0].N * (ds[0].CoutPad / (nt2 ? 64 : 32)) * n;
-        small = tiles4 < 384;
-        if (nt2) return small ? launch_conv4<__bf16, 2, 2, 1, 2, 2, 2>(ds, n, st) : launch_conv4<__bf16, 2, 2, 1, 2, 4, 2>(ds, n, st);
-        return small ? launch_conv4<__bf16, 2, 2, 1, 1, 2, 2>(ds, n, st) : launch_conv4<__bf16, 2, 2, 1, 1, 4, 2>(ds, n, st);
+        for (int k = 0; k < n; ++k)
+            if (!desc_valid(ds[k])) return SSR_EINVAL;
+        if (ssr_conv_big_batch_try(ds, n, st, &rc)) return rc;   // 512-pixel tiles (conv_big.hip) when the grid is large enough
+        // the class launches together fill the chip: use the tile shape the n times larger grid would get
+        const conv_tile_pick p = pick_tile(ds[0], n);
+        if (p.nt2) return p.small ? launch_conv4<__bf16, 2, 2, 1, 2, 2, 2>(ds, n, st) : launch_conv4<__bf16, 2, 2, 1, 2, 4, 2>(ds, n, st);
+        return p.small ? launch_conv4<__bf16, 2, 2, 1, 1, 2, 2>(ds, n, st) : launch_conv4<__bf16, 2, 2, 1, 1, 4, 2>(ds, n, st);
     }
     for (int k = 0; k < n; ++k) {
-        const int rc = conv2d_impl(ds + k, stream, 0);
+        rc = ssr_conv2d(ds + k, stream);
         if (rc != SSR_OK) return rc;
     }
     return SSR_OK;
-}
-extern "C" int ssr_conv2d_impl(const ssr_conv_desc* dp, void* stream, int32_t impl) {
-    return conv2d_impl(dp, stream, impl);
 }

@@ -27,8 +27,7 @@
 //
 // Replaces nn.Conv2d 3x3 forward / dgrad at /root/reference/ssr/archs/discriminator_arch.py:35-37,55,59,63
 // (conv4, conv5, conv6 and the dgrads of conv4..conv6) when the pixel count fills the chip.
-#include "common.h"
-#include <cstdlib>
+#include "conv_dispatch.h"
 
 #ifdef SSR_PROBE   // tools/big_probe.hip
 #define BPROBE(k) do { if (threadIdx.x == 0) g_probe[(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -641,7 +640,7 @@ int launch_big(const ssr_conv_desc* ds, int n, hipStream_t st) {
     // G minimises rounds x images-per-workgroup on 256 CUs (one workgroup per CU), then rounds, then prefers more groups.
     const int tpi = ((d.Gh + CB_TH - 1) / CB_TH) * ((d.Gw + CB_TW - 1) / CB_TW);
     // SSR_CONV_BIG_PERSIST: 0 = one image per workgroup, 2 / 3 = persistent 2x2 / 3x3 kernels only, default both
-    static const int persist = [] { const char* e = getenv("SSR_CONV_BIG_PERSIST"); return e ? atoi(e) : 1; }();
+    static const int persist = ssr_env_int("SSR_CONV_BIG_PERSIST", 1);
     int G = d.N;
     if (persist == 1 || persist == KT) {
         const long per_img = (long)tpi * (d.CoutPad / 64) * n;
@@ -652,7 +651,7 @@ int launch_big(const ssr_conv_desc* ds, int n, hipStream_t st) {
             if (best < 0 || key < best) { best = key; G = g; }
         }
     }
-    if (const char* e = getenv("SSR_CONV_BIG_G")) {           // test hook: force the number of image groups (1..N)
+    if (const char* e = ssr_env_now("SSR_CONV_BIG_G")) {           // test hook: force the number of image groups (1..N)
         const int g = atoi(e);
         if (g >= 1) G = g < d.N ? g : d.N;
     }
@@ -693,10 +692,8 @@ int cb_epilogue_of(const ssr_conv_desc& d) {
     return CB_GENERIC;
 }
 
-}  // namespace
-
 // everything except the grid-size heuristic (ssr_conv2d_impl(impl = 4) forces this kernel on small shapes)
-bool ssr_conv_big_shape_ok(const ssr_conv_desc& d) {
+bool big_shape_ok(const ssr_conv_desc& d) {
     if (d.dtype != SSR_BF16) return false;
     const bool k3 = d.KH == 3 && d.KW == 3 && d.pad_y == 1 && d.pad_x == 1;
     const bool k2 = d.KH == 2 && d.KW == 2 && (d.pad_y == 0 || d.pad_y == 1) && (d.pad_x == 0 || d.pad_x == 1);
@@ -720,16 +717,16 @@ bool ssr_conv_big_shape_ok(const ssr_conv_desc& d) {
     return al16(d.y) && al(d.y0) && al(d.y1) && al(d.r1) && al(d.r2) && al(d.m);
 }
 
-bool ssr_conv_big_qualifies(const ssr_conv_desc& d) {
-    static const bool off = [] { const char* e = getenv("SSR_CONV_BIGTILE"); return e && e[0] == '0'; }();
-    if (off || !ssr_conv_big_shape_ok(d) || d.KH != 3) return false;
+bool big_qualifies(const ssr_conv_desc& d) {
+    static const bool off = ssr_env_off("SSR_CONV_BIGTILE");
+    if (off || !big_shape_ok(d) || d.KH != 3) return false;
     if (d.Cin <= 64) return false;                            // weight-stationary kernel (conv_ws.hip) territory
     const long wgs = (long)d.N * ((d.Gh + CB_TH - 1) / CB_TH) * ((d.Gw + CB_TW - 1) / CB_TW) * (d.CoutPad / 64);
     return wgs >= 128;                                        // at least half the CUs get a 512-pixel tile
 }
 
 template <int KT, int CK>
-static int cb_dispatch(const ssr_conv_desc* ds, int n, hipStream_t st) {
+int cb_dispatch(const ssr_conv_desc* ds, int n, hipStream_t st) {
     switch (cb_epilogue_of(ds[0])) {
         case 0: return launch_big<0, KT, CK>(ds, n, st);
         case CB_LRELU: return launch_big<CB_LRELU, KT, CK>(ds, n, st);
@@ -742,24 +739,27 @@ static int cb_dispatch(const ssr_conv_desc* ds, int n, hipStream_t st) {
     }
 }
 
-bool ssr_conv_big_try(const ssr_conv_desc& d, hipStream_t st, int* rc, bool force) {
-    if (force ? !ssr_conv_big_shape_ok(d) : !ssr_conv_big_qualifies(d)) return false;
-    // (CbT<3, 16> — the 3x3 layers on the double-buffered stream in 16-channel chunks — builds and passes the parity tests but
-    // is slower: 49.6 vs 42.5 us on tools/big_probe.hip, 13.86 vs 13.76 ms per step.  A 16-channel chunk reads 32-byte
-    // pieces of every pixel / weight row, so each staging load touches twice the cache lines, and its 48-byte LDS rows are
-    // one third padding.  Not instantiated.)
-    *rc = d.KH == 3 ? cb_dispatch<3, 32>(&d, 1, st) : cb_dispatch<2, 32>(&d, 1, st);
-    return true;
-}
+// KT of conv_big_kernel<EP, KT, CK>: the taps per side (a space-to-depth layer arrives here as its 2x2 view)
+// (CbT<3, 16> — the 3x3 layers on the double-buffered stream in 16-channel chunks — builds and passes the parity tests but
+// is slower: 49.6 vs 42.5 us on tools/big_probe.hip, 13.86 vs 13.76 ms per step.  A 16-channel chunk reads 32-byte
+// pieces of every pixel / weight row, so each staging load touches twice the cache lines, and its 48-byte LDS rows are
+// one third padding.  Not instantiated.)
+int big_launch(const ssr_conv_desc& d, hipStream_t st) { return d.KH == 3 ? cb_dispatch<3, 32>(&d, 1, st) : cb_dispatch<2, 32>(&d, 1, st); }
+
+void big_symbol(const ssr_conv_desc& d, int v, char* buf, int buflen) { ssr_conv_symbol_coded("conv_big_kernel", d, v, buf, buflen); }
+
+}  // namespace
+
+ssr_conv_family ssr_conv_big = {"big", 4, big_shape_ok, big_qualifies, big_launch, ssr_conv_code<29>, big_symbol};
 
 // n <= 4 parity-class descriptors (2x2 stride 1, identical geometry and epilogue features) in one launch
 bool ssr_conv_big_batch_try(const ssr_conv_desc* ds, int n, hipStream_t st, int* rc) {
-    const char* e = getenv("SSR_CONV_BIGTILE2");             // 0: never, 2: always (tests), default: by grid size
+    const char* e = ssr_env_now("SSR_CONV_BIGTILE2");        // 0: never, 2: always (tests), default: by grid size
     const bool off = e && e[0] == '0', always = e && e[0] == '2';
     if (off || n < 1 || n > 4) return false;
     const int ep = cb_epilogue_of(ds[0]);
     for (int k = 0; k < n; ++k)
-        if (!ssr_conv_big_shape_ok(ds[k]) || ds[k].KH != 2 || cb_epilogue_of(ds[k]) != ep) return false;
+        if (!big_shape_ok(ds[k]) || ds[k].KH != 2 || cb_epilogue_of(ds[k]) != ep) return false;
     const ssr_conv_desc& d = ds[0];
     const long wgs = (long)d.N * ((d.Gh + CB_TH - 1) / CB_TH) * ((d.Gw + CB_TW - 1) / CB_TW) * (d.CoutPad / 64) * n;
     if (!always && (wgs < 192 || d.Gh < 24)) return false;   // small grids / half-empty 32-row tiles: pipelined kernel

@@ -24,8 +24,7 @@
 //
 // Replaces nn.Conv2d 3x3 / 4x4-stride-2 forward and dgrad at /root/reference/ssr/archs/discriminator_arch.py:28-40,45-69 and
 // rrdbnet_arch.py:109-112,127-136 in the fp32x3 arithmetic mode.
-#include "common.h"
-#include <cstdlib>
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -447,7 +446,7 @@ int launch_bigx3(const ssr_conv_desc* ds, int n, hipStream_t st) {
             if (best < 0 || key < best) { best = key; G = g; }
         }
     }
-    if (const char* e = getenv("SSR_CONV_BIG_G")) {           // test hook: force the number of image groups (1..N)
+    if (const char* e = ssr_env_now("SSR_CONV_BIG_G")) {           // test hook: force the number of image groups (1..N)
         const int g = atoi(e);
         if (g >= 1) G = g < d.N ? g : d.N;
     }
@@ -467,10 +466,8 @@ int launch_bigx3(const ssr_conv_desc* ds, int n, hipStream_t st) {
     return SSR_OK;
 }
 
-}  // namespace
-
 // everything except the grid-size heuristic
-bool ssr_conv_bigx3_shape_ok(const ssr_conv_desc& d) {
+bool bigx3_shape_ok(const ssr_conv_desc& d) {
     if ((d.dtype != SSR_F32X3 && d.dtype != SSR_F32H) || d.fix_list) return false;
     const bool k3 = d.KH == 3 && d.KW == 3 && d.pad_y == 1 && d.pad_x == 1;
     const bool k2 = d.KH == 2 && d.KW == 2 && (d.pad_y == 0 || d.pad_y == 1) && (d.pad_x == 0 || d.pad_x == 1);
@@ -495,31 +492,39 @@ bool ssr_conv_bigx3_shape_ok(const ssr_conv_desc& d) {
     return d.x.p && d.y.p && al16(d.x) && al16(d.y) && al16(d.y0) && al16(d.y1) && al16(d.r1) && al16(d.r2) && al16(d.m);
 }
 
-bool ssr_conv_bigx3_qualifies(const ssr_conv_desc& d) {
-    static const bool off = [] { const char* e = getenv("SSR_X3_BIGTILE"); return e && e[0] == '0'; }();
-    if (off || !ssr_conv_bigx3_shape_ok(d) || d.KH != 3) return false;
+bool bigx3_qualifies(const ssr_conv_desc& d) {
+    static const bool off = ssr_env_off("SSR_X3_BIGTILE");
+    if (off || !bigx3_shape_ok(d) || d.KH != 3) return false;
     // The choice depends on the LAYER only, never on the batch: an image's result must not depend on how many images are launched
     // together (whole-tile inference deals chunks to ranks and batches; a last partial batch on another kernel would change bytes -
     // tests/test_gpu_baseline_shapes.py::test_infer_grid_tile_end_to_end_vs_oracle).  >= 4 tile x channel-group workgroups per image
-    // (64 x 64 grids and up, or >= 256 output channels at 32 x 32), 32-row tiles not half empty; the 32 x 32 body goes to conv_x3q.hip.
+    // (64 x 64 grids and up, or >= 256 output channels at 32 x 32), 32-row tiles not half empty; the 32 x 32 body goes to conv_x3r.hip.
     const long per_img = (long)((d.Gh + XB_TH - 1) / XB_TH) * ((d.Gw + XB_TW - 1) / XB_TW) * (d.CoutPad / 64);
     return per_img >= 4 && d.Gh >= 24;
 }
 
-bool ssr_conv_bigx3_try(const ssr_conv_desc& d, hipStream_t st, int* rc, bool force) {
-    if (force ? !ssr_conv_bigx3_shape_ok(d) : !ssr_conv_bigx3_qualifies(d)) return false;
-    if (d.dtype == SSR_F32H) *rc = d.KH == 3 ? launch_bigx3<3, true>(&d, 1, st) : launch_bigx3<2, true>(&d, 1, st);
-    else *rc = d.KH == 3 ? launch_bigx3<3>(&d, 1, st) : launch_bigx3<2>(&d, 1, st);
-    return true;
+// KT of conv_bigx3_kernel4<KT> / conv_bigh3_kernel4<KT>: the taps per side (a space-to-depth layer arrives here as its 2x2 view)
+int bigx3_kt(const ssr_conv_desc& d) { return d.KH == 3 ? 3 : 2; }
+int bigx3_launch(const ssr_conv_desc& d, hipStream_t st) {
+    if (d.dtype == SSR_F32H) return bigx3_kt(d) == 3 ? launch_bigx3<3, true>(&d, 1, st) : launch_bigx3<2, true>(&d, 1, st);
+    return bigx3_kt(d) == 3 ? launch_bigx3<3>(&d, 1, st) : launch_bigx3<2>(&d, 1, st);
 }
+
+void bigx3_symbol(const ssr_conv_desc& d, int, char* buf, int buflen) {
+    snprintf(buf, buflen, "%s<%d>", d.dtype == SSR_F32H ? "conv_bigh3_kernel4" : "conv_bigx3_kernel4", bigx3_kt(d));
+}
+
+}  // namespace
+
+ssr_conv_family ssr_conv_bigx3 = {"bigx3", 4, bigx3_shape_ok, bigx3_qualifies, bigx3_launch, ssr_conv_code<29>, bigx3_symbol};
 
 // n <= 4 parity-class descriptors (2x2 stride 1, identical geometry) in one launch
 bool ssr_conv_bigx3_batch_try(const ssr_conv_desc* ds, int n, hipStream_t st, int* rc) {
-    const char* e = getenv("SSR_X3_BIGTILE2");               // 0: never, 2: always (tests), default: by grid size
+    const char* e = ssr_env_now("SSR_X3_BIGTILE2");          // 0: never, 2: always (tests), default: by grid size
     const bool off = e && e[0] == '0', always = e && e[0] == '2';
     if (off || n < 1 || n > 4) return false;
     for (int k = 0; k < n; ++k)
-        if (!ssr_conv_bigx3_shape_ok(ds[k]) || ds[k].dtype != SSR_F32X3 || ds[k].KH != 2 || ds[k].s2d) return false;
+        if (!bigx3_shape_ok(ds[k]) || ds[k].dtype != SSR_F32X3 || ds[k].KH != 2 || ds[k].s2d) return false;
     const ssr_conv_desc& d = ds[0];
     for (int k = 1; k < n; ++k)
         if (ds[k].N != d.N || ds[k].Gh != d.Gh || ds[k].Gw != d.Gw || ds[k].CoutPad != d.CoutPad || ds[k].Cin != d.Cin || ds[k].Hi != d.Hi || ds[k].Wi != d.Wi ||

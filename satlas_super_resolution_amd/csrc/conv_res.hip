@@ -21,6 +21,7 @@
 // Replaces the same reference ops as conv.hip for /root/reference/ssr/archs/rrdbnet_arch.py:37-44,63-68
 // (ResidualDenseBlock / RRDB forward) and their autograd backward.
 #include "conv_epilogue.h"
+#include "conv_dispatch.h"
 
 #ifdef SSR_PROBE   // tools/conv_probe.hip: per-phase s_memtime stamps (lane 0 of wave 0 of every workgroup)
 #define PROBE(k)                                                                                       \
@@ -210,26 +211,28 @@ int launch_res(const ssr_conv_desc& d, int nchunks, hipStream_t st) {
     return SSR_OK;
 }
 
-}  // namespace
+int res_nchunks(const ssr_conv_desc& d) { return (d.Cin + d.Cin2 + (d.dtype == SSR_F32 ? 15 : 31)) / (d.dtype == SSR_F32 ? 16 : 32); }
 
-// Returns true and launches if the descriptor qualifies for the K-resident kernel:
-// 3x3 stride 1, no upsampling, identity output mapping, small grid, whole reduction fits in LDS.
-bool ssr_conv_res_qualifies(const ssr_conv_desc& d) {
+// 3x3 stride 1, no upsampling, identity output mapping, whole reduction fits in LDS
+bool res_shape_ok(const ssr_conv_desc& d) {
     if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.up == 1 && d.pad_y == 1 && d.pad_x == 1)) return false;
     if (d.Gh != d.Hi || d.Gw != d.Wi) return false;
     if (d.dtype != SSR_F32 && d.dtype != SSR_BF16) return false;
-    const int ck = d.dtype == SSR_F32 ? 16 : 32;
-    const int nchunks = (d.Cin + d.Cin2 + ck - 1) / ck;
-    const long tiles = (long)((d.Gw + RES_TW - 1) / RES_TW) * ((d.Gh + RES_TH - 1) / RES_TH) * d.N;
-    if (tiles * (d.CoutPad / 32) > 2048) return false;                   // large grids: pipelined kernel
-    return (size_t)nchunks * (RES_PROWS_PAD + 9 * 32) * RES_ROWB <= 160 * 1024;
+    return (size_t)res_nchunks(d) * (RES_PROWS_PAD + 9 * 32) * RES_ROWB <= 160 * 1024;
 }
 
-bool ssr_conv_res_try(const ssr_conv_desc& d, hipStream_t st, int* rc) {
-    if (!ssr_conv_res_qualifies(d)) return false;
-    const int ck = d.dtype == SSR_F32 ? 16 : 32;
-    const int nchunks = (d.Cin + d.Cin2 + ck - 1) / ck;
-    if (d.dtype == SSR_F32) *rc = launch_res<float, 1>(d, nchunks, st);
-    else *rc = launch_res<__bf16, 1>(d, nchunks, st);
-    return true;
+bool res_qualifies(const ssr_conv_desc& d) {
+    if (!res_shape_ok(d)) return false;
+    const long tiles = (long)((d.Gw + RES_TW - 1) / RES_TW) * ((d.Gh + RES_TH - 1) / RES_TH) * d.N;
+    return tiles * (d.CoutPad / 32) <= 2048;                             // large grids: pipelined kernel
 }
+
+int res_launch(const ssr_conv_desc& d, hipStream_t st) {
+    return d.dtype == SSR_F32 ? launch_res<float, 1>(d, res_nchunks(d), st) : launch_res<__bf16, 1>(d, res_nchunks(d), st);
+}
+
+void res_symbol(const ssr_conv_desc& d, int v, char* buf, int buflen) { ssr_conv_symbol_coded("conv_res_kernel", d, v, buf, buflen); }
+
+}  // namespace
+
+ssr_conv_family ssr_conv_res = {"res", -1, res_shape_ok, res_qualifies, res_launch, ssr_conv_code<11>, res_symbol};

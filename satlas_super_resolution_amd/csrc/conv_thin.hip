@@ -9,8 +9,7 @@
 //
 // Replaces nn.Conv2d forward at /root/reference/ssr/archs/discriminator_arch.py:40,69 (conv9), rrdbnet_arch.py:113,136
 // (conv_last) and autograd's input gradient of discriminator_arch.py:28,44 (conv0) in the generator phase.
-#include "common.h"
-#include <cstdlib>
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -279,12 +278,17 @@ int launch_thin_f32(const ssr_conv_desc& d, hipStream_t st) {
     SSR_LAUNCH_CHECK();
     return SSR_OK;
 }
+// the one Cout bucket of a descriptor: the NCO of conv_thin_f32_kernel<NCO, X3> (fp32 modes) / conv_thin_kernel<NCO> (bf16)
+int ct_cout_bucket(const ssr_conv_desc& d) {
+    if (d.Cout == 1) return 1;
+    if (d.dtype == SSR_BF16) return d.Cout <= 4 ? 4 : 8;
+    return d.Cout <= 3 ? 3 : d.Cout == 4 ? 4 : 8;
+}
 template <int X3>
 int launch_thin_f32_by_cout(const ssr_conv_desc& d, hipStream_t st) {
-    if (d.Cout == 1) return launch_thin_f32<1, X3>(d, st);
-    if (d.Cout <= 3) return launch_thin_f32<3, X3>(d, st);
-    if (d.Cout == 4) return launch_thin_f32<4, X3>(d, st);
-    return launch_thin_f32<8, X3>(d, st);
+    const int nco = ct_cout_bucket(d);
+    if (nco <= 3) return nco == 1 ? launch_thin_f32<1, X3>(d, st) : launch_thin_f32<3, X3>(d, st);
+    return nco == 4 ? launch_thin_f32<4, X3>(d, st) : launch_thin_f32<8, X3>(d, st);
 }
 
 template <int NCO>
@@ -305,9 +309,7 @@ int launch_thin(const ssr_conv_desc& d, hipStream_t st) {
     return SSR_OK;
 }
 
-}  // namespace
-
-bool ssr_conv_thin_shape_ok(const ssr_conv_desc& d) {
+bool thin_shape_ok(const ssr_conv_desc& d) {
     const bool f32 = d.dtype == SSR_F32 || d.dtype == SSR_F32X3 || d.dtype == SSR_F32H;
     if (d.dtype != SSR_BF16 && !f32) return false;
     if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad_y == 1 && d.pad_x == 1) || d.x2.p || d.up != 1 || d.fix_list) return false;
@@ -319,26 +321,32 @@ bool ssr_conv_thin_shape_ok(const ssr_conv_desc& d) {
     return (d.x.cs % 8) == 0 && (d.x.coff % 8) == 0 && ((uintptr_t)d.x.p % 16) == 0 && ((uintptr_t)d.w % 16) == 0;
 }
 
-bool ssr_conv_thin_qualifies(const ssr_conv_desc& d) {
-    static const bool off = [] { const char* e = getenv("SSR_CONV_THIN"); return e && e[0] == '0'; }();
-    if (off || !ssr_conv_thin_shape_ok(d)) return false;
+bool thin_qualifies(const ssr_conv_desc& d) {
+    static const bool off = ssr_env_off("SSR_CONV_THIN");
+    if (off || !thin_shape_ok(d)) return false;
     // fp32 modes: by the LAYER's grid only (64 x 64 pixels and up) - an image's bytes must not depend on how many images are launched
     // together (whole-tile inference deals chunks to ranks and batches; conv_last is such a layer).  Measured in the fp32x3 step
     // (call r05v, B = 32, 128 x 128): 79 us per launch against 117 us on the MFMA kernel; SSR_CONV_THIN_F32=0 switches it off.
     if (d.dtype != SSR_BF16) {
-        static const bool off32 = [] { const char* e = getenv("SSR_CONV_THIN_F32"); return e && e[0] == '0'; }();
+        static const bool off32 = ssr_env_off("SSR_CONV_THIN_F32");
         return !off32 && (long)d.Gh * d.Gw >= 4096;
     }
     return (long)d.N * d.Gh * d.Gw >= 65536;                  // enough 256-pixel tiles to fill the chip
 }
 
-bool ssr_conv_thin_try(const ssr_conv_desc& d, hipStream_t st, int* rc, bool force) {
-    if (force ? !ssr_conv_thin_shape_ok(d) : !ssr_conv_thin_qualifies(d)) return false;
-    if (d.dtype == SSR_F32H) { *rc = launch_thin_f32_by_cout<2>(d, st); return true; }
-    if (d.dtype == SSR_F32X3) { *rc = launch_thin_f32_by_cout<1>(d, st); return true; }
-    if (d.dtype == SSR_F32) { *rc = launch_thin_f32_by_cout<0>(d, st); return true; }
-    if (d.Cout == 1) *rc = launch_thin<1>(d, st);
-    else if (d.Cout <= 4) *rc = launch_thin<4>(d, st);
-    else *rc = launch_thin<8>(d, st);
-    return true;
+int thin_launch(const ssr_conv_desc& d, hipStream_t st) {
+    if (d.dtype == SSR_F32H) return launch_thin_f32_by_cout<2>(d, st);
+    if (d.dtype == SSR_F32X3) return launch_thin_f32_by_cout<1>(d, st);
+    if (d.dtype == SSR_F32) return launch_thin_f32_by_cout<0>(d, st);
+    const int nco = ct_cout_bucket(d);
+    return nco == 1 ? launch_thin<1>(d, st) : nco == 4 ? launch_thin<4>(d, st) : launch_thin<8>(d, st);
 }
+
+void thin_symbol(const ssr_conv_desc& d, int v, char* buf, int buflen) {
+    if (d.dtype == SSR_BF16) ssr_conv_symbol_coded("conv_thin_kernel", d, v, buf, buflen);
+    else snprintf(buf, buflen, "conv_thin_f32_kernel<%d, %d>", ct_cout_bucket(d), d.dtype == SSR_F32X3 ? 1 : d.dtype == SSR_F32H ? 2 : 0);
+}
+
+}  // namespace
+
+ssr_conv_family ssr_conv_thin = {"thin", 5, thin_shape_ok, thin_qualifies, thin_launch, ssr_conv_code<17>, thin_symbol};

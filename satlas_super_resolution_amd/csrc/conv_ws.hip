@@ -17,8 +17,7 @@
 //
 // Replaces nn.Conv2d 3x3 (and its dgrad) at /root/reference/ssr/archs/discriminator_arch.py:28,38-40,44,67-69
 // and rrdbnet_arch.py:104,111-112,128,136 (conv0, conv7, conv8, conv9; conv_up2, conv_hr, conv_last).
-#include "common.h"
-#include <cstdlib>
+#include "conv_dispatch.h"
 
 #ifdef SSR_PROBE
 #define WPROBE(k) do { if (threadIdx.x == 0 && tile == (int)blockIdx.x + (int)gridDim.x) g_probe[(blockIdx.y * gridDim.x + blockIdx.x) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -402,25 +401,9 @@ int launch_ws(const ssr_conv_desc& d, hipStream_t st) {
     return launch_ws_ep<NPL, NT, WS_GENERIC>(d, st);
 }
 
-}  // namespace
-
-// 3x3 stride 1 bf16, Cin <= 64, large grid, single input, full-range residual / mask channel windows
-bool ssr_conv_ws_shape_ok(const ssr_conv_desc& d);
-bool ssr_conv_ws_qualifies(const ssr_conv_desc& d) {
-    static const bool off = [] { const char* e = getenv("SSR_CONV_WS"); return e && e[0] == '0'; }();
-    if (off || d.dtype != SSR_BF16) return false;
-    if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad_y == 1 && d.pad_x == 1) || d.x2.p) return false;
-    if (d.Cin > 64 || (d.Cout % 8) != 0) return false;
-    if (d.Gh != (d.Hi << (d.up == 2)) || d.Gw != (d.Wi << (d.up == 2))) return false;
-    const long ntiles = (long)d.N * ((d.Gh + WS_TH - 1) / WS_TH) * ((d.Gw + WS_TW - 1) / WS_TW);
-    if (ntiles * (d.CoutPad / 32) < 2048) return false;                 // small grids: resident / fused kernels
-    // r01 measurements (tools/ws_probe.hip): Cin <= 32 beats the pipelined kernel by 1.3-3x; the 64-channel variant
-    // (one wave per SIMD, 288 weight registers) by 1.5x once its epilogue is a branch-free instantiation
-    return ssr_conv_ws_shape_ok(d);
-}
-
-// everything except the grid-size heuristic (ssr_conv2d_impl can force this kernel on small shapes)
-bool ssr_conv_ws_shape_ok(const ssr_conv_desc& d) {
+// everything except the grid-size heuristic (ssr_conv2d_impl can force this kernel on small shapes):
+// 3x3 stride 1 bf16, Cin <= 64, single input, full-range residual / mask channel windows
+bool ws_shape_ok(const ssr_conv_desc& d) {
     if (d.dtype != SSR_BF16) return false;
     if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad_y == 1 && d.pad_x == 1) || d.x2.p) return false;
     if (d.Cin > 64 || (d.Cout % 8) != 0) return false;
@@ -434,21 +417,41 @@ bool ssr_conv_ws_shape_ok(const ssr_conv_desc& d) {
     return al(d.y) && al(d.y0) && al(d.y1) && al(d.r1) && al(d.r2) && al(d.m);
 }
 
-bool ssr_conv_ws_try(const ssr_conv_desc& d, hipStream_t st, int* rc, bool force) {
-    if (force ? !ssr_conv_ws_shape_ok(d) : !ssr_conv_ws_qualifies(d)) return false;
-    // Cin <= 32: 32-channel output tiles, 2 workgroups per CU; Cin <= 64: 64-channel tiles held by one wave per SIMD
-    // (288 weight registers) when the padded output width allows it
-    // Cin <= 64: 32-channel tiles with TWO workgroups per CU (one's epilogue overlaps the other's MFMAs: 27.7 vs 36.0 us on
-    // a 64->64 128x128 layer) for the epilogue variants that fit 256 registers without spilling (plain / LeakyReLU);
-    // the others keep 64-channel tiles on one wave per SIMD.  SSR_CONV_WS21=0 / 2: never / always 32-channel tiles.
-    static const int v21 = [] { const char* e = getenv("SSR_CONV_WS21"); return e ? atoi(e) : 1; }();
+// <NPL, NT> of the instantiation as NPL * 10 + NT; 0: none unless forced.  Cin <= 32: 32-channel output tiles, 2 workgroups per CU.
+// Cin <= 64: 32-channel tiles with TWO workgroups per CU (one's epilogue overlaps the other's MFMAs: 27.7 vs 36.0 us on a 64->64
+// 128x128 layer) for the epilogue variants that fit 256 registers without spilling (plain / LeakyReLU); the others keep 64-channel
+// tiles on one wave per SIMD (288 weight registers) when the padded output width allows it.  SSR_CONV_WS21=0 / 2: never / always 32.
+int ws_pick(const ssr_conv_desc& d, bool force) {
+    static const int v21 = ssr_env_int("SSR_CONV_WS21", 1);
     const bool light = !d.y0.p && !d.y1.p && !d.r2.p && !d.r1.p && !d.m.p && !d.accumulate && d.alpha == 1.f;
     const bool mask_only = !d.y0.p && !d.y1.p && !d.r2.p && !d.r1.p && d.m.p && !d.accumulate && d.alpha == 1.f &&
                            d.act != SSR_ACT_LRELU;
-    if (d.Cin <= 32) *rc = launch_ws<1, 1>(d, st);
-    else if (v21 == 2 || (v21 >= 1 && light) || (v21 == 3 && mask_only)) *rc = launch_ws<2, 1>(d, st);
-    else if (d.CoutPad % 64 == 0) *rc = launch_ws<2, 2>(d, st);
-    else if (force) *rc = launch_ws<2, 1>(d, st);             // spills with the heavier epilogues: only on request
-    else return false;
-    return true;
+    if (d.Cin <= 32) return 11;
+    if (v21 == 2 || (v21 >= 1 && light) || (v21 == 3 && mask_only)) return 21;
+    if (d.CoutPad % 64 == 0) return 22;
+    return force ? 21 : 0;                                    // spills with the heavier epilogues: only on request
 }
+
+bool ws_qualifies(const ssr_conv_desc& d) {
+    static const bool off = ssr_env_off("SSR_CONV_WS");
+    if (off || !ws_shape_ok(d)) return false;
+    const long ntiles = (long)d.N * ((d.Gh + WS_TH - 1) / WS_TH) * ((d.Gw + WS_TW - 1) / WS_TW);
+    if (ntiles * (d.CoutPad / 32) < 2048) return false;                 // small grids: resident / fused kernels
+    // r01 measurements (tools/ws_probe.hip): Cin <= 32 beats the pipelined kernel by 1.3-3x; the 64-channel variant
+    // (one wave per SIMD, 288 weight registers) by 1.5x once its epilogue is a branch-free instantiation
+    return ws_pick(d, false) != 0;
+}
+
+int ws_launch(const ssr_conv_desc& d, hipStream_t st) {
+    switch (ws_pick(d, true)) {
+        case 11: return launch_ws<1, 1>(d, st);
+        case 21: return launch_ws<2, 1>(d, st);
+        default: return launch_ws<2, 2>(d, st);
+    }
+}
+
+void ws_symbol(const ssr_conv_desc& d, int v, char* buf, int buflen) { ssr_conv_symbol_coded("conv_ws_kernel", d, v, buf, buflen); }
+
+}  // namespace
+
+ssr_conv_family ssr_conv_ws = {"ws", 1, ws_shape_ok, ws_qualifies, ws_launch, ssr_conv_code<18>, ws_symbol};

@@ -21,6 +21,7 @@
 // Forward chains add the same products in the same order as four conv_x3r launches (bit-identical results); backward chains walk
 // K in the opposite direction (same products, other fp32 summation order).
 #include "conv_x3r_core.h"
+#include "conv_dispatch.h"
 #include <cstdio>
 
 #ifdef SSR_PROBE   // tools/x3c_probe.hip: s_memtime stamps of MFMA wave 0, 32 slots per workgroup
@@ -410,25 +411,21 @@ bool overlap(const ssr_view& a, int na, const ssr_view& b, int nb) {
 
 }  // namespace
 
-bool ssr_conv_x3r_shape_ok(const ssr_conv_desc& d);
-void ssr_conv_x3r_instance(const ssr_conv_desc& d, int* ntw, int* nu, int* ep);
-
 extern "C" int64_t ssr_conv2d_chain_state_bytes(int32_t N, int32_t Gh, int32_t Gw) {
     return XC_STATE_HDR + (int64_t)N * ((Gw + 15) / 16) * ((Gh + 7) / 8) * 16;
 }
 
 // 1 if the n descriptors can run as one chain launch (else ssr_conv2d_chain launches them one by one)
 extern "C" int ssr_conv2d_chain_ok(const ssr_conv_desc* ds, int32_t n) {
-    static const bool off = [] { const char* e = getenv("SSR_X3_CHAIN"); return e && e[0] == '0'; }();
+    static const bool off = ssr_env_off("SSR_X3_CHAIN");
     if (off || !ds || n < 2 || n > XC_MAXN) return 0;
     int ep0 = -1;
     for (int k = 0; k < n; ++k) {
         const ssr_conv_desc& d = ds[k];
-        if (d.dtype != SSR_F32X3 || !ssr_conv_x3r_shape_ok(d) || d.CoutPad != 32 || d.Cout > 32) return 0;
+        if (d.dtype != SSR_F32X3 || !ssr_conv_x3r.shape_ok(d) || d.CoutPad != 32 || d.Cout > 32) return 0;
         if (d.N != ds[0].N || d.Hi != ds[0].Hi || d.Wi != ds[0].Wi || d.Gh != ds[0].Gh || d.Gw != ds[0].Gw) return 0;
         if ((d.Cin % 16) != 0 || (d.x2.p && (d.Cin2 % 16) != 0) || (d.Cin + d.Cin2) / 16 > XC_MAXCH || d.Cin + d.Cin2 < 16) return 0;
-        int nt = 0, nu = 0, ep = 3;
-        ssr_conv_x3r_instance(d, &nt, &nu, &ep);
+        const int ep = ssr_conv_x3r_pick(d).ep;
         if (ep == XR_EP_GENERIC || (ep0 >= 0 && ep != ep0)) return 0;
         ep0 = ep;
         // no later conv of the chain may overwrite what an earlier one reads or writes (a workgroup runs ahead of its neighbours)
@@ -446,7 +443,7 @@ extern "C" int ssr_conv2d_chain_ok(const ssr_conv_desc* ds, int32_t n) {
     for (int k = 0; k < n; ++k) {
         const ssr_conv_desc& d = ds[k];
         const int nch = (d.Cin + d.Cin2) / 16;
-        int first_dep = -1, last_free = -1, prev = -2;
+        int prev = -2;
         bool asc = true, desc = true;
         for (int c = 0; c < nch; ++c) {
             const bool in_x = c * 16 < d.Cin;
@@ -465,7 +462,6 @@ extern "C" int ssr_conv2d_chain_ok(const ssr_conv_desc* ds, int32_t n) {
                 if (dep > prev) desc = false;
             }
             prev = dep;
-            (void)first_dep; (void)last_free;
         }
         if (!asc && !desc) return 0;
     }
@@ -492,7 +488,7 @@ extern "C" int ssr_conv2d_chain(const ssr_conv_desc* ds, int32_t n, void* state,
     a.tiles_x = (ds[0].Gw + 15) / 16;
     a.tiles_y = (ds[0].Gh + 7) / 8;
     a.state = reinterpret_cast<uint32_t*>(state);
-    int ep = 3, nt = 0, nu = 0;
+    int ep = 3;
     for (int k = 0; k < n; ++k) {
         a.d[k] = ds[k];
         const ssr_conv_desc& d = ds[k];
@@ -511,7 +507,7 @@ extern "C" int ssr_conv2d_chain(const ssr_conv_desc* ds, int32_t n, void* state,
         }
         // dependent chunks must be walked LAST: ascending when the producers grow with the chunk index, else descending
         a.rev[k] = (int8_t)((nch > 1 && firstd > a.dep[k][nch - 1]) ? 1 : 0);
-        ssr_conv_x3r_instance(d, &nt, &nu, &ep);
+        ep = ssr_conv_x3r_pick(d).ep;
     }
     const int blocks = a.tiles_x * a.tiles_y * ds[0].N;
     switch (ep) {

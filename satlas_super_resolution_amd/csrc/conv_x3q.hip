@@ -28,7 +28,7 @@
 // Replaces nn.Conv2d 3x3 forward and dgrad of the dense blocks, /root/reference/ssr/archs/rrdbnet_arch.py:26-30,37-44 (and any other
 // stride-1 3x3 layer on a small grid) in the fp32x3 arithmetic mode.
 #include "conv_epilogue.h"
-#include <cstdlib>
+#include "conv_dispatch.h"
 
 #ifdef SSR_PROBE   // tools/x3q_probe.hip: s_memtime stamps of one thread per role, 16 slots per workgroup
 #define QPROBE(cond, k) do { if (cond) g_probe[(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -376,9 +376,7 @@ int launch_x3q(const ssr_conv_desc& d, hipStream_t st) {
     return SSR_OK;
 }
 
-}  // namespace
-
-bool ssr_conv_x3q_shape_ok(const ssr_conv_desc& d) {
+bool x3q_shape_ok(const ssr_conv_desc& d) {
     if (d.dtype != SSR_F32X3 || d.fix_list) return false;
     if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad_y == 1 && d.pad_x == 1 && d.up == 1 && !d.s2d)) return false;
     if (d.Gh != d.Hi || d.Gw != d.Wi || (d.CoutPad % 32) != 0) return false;
@@ -389,16 +387,22 @@ bool ssr_conv_x3q_shape_ok(const ssr_conv_desc& d) {
     return true;
 }
 
-bool ssr_conv_x3q_qualifies(const ssr_conv_desc& d) {
-    static const bool off = [] { const char* e = getenv("SSR_X3_RING"); return e && e[0] == '0'; }();
-    if (off || !ssr_conv_x3q_shape_ok(d)) return false;
+bool x3q_qualifies(const ssr_conv_desc& d) {
+    static const bool off = ssr_env_off("SSR_X3_RING");
+    if (off || !x3q_shape_ok(d)) return false;
     // small grids (the 32 x 32 body at any batch; conv_first / conv_body): the big-tile kernel takes the others
     return d.Gh <= 64 && d.Gw <= 64 && d.Cin + d.Cin2 >= 16;
 }
 
-bool ssr_conv_x3q_try(const ssr_conv_desc& d, hipStream_t st, int* rc, bool force) {
-    if (force ? !ssr_conv_x3q_shape_ok(d) : !ssr_conv_x3q_qualifies(d)) return false;
-    static const bool nt2_off = [] { const char* e = getenv("SSR_X3_RING_NT2"); return e && e[0] == '0'; }();
-    *rc = ((d.CoutPad % 64) == 0 && !nt2_off) ? launch_x3q<2>(d, st) : launch_x3q<1>(d, st);
-    return true;
+// NT of conv_x3q_kernel<NT>: 64 output channels per workgroup where the padded width allows it (SSR_X3_RING_NT2=0: never)
+int x3q_nt(const ssr_conv_desc& d) {
+    static const bool nt2_off = ssr_env_off("SSR_X3_RING_NT2");
+    return ((d.CoutPad % 64) == 0 && !nt2_off) ? 2 : 1;
 }
+int x3q_launch(const ssr_conv_desc& d, hipStream_t st) { return x3q_nt(d) == 2 ? launch_x3q<2>(d, st) : launch_x3q<1>(d, st); }
+int x3q_code(const ssr_conv_desc& d) { return x3q_nt(d) * 10 + 6; }
+void x3q_symbol(const ssr_conv_desc& d, int, char* buf, int buflen) { snprintf(buf, buflen, "conv_x3q_kernel<%d>", x3q_nt(d)); }
+
+}  // namespace
+
+ssr_conv_family ssr_conv_x3q = {"x3q", 6, x3q_shape_ok, x3q_qualifies, x3q_launch, x3q_code, x3q_symbol};

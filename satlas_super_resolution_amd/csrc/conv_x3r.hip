@@ -30,6 +30,7 @@
 // Replaces nn.Conv2d 3x3 forward and dgrad of the dense blocks, /root/reference/ssr/archs/rrdbnet_arch.py:26-30,37-44 (and any
 // other stride-1 3x3 layer on a small grid) in the fp32x3 arithmetic mode.
 #include "conv_x3r_core.h"
+#include "conv_dispatch.h"
 
 #ifdef SSR_PROBE   // tools/x3r_probe.hip: s_memtime stamps of one thread per role, 16 slots per workgroup
 #define RPROBE(cond, k) do { if (cond) g_probe[(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -446,7 +447,7 @@ int launch_x3r(const ssr_conv_desc& d, hipStream_t st) {
 
 // which of the straight-line epilogues covers the descriptor (else the generic one)
 int xr_pick_epilogue(const ssr_conv_desc& d) {
-    static const bool generic_only = [] { const char* e = getenv("SSR_X3R_EPI"); return e && e[0] == '0'; }();
+    static const bool generic_only = ssr_env_off("SSR_X3R_EPI");
     if (generic_only) return XR_EP_GENERIC;
     const long lim = 0x7fffff00L, npx = (long)d.N * d.Ho * d.Wo * 4;
     auto vok = [&](const ssr_view& v) { return (v.cs % 4) == 0 && (v.coff % 4) == 0 && ((uintptr_t)v.p % 16) == 0 && npx * v.cs <= lim; };
@@ -472,7 +473,7 @@ int launch_x3r_ep(const ssr_conv_desc& d, hipStream_t st) {
 // half-height tiles (4 x 16 pixels, <1, 1> form only): when the 8 x 16 tiling of a 32-channel layer would leave more than 3/8 of the
 // CUs without a workgroup (per-GPU batch 16 on the 32 x 32 body: 128 tiles).  SSR_X3_REGTILE_TH=8 | 4 forces one
 int xr_tile_height(const ssr_conv_desc& d, int form) {
-    static const int forced = [] { const char* e = getenv("SSR_X3_REGTILE_TH"); return e ? atoi(e) : 0; }();
+    static const int forced = ssr_env_int("SSR_X3_REGTILE_TH", 0);
     if (form != 0) return 8;
     if (forced == 4 || forced == 8) return forced;
     const long tiles8 = (long)((d.Gw + 15) / 16) * ((d.Gh + 7) / 8) * d.N * (d.CoutPad / 32);
@@ -484,35 +485,22 @@ int xr_tile_height(const ssr_conv_desc& d, int form) {
 // against 27.24 ms per step, call r06j: twelve-wave workgroups share the chip worse with the second chain and the discriminator stream);
 // 0 = as two 32-channel workgroups (SSR_X3_REGTILE_NT2=0)
 int xr_wide_form(const ssr_conv_desc& d) {
-    static const int f = [] { const char* e = getenv("SSR_X3_REGTILE_NT2"); return !e ? 1 : e[0] == '0' ? 0 : e[0] == '8' ? 2 : 1; }();
+    static const int f = ssr_env_off("SSR_X3_REGTILE_NT2") ? 0 : ssr_env_int("SSR_X3_REGTILE_NT2", 1) == 8 ? 2 : 1;
     if ((d.CoutPad % 64) != 0) return 0;
     // a launch that leaves half the chip idle (per-GPU batch 16 on the 32 x 32 body: 128 tiles) runs its 64-channel layers as two
     // 32-channel workgroups per tile: twice the workgroups, the same products in the same order (an image's bytes do not depend on
     // the form: every form sums the four K quarters of a (pixel tile, channel tile) in wave order)
-    static const bool split_off = [] { const char* e = getenv("SSR_X3_REGTILE_SPLIT"); return e && e[0] == '0'; }();
+    static const bool split_off = ssr_env_off("SSR_X3_REGTILE_SPLIT");
     const long tiles = (long)((d.Gw + 15) / 16) * ((d.Gh + 7) / 8) * d.N;
     if (!split_off && tiles * (d.CoutPad / 64) <= 160) return 0;
     // the generic epilogue does not fit the 168 registers of a twelve-wave workgroup (77 spilled): those (rare) layers keep the four-wave form
     return (f == 2 && xr_pick_epilogue(d) == XR_EP_GENERIC) ? 1 : f;
 }
 
-}  // namespace
-
-// channel tiles per workgroup, MFMA waves and straight-line-epilogue index of the instantiation ssr_conv_x3r_try launches (the rocprofv3
-// symbol is conv_x3r_kernel<NTW, NU, EP>)
-void ssr_conv_x3r_instance(const ssr_conv_desc& d, int* ntw, int* nu, int* ep) {
-    int f = xr_wide_form(d);
-    if ((d.dtype == SSR_F32 || d.dtype == SSR_F32H) && f == 2) f = 1;
-    *ntw = f == 1 ? 2 : 1;
-    *nu = f == 2 ? 2 : 1;
-    *ep = xr_pick_epilogue(d);
-}
-int ssr_conv_x3r_tile_height(const ssr_conv_desc& d) { return xr_tile_height(d, xr_wide_form(d)); }
-
-bool ssr_conv_x3r_shape_ok(const ssr_conv_desc& d) {
-    static const bool ex_off = [] { const char* e = getenv("SSR_F32_REGTILE"); return e && e[0] == '0'; }();
+bool x3r_shape_ok(const ssr_conv_desc& d) {
+    static const bool ex_off = ssr_env_off("SSR_F32_REGTILE");
     if (!(d.dtype == SSR_F32X3 || d.dtype == SSR_F32H || (d.dtype == SSR_F32 && !ex_off)) || d.fix_list) return false;
-    if (d.dtype == SSR_F32 && (d.act == SSR_ACT_RELU || d.m_relu)) return false;      // (the VGG19 layers keep the pipelined kernel: conv2d_impl)
+    if (d.dtype == SSR_F32 && (d.act == SSR_ACT_RELU || d.m_relu)) return false;      // (the VGG19 layers keep the pipelined kernel: conv.hip select)
     if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad_y == 1 && d.pad_x == 1 && d.up == 1 && !d.s2d)) return false;
     if (d.Gh != d.Hi || d.Gw != d.Wi || (d.CoutPad % 32) != 0) return false;
     if (d.x2.p && (d.Cin % 16) != 0) return false;            // a 16-channel chunk comes from ONE view
@@ -522,28 +510,40 @@ bool ssr_conv_x3r_shape_ok(const ssr_conv_desc& d) {
     return true;
 }
 
-bool ssr_conv_x3r_qualifies(const ssr_conv_desc& d) {
-    static const bool off = [] { const char* e = getenv("SSR_X3_REGTILE"); return e && e[0] == '0'; }();
-    if (off || !ssr_conv_x3r_shape_ok(d)) return false;
+bool x3r_qualifies(const ssr_conv_desc& d) {
+    static const bool off = ssr_env_off("SSR_X3_REGTILE");
+    if (off || !x3r_shape_ok(d)) return false;
     // small grids (the 32 x 32 body at any batch; conv_first / conv_body): the big-tile kernel takes the others
     return d.Gh <= 64 && d.Gw <= 64 && d.Cin + d.Cin2 >= 16;
 }
 
-bool ssr_conv_x3r_try(const ssr_conv_desc& d, hipStream_t st, int* rc, bool force) {
-    if (force ? !ssr_conv_x3r_shape_ok(d) : !ssr_conv_x3r_qualifies(d)) return false;
-    const int f = xr_wide_form(d);
-    if (d.dtype == SSR_F32) {                                  // exact fp32 arithmetic: four-wave forms only
-        if (f != 0) *rc = launch_x3r_ep<2, 1, 8, 1>(d, st);
-        else *rc = xr_tile_height(d, f) == 4 ? launch_x3r_ep<1, 1, 4, 1>(d, st) : launch_x3r_ep<1, 1, 8, 1>(d, st);
-        return true;
-    }
-    if (d.dtype == SSR_F32H) {                                 // fp16-split forward arithmetic: four-wave forms only
-        if (f != 0) *rc = launch_x3r_ep<2, 1, 8, 2>(d, st);
-        else *rc = xr_tile_height(d, f) == 4 ? launch_x3r_ep<1, 1, 4, 2>(d, st) : launch_x3r_ep<1, 1, 8, 2>(d, st);
-        return true;
-    }
-    if (f == 2) *rc = launch_x3r_ep<1, 2>(d, st);
-    else if (f == 1) *rc = launch_x3r_ep<2, 1>(d, st);
-    else *rc = xr_tile_height(d, f) == 4 ? launch_x3r_ep<1, 1, 4>(d, st) : launch_x3r_ep<1, 1, 8>(d, st);
-    return true;
+template <int AM>
+int launch_x3r_am(const ssr_conv_x3r_instance& i, const ssr_conv_desc& d, hipStream_t st) {
+    if constexpr (AM == 0)
+        if (i.nu == 2) return launch_x3r_ep<1, 2>(d, st);
+    if (i.ntw == 2) return launch_x3r_ep<2, 1, 8, AM>(d, st);
+    return i.th == 4 ? launch_x3r_ep<1, 1, 4, AM>(d, st) : launch_x3r_ep<1, 1, 8, AM>(d, st);
 }
+
+int x3r_launch(const ssr_conv_desc& d, hipStream_t st) {
+    const ssr_conv_x3r_instance i = ssr_conv_x3r_pick(d);
+    return i.am == 1 ? launch_x3r_am<1>(i, d, st) : i.am == 2 ? launch_x3r_am<2>(i, d, st) : launch_x3r_am<0>(i, d, st);
+}
+
+int x3r_code(const ssr_conv_desc& d) { return ((d.CoutPad % 64) == 0 ? 2 : 1) * 10 + 5; }
+void x3r_symbol(const ssr_conv_desc& d, int, char* buf, int buflen) {
+    const ssr_conv_x3r_instance i = ssr_conv_x3r_pick(d);
+    snprintf(buf, buflen, "conv_x3r_kernel<%d, %d, %d, %d, %d>", i.ntw, i.nu, i.ep, i.th, i.am);
+}
+
+}  // namespace
+
+// <NTW, NU, EP, TH, AM> of the instantiation the family launches; AM 1 (exact fp32) and 2 (fp16 split) have four-wave forms only
+ssr_conv_x3r_instance ssr_conv_x3r_pick(const ssr_conv_desc& d) {
+    const int am = d.dtype == SSR_F32 ? 1 : d.dtype == SSR_F32H ? 2 : 0;
+    int f = xr_wide_form(d);
+    if (am != 0 && f == 2) f = 1;
+    return {f == 1 ? 2 : 1, f == 2 ? 2 : 1, xr_pick_epilogue(d), xr_tile_height(d, f), am};
+}
+
+ssr_conv_family ssr_conv_x3r = {"x3r", 7, x3r_shape_ok, x3r_qualifies, x3r_launch, x3r_code, x3r_symbol};

@@ -21,9 +21,9 @@ int main(int argc, char** argv) {
     unsigned long long* probe; hipMalloc(&probe, (size_t)nb * 16 * 8); hipMemset(probe, 0, (size_t)nb * 16 * 8);
     hipMemcpyToSymbol(HIP_SYMBOL(g_probe), &probe, sizeof(probe));
     int rc = 0; hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    for (int it = 0; it < 3; ++it) ssr_conv_big_try(d, 0, &rc, true);
+    for (int it = 0; it < 3; ++it) rc = ssr_conv_big.launch(d, 0);
     hipDeviceSynchronize(); hipEventRecord(e0);
-    for (int it = 0; it < 10; ++it) ssr_conv_big_try(d, 0, &rc, true);
+    for (int it = 0; it < 10; ++it) rc = ssr_conv_big.launch(d, 0);
     hipEventRecord(e1); hipEventSynchronize(e1); float ms; hipEventElapsedTime(&ms, e0, e1);
     std::vector<unsigned long long> h((size_t)nb * 16); hipMemcpy(h.data(), probe, h.size() * 8, hipMemcpyDeviceToHost);
     const double gf = 2.0 * N * H * W * Cin * Cout * KT * KT / 1e9;

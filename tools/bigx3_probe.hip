@@ -28,10 +28,10 @@ int main(int argc, char** argv) {
     if (epi == 2) { d.m = {r1, Cout, 0}; d.m_c0 = 0; d.m_c1 = Cout; }
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     int rc = 0;
-    for (int it = 0; it < 3; ++it) ssr_conv_bigx3_try(d, 0, &rc, true);
+    for (int it = 0; it < 3; ++it) rc = ssr_conv_bigx3.launch(d, 0);
     hipDeviceSynchronize();
     hipEventRecord(e0);
-    for (int it = 0; it < 20; ++it) ssr_conv_bigx3_try(d, 0, &rc, true);
+    for (int it = 0; it < 20; ++it) rc = ssr_conv_bigx3.launch(d, 0);
     hipEventRecord(e1); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     std::vector<unsigned long long> h((size_t)nblk_max * 8);

@@ -15,9 +15,9 @@ int main() {
     d.KH = d.KW = 3; d.stride = 1; d.pad_y = d.pad_x = 1; d.Gh = H; d.Gw = W; d.Ho = H; d.Wo = W; d.oys = d.oxs = 1;
     d.Cout = 64; d.y = {y, C, 0}; d.alpha = 1.f; d.act = 1;
     int rc = 0; hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    for (int it = 0; it < 3; ++it) ssr_conv_ws_try(d, 0, &rc, true);
+    for (int it = 0; it < 3; ++it) rc = ssr_conv_ws.launch(d, 0);
     hipDeviceSynchronize(); hipEventRecord(e0);
-    for (int it = 0; it < 20; ++it) ssr_conv_ws_try(d, 0, &rc, true);
+    for (int it = 0; it < 20; ++it) rc = ssr_conv_ws.launch(d, 0);
     hipEventRecord(e1); hipEventSynchronize(e1); float ms; hipEventElapsedTime(&ms, e0, e1);
     std::vector<unsigned long long> h(256 * 8); hipMemcpy(h.data(), probe, h.size() * 8, hipMemcpyDeviceToHost);
     double ph[8] = {0}; int nb2 = 256;

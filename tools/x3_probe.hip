@@ -9,18 +9,13 @@
 #include <algorithm>
 __device__ unsigned long long* g_probe;
 #include "../satlas_super_resolution_amd/csrc/conv.hip"
-// the other kernel families are not linked into the probe
-bool ssr_conv_res_try(const ssr_conv_desc&, hipStream_t, int*) { return false; }
-bool ssr_conv_res_qualifies(const ssr_conv_desc&) { return false; }
-bool ssr_conv_ws_try(const ssr_conv_desc&, hipStream_t, int*, bool) { return false; }
-bool ssr_conv_ws_qualifies(const ssr_conv_desc&) { return false; }
-bool ssr_conv_thin_try(const ssr_conv_desc&, hipStream_t, int*, bool) { return false; }
-bool ssr_conv_thin_qualifies(const ssr_conv_desc&) { return false; }
-bool ssr_conv_big_try(const ssr_conv_desc&, hipStream_t, int*, bool) { return false; }
-bool ssr_conv_big_qualifies(const ssr_conv_desc&) { return false; }
+// the other kernel families are not linked into the probe: records that never qualify
+static bool never(const ssr_conv_desc&) { return false; }
+ssr_conv_family ssr_conv_thin = {"thin", 5, never, never, nullptr, nullptr, nullptr}, ssr_conv_ws = {"ws", 1, never, never, nullptr, nullptr, nullptr},
+                ssr_conv_big = {"big", 4, never, never, nullptr, nullptr, nullptr}, ssr_conv_bigx3 = {"bigx3", 4, never, never, nullptr, nullptr, nullptr},
+                ssr_conv_x3r = {"x3r", 7, never, never, nullptr, nullptr, nullptr}, ssr_conv_x3q = {"x3q", 6, never, never, nullptr, nullptr, nullptr},
+                ssr_conv_res = {"res", -1, never, never, nullptr, nullptr, nullptr};
 bool ssr_conv_big_batch_try(const ssr_conv_desc*, int, hipStream_t, int*) { return false; }
-bool ssr_conv_bigx3_try(const ssr_conv_desc&, hipStream_t, int*, bool) { return false; }
-bool ssr_conv_bigx3_qualifies(const ssr_conv_desc&) { return false; }
 bool ssr_conv_bigx3_batch_try(const ssr_conv_desc*, int, hipStream_t, int*) { return false; }
 
 int main(int argc, char** argv) {

@@ -27,10 +27,10 @@ int main(int argc, char** argv) {
     d.Cout = Cout; d.y = {y, CS, 64}; d.alpha = 1.f; d.act = 1;
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     int rc = 0;
-    for (int it = 0; it < 5; ++it) ssr_conv_x3q_try(d, 0, &rc, true);
+    for (int it = 0; it < 5; ++it) rc = ssr_conv_x3q.launch(d, 0);
     hipDeviceSynchronize();
     hipEventRecord(e0);
-    for (int it = 0; it < 50; ++it) ssr_conv_x3q_try(d, 0, &rc, true);
+    for (int it = 0; it < 50; ++it) rc = ssr_conv_x3q.launch(d, 0);
     hipEventRecord(e1); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     std::vector<unsigned long long> h((size_t)nblk * 16);

@@ -34,7 +34,7 @@ int main(int argc, char** argv) {
     int rc = 0;
     float ms[2];
     for (int k = 0; k < 2; ++k) {
-        auto run = [&]() { if (k == 0) ssr_conv_x3r_try(d, 0, &rc, true); else ssr_conv_x3q_try(d, 0, &rc, true); };
+        auto run = [&]() { if (k == 0) rc = ssr_conv_x3r.launch(d, 0); else rc = ssr_conv_x3q.launch(d, 0); };
         for (int it = 0; it < 5; ++it) run();
         hipDeviceSynchronize();
         hipEventRecord(e0);
@@ -43,7 +43,7 @@ int main(int argc, char** argv) {
         hipEventElapsedTime(&ms[k], e0, e1);
     }
     hipMemset(probe, 0, (size_t)nblk * 16 * 8);
-    ssr_conv_x3r_try(d, 0, &rc, true);
+    rc = ssr_conv_x3r.launch(d, 0);
     hipDeviceSynchronize();
     std::vector<unsigned long long> h((size_t)nblk * 16);
     hipMemcpy(h.data(), probe, h.size() * 8, hipMemcpyDeviceToHost);
