@@ -35,8 +35,8 @@ import torch
 import torch.nn as nn
 
 from .. import engine, hip
-from ..engine import Launcher, WgradBatch, rup
-from ..hip import ConvDesc, PackItem, PreluReflectDesc, SrTailDesc, View, view
+from ..engine import ConvSpec, Launcher, WgradBatch, conv_desc, rup, wgrad_args
+from ..hip import PackItem, PreluReflectDesc, SrTailDesc, View, view
 from ..l2_reference import mask_words, pack_mask_nhwc
 from ..registry import ARCH_REGISTRY
 from .hipnet import ConvParams
@@ -153,7 +153,7 @@ class L2Store:
         self.grad = torch.zeros(off, dtype=torch.float32, device=self.device)
         L = hip.lib()
         ck = L.ssr_conv2d_ck(hip.F32, 3)
-        self.packed_fwd, self.packed_dgrad, self.pad, self.conv_shape = {}, {}, {}, {}
+        self.packed_fwd, self.packed_dgrad, self.pad, self.specs = {}, {}, {}, {}
         items = []
         for name in convs:
             cout, cin, k, _ = shapes[name + ".weight"]
@@ -164,11 +164,11 @@ class L2Store:
             pd = torch.zeros(9 * cin_pad_o * cout_pad_i, dtype=torch.float32, device=self.device)
             self.packed_fwd[name], self.packed_dgrad[name] = pf, pd
             self.pad[name] = (cout_pad, cin_pad, cin_pad_o, cout_pad_i)
-            self.conv_shape[name] = (cout, cin)
+            self.specs[name] = ConvSpec(name, cout, cin)
             items.append(PackItem(self.ptr(name + ".weight"), None, pf.data_ptr(), pd.data_ptr(), cout, cin, 3, 3, 1, cout_pad, cin_pad,
                                   cin_pad_o, cout_pad_i, ck, ck, 0))
         self._pack_items = items
-        self.pack_table = hip.device_table(items)
+        self.pack_table = hip.device_table(items, self.device)
 
     def tensor(self, key: str, arena: Optional[torch.Tensor] = None) -> torch.Tensor:
         off, shape = self.offsets[key]
@@ -176,6 +176,9 @@ class L2Store:
 
     def ptr(self, key: str, arena: Optional[torch.Tensor] = None) -> int:
         return (self.data if arena is None else arena).data_ptr() + 4 * self.offsets[key][0]
+
+    def wkey(self, name: str) -> str:
+        return name + ".weight"
 
     def pack(self):
         hip.check(hip.lib().ssr_pack_weights(self.pack_table.data_ptr(), len(self._pack_items), hip.F32, hip.stream_ptr()),
@@ -327,15 +330,8 @@ class L2Plan:
         """conv 3x3 (reflect) over node x -> pre; PReLU (+ dropout, + residual) -> node `out`; and the same backwards"""
         st, H, W = self.st, self.H, self.W
         pre = self._zeros(N, H, W, cout)
-        cout_pad = st.pad[conv][0]
-        d = ConvDesc()
-        d.dtype = hip.F32
-        d.x, d.N, d.Hi, d.Wi, d.up, d.Cin = view(x.buf), N, H + 2, W + 2, 1, cin
-        d.w, d.CoutPad, d.bias = st.packed_fwd[conv].data_ptr(), cout_pad, st.ptr(conv + ".bias")
-        d.KH = d.KW = 3
-        d.stride, d.pad_y, d.pad_x = 1, 0, 0
-        d.Gh, d.Gw, d.Ho, d.Wo, d.oys, d.oyo, d.oxs, d.oxo = H, W, H, W, 1, 0, 1, 0
-        d.Cout, d.y, d.alpha, d.act = cout, view(pre), 1.0, hip.ACT_NONE
+        d = conv_desc(dtype=hip.F32, x=view(x.buf), N=N, Hi=H + 2, Wi=W + 2, Cin=cin, w=st.packed_fwd[conv].data_ptr(),
+                      CoutPad=st.pad[conv][0], bias=st.ptr(conv + ".bias"), KH=3, pad_y=0, Gh=H, Gw=W, Cout=cout, y=view(pre))
         self.keep.append(d)
         self.fwd.add(hip.lib().ssr_conv2d, C.byref(d), what=f"conv fwd {conv}")
         mask = None
@@ -369,21 +365,13 @@ class L2Plan:
             self.keep.append(b)
             self.bwd.add(hip.lib().ssr_prelu_reflect_bwd, C.byref(b), what=f"prelu / reflect bwd {conv}")
             # weight and bias gradient: pad-0 wgrad over the padded input
-            real_cin = st.conv_shape[conv][1]
-            self._wgrad(conv, view(x.buf), view(dpre), N, cin, cout, real_cin)
+            self._wgrad(conv, view(x.buf), view(dpre), N, cin)
             if first:
                 return
             # data gradient: the full correlation with flipped weights (pad 2) onto the padded grid of x
             gx = self._zeros(*x.buf.shape)
-            _, _, cin_pad_o, _ = st.pad[conv]
-            e = ConvDesc()
-            e.dtype = hip.F32
-            e.x, e.N, e.Hi, e.Wi, e.up, e.Cin = view(dpre), N, H, W, 1, rup(cout, 8)
-            e.w, e.CoutPad, e.bias = st.packed_dgrad[conv].data_ptr(), cin_pad_o, None
-            e.KH = e.KW = 3
-            e.stride, e.pad_y, e.pad_x = 1, 2, 2
-            e.Gh, e.Gw, e.Ho, e.Wo, e.oys, e.oyo, e.oxs, e.oxo = H + 2, W + 2, H + 2, W + 2, 1, 0, 1, 0
-            e.Cout, e.y, e.alpha, e.act = real_cin, view(gx), 1.0, hip.ACT_NONE
+            e = conv_desc(dtype=hip.F32, x=view(dpre), N=N, Hi=H, Wi=W, Cin=rup(cout, 8), w=st.packed_dgrad[conv].data_ptr(),
+                          CoutPad=st.pad[conv][2], KH=3, pad_y=2, Gh=H + 2, Gw=W + 2, Cout=st.specs[conv].cin, y=view(gx))
             self.keep.append(e)
             self.bwd.add(hip.lib().ssr_conv2d, C.byref(e), what=f"conv dgrad {conv}")
             x.grads.insert(0, (gx, 1))
@@ -394,21 +382,16 @@ class L2Plan:
         self._conv_prelu(p + "0", p + "2.weight", x, N, cin, cout, mid, drop=True, first=first)
         self._conv_prelu(p + "4", p + "6.weight", mid, N, cout, cout, out, drop=True, res=res)
 
-    def _wgrad(self, conv, x: View, dy: View, N, cin, cout, real_cin):
+    def _wgrad(self, conv, x: View, dy: View, N, cin):
         """deterministic batches (per-split partials, fixed-order sums); a layer applied more than once - HighResNet's shared fusion
         block - goes into a later batch each time, so that one launch never has two writers of one gradient"""
         st = self.st
         if self._wb is None or conv in self._used_dw:
             self._close_wbatch()
-            self._wb = WgradBatch(hip.F32, 3, 1, det=True)
+            self._wb = WgradBatch(hip.F32, 3, 1, det=True, device=st.device)
             self._used_dw = set()
         self._used_dw.add(conv)
-        wb = self._wb
-        n0 = len(wb.layers)
-        wb.add(x, dy, N, self.H + 2, self.W + 2, 1, cin, cout, self.H, self.W, 1.0, st.ptr(conv + ".weight", st.grad), real_cin,
-               st.ptr(conv + ".bias", st.grad))
-        for L in wb.layers[n0:]:
-            L.pad_y = L.pad_x = 0
+        self._wb.add(x, dy, N, self.H + 2, self.W + 2, 1, gh=self.H, gw=self.W, alpha=1.0, pad=0, **wgrad_args(st, conv, cin))
 
     def _close_wbatch(self):
         if self._wb is not None and self._wb.layers:

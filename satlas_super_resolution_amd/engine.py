@@ -14,15 +14,14 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import hip
-from .hip import ConvDesc, View, WgradItem, WgradLayer, PackItem, SNItem, SNBwdItem, ReduceItem, view
+from . import hip, wgrad_plan
+from .hip import ConvDesc, View, WgradItem, WgradLayer, PackItem, SNItem, SNBwdItem, ReduceItem, view  # noqa: F401
 
 
 def rup(a: int, b: int) -> int:
@@ -68,7 +67,7 @@ class ParamStore:
         self.offsets: "OrderedDict[str, Tuple[int, Tuple[int, ...]]]" = OrderedDict()
         off = 0
         for s in specs:
-            wname = s.name + (".weight_orig" if s.sn else ".weight")
+            wname = self.wkey(s.name)
             shape = (s.cout, s.cin, s.k, s.k)
             self.offsets[wname] = (off, shape)
             off += s.cout * s.cin * s.k * s.k
@@ -123,7 +122,7 @@ class ParamStore:
             ntap_d = kk if s.stride == 1 else 16
             pd = torch.zeros(ntap_d * cin_pad_o * cout_pad_i if s.dgrad_packed else 8, dtype=tdt, device=self.device)
             self.packed_fwd[s.name], self.packed_dgrad[s.name] = pf, pd
-            woff, _ = self.offsets[s.name + (".weight_orig" if s.sn else ".weight")]
+            woff, _ = self.offsets[self.wkey(s.name)]
             inv = (self.sigma.data_ptr() + 4 * self.sn_names.index(s.name)) if s.sn else None
             items.append(PackItem(self.data.data_ptr() + 4 * woff, inv, pf.data_ptr(),
                                   pd.data_ptr() if s.dgrad_packed else None,
@@ -144,14 +143,14 @@ class ParamStore:
                 bw.append(b)
             self._pack_items, self._pack_items_bwd = fw, bw
             items = fw
-            self.pack_table_bwd = hip.device_table(bw)
+            self.pack_table_bwd = hip.device_table(bw, self.device)
         self.repacked: Dict[Tuple[str, int], torch.Tensor] = {}
         # gathered dense-block dgrad weights (filled by add_rdb_gather)
         self.gather: Dict[Tuple[str, int], torch.Tensor] = {}
         self.gather_rows: Dict[Tuple[str, int], int] = {}
         self._seg_items: List[hip.PackSeg] = []
         self.seg_table = None
-        self.pack_table = hip.device_table(items)
+        self.pack_table = hip.device_table(items, self.device)
         if self.sn_names:
             sn_items, bwd_items = [], []
             for j, n in enumerate(self.sn_names):
@@ -163,8 +162,8 @@ class ParamStore:
                 bwd_items.append(SNBwdItem(self.grad_sn.data_ptr() + 4 * woff, self.data.data_ptr() + 4 * woff,
                                            self.u[n].data_ptr(), self.v[n].data_ptr(), self.sigma.data_ptr() + 4 * j,
                                            self.grad.data_ptr() + 4 * woff, self.sn_dot[j].data_ptr(), rows, cols))
-            self.sn_table = hip.device_table(sn_items)
-            self.sn_bwd_table = hip.device_table(bwd_items)
+            self.sn_table = hip.device_table(sn_items, self.device)
+            self.sn_bwd_table = hip.device_table(bwd_items, self.device)
             self.sn_max_rows = max(self.specs[n].cout for n in self.sn_names)
             self.sn_max_cols = max(self.specs[n].cin * self.specs[n].k ** 2 for n in self.sn_names)
             self.sn_max_elems = max(self.specs[n].cout * self.specs[n].cin * self.specs[n].k ** 2
@@ -219,7 +218,7 @@ class ParamStore:
                                                  hip.stream_ptr()), "ssr_pack_weights (backward layouts)")
         if self._seg_items:
             if self.seg_table is None:
-                self.seg_table = hip.device_table(self._seg_items)
+                self.seg_table = hip.device_table(self._seg_items, self.device)
             hip.check(hip.lib().ssr_pack_dgrad_gather(self.seg_table.data_ptr(), len(self._seg_items), self.dtype,
                                                       hip.stream_ptr()), "ssr_pack_dgrad_gather")
 
@@ -232,11 +231,11 @@ class ParamStore:
         s = self.specs[name]
         cout_pad, cin_pad = rup(s.cout, 32), rup(rup(s.cin, 8), ck)
         buf = torch.zeros(s.k * s.k * cout_pad * cin_pad, dtype=hip.torch_dtype(self.dtype), device=self.device)
-        woff, _ = self.offsets[name + (".weight_orig" if s.sn else ".weight")]
+        woff, _ = self.offsets[self.wkey(name)]
         inv = (self.sigma.data_ptr() + 4 * self.sn_names.index(name)) if s.sn else None
         self._pack_items.append(PackItem(self.data.data_ptr() + 4 * woff, inv, buf.data_ptr(), None, s.cout, s.cin, s.k, s.k,
                                          s.stride, cout_pad, cin_pad, rup(s.cin, 32), rup(rup(s.cout, 8), ck), ck, ck))
-        self.pack_table = hip.device_table(self._pack_items)
+        self.pack_table = hip.device_table(self._pack_items, self.device)
         self.repacked[key] = buf
         return buf
 
@@ -287,6 +286,16 @@ class ParamStore:
             hip.check(hip.lib().ssr_spectral_norm_bwd(self.sn_bwd_table.data_ptr(), len(self.sn_names),
                                                       self.sn_max_elems, hip.stream_ptr()), "ssr_spectral_norm_bwd")
             hip.check(hip.lib().ssr_fill(self.grad_sn.data_ptr(), self.grad_sn.numel(), hip.F32, 0.0, hip.stream_ptr()), "ssr_fill")
+
+
+def wgrad_args(st, name: str, cin: Optional[int] = None) -> Dict:
+    """What WgradBatch.add needs of layer `name` of a store (ParamStore, or l2_archs.L2Store): the channels of the input view it reads
+    (`cin`, default the layer's own padded to 8), its real channel counts and where dW / db go - dW of a spectral-normalised layer into
+    grad_sn (the gradient w.r.t. the normalised weight), everything else into grad."""
+    s = st.specs[name]
+    return dict(cin=rup(s.cin, 8) if cin is None else cin, cout=s.cout, cin_w=s.cin,
+                dw_ptr=st.ptr(st.wkey(name), st.grad_sn if s.sn else st.grad),
+                db_ptr=st.ptr(name + ".bias", st.grad) if s.bias else None)
 
 
 class Launcher:
@@ -340,6 +349,20 @@ class Launcher:
         return len(self.calls)
 
 
+def conv_desc(**fields) -> ConvDesc:
+    """One ssr_conv_desc (include/ssr_hip.h) from keyword arguments named as its fields.  What is not given is the common case: a square
+    stride-1 pad-1 kernel (KW = KH, pad_x = pad_y), no upsampling, the output grid written densely (Ho, Wo = Gh, Gw; unit strides, zero
+    offsets), alpha 1, no activation, null y0 / y1 / r1 / r2 / m / x2 views, no accumulation, no fix-up list."""
+    f = dict(up=1, stride=1, pad_y=1, oys=1, oxs=1, alpha=1.0, act=hip.ACT_NONE)
+    f.update(fields)
+    for k, src in (("KW", "KH"), ("pad_x", "pad_y"), ("Ho", "Gh"), ("Wo", "Gw")):
+        f.setdefault(k, f[src])
+    d = ConvDesc()
+    for k, v in f.items():
+        setattr(d, k, v)
+    return d
+
+
 class _ConvBuilder:
     """Fills ssr_conv_desc records; keeps them alive."""
 
@@ -347,35 +370,28 @@ class _ConvBuilder:
         self.store, self.N, self.dt = store, N, store.dtype
         self.keep = []
         self.packed_fwd, self.packed_dgrad = store.packed_fwd, store.packed_dgrad
+        self._fix_pool, self._fix_used = [], 0
+
+    def array(self, descs):
+        """already filled descriptors copied into one ctypes array (ssr_conv2d_batch, ssr_conv2d_chain)"""
+        arr = (ConvDesc * len(descs))()
+        for i, d in enumerate(descs):
+            C.memmove(C.byref(arr[i]), C.byref(d), C.sizeof(ConvDesc))
+        self.keep.append(arr)
+        return arr
 
     def conv(self, L: Launcher, name: str, x: View, hi: int, wi: int, y: View, *, up=1, act=hip.ACT_NONE, alpha=1.0,
              y0: View = hip.NULL_VIEW, r1: View = hip.NULL_VIEW, r1_nc=0, beta1=0.0, r2: View = hip.NULL_VIEW,
              r2_nc=0, beta2=0.0, cin: Optional[int] = None):
-        s = self.store.specs[name]
-        cout_pad, _, _, _ = self.store.pad[name]
-        d = ConvDesc()
-        d.dtype = self.store.fwd_dtype                          # (mode fp32f: forward convolutions exact, hip.F32F)
-        d.x, d.N, d.Hi, d.Wi, d.up = x, self.N, hi, wi, up
-        d.Cin = rup(s.cin, 8) if cin is None else cin
-        d.w = self.packed_fwd[name].data_ptr()
-        d.CoutPad = cout_pad
-        d.bias = self.store.ptr(name + ".bias") if s.bias else None
-        d.KH = d.KW = s.k
-        d.stride = s.stride
-        d.pad_y = d.pad_x = 1
-        lh, lw = hi * up, wi * up
-        d.Gh, d.Gw = (lh // s.stride, lw // s.stride)
-        d.Ho, d.Wo, d.oys, d.oyo, d.oxs, d.oxo = d.Gh, d.Gw, 1, 0, 1, 0
-        d.Cout = s.cout
-        d.y, d.y0, d.y1 = y, y0, hip.NULL_VIEW
-        d.alpha, d.act = alpha, act
-        d.r1, d.r1_nc, d.beta1 = r1, r1_nc, beta1
-        d.r2, d.r2_nc, d.beta2 = r2, r2_nc, beta2
-        d.accumulate = 0
-        d.m, d.m_c0, d.m_c1 = hip.NULL_VIEW, 0, 0
-        d.s2d = 1 if self.store.s2d.get(name) else 0
+        st, s = self.store, self.store.specs[name]
+        d = conv_desc(dtype=st.fwd_dtype,                       # (mode fp32f: forward convolutions exact, hip.F32F)
+                      x=x, N=self.N, Hi=hi, Wi=wi, up=up, Cin=rup(s.cin, 8) if cin is None else cin,
+                      w=self.packed_fwd[name].data_ptr(), CoutPad=st.pad[name][0], bias=st.ptr(name + ".bias") if s.bias else None,
+                      KH=s.k, stride=s.stride, Gh=hi * up // s.stride, Gw=wi * up // s.stride, Cout=s.cout, y=y, y0=y0,
+                      alpha=alpha, act=act, r1=r1, r1_nc=r1_nc, beta1=beta1, r2=r2, r2_nc=r2_nc, beta2=beta2,
+                      s2d=1 if st.s2d.get(name) else 0)
         self.keep.append(d)
-        fix = (self.store.fwd_dtype == hip.F32X3 and act == hip.ACT_LRELU and s.stride == 1 and s.k == 3 and alpha == 1.0 and not y0.p
+        fix = (st.fwd_dtype == hip.F32X3 and act == hip.ACT_LRELU and s.stride == 1 and s.k == 3 and alpha == 1.0 and not y0.p
                and not r1.p and not r2.p and X3_FIXUP[0])
         if fix:
             # split-bf16 mode: the LeakyReLU decisions of this layer are those of an exact evaluation - outputs whose pre-activation
@@ -383,8 +399,8 @@ class _ConvBuilder:
             # the reference-layout fp32 weights by the launch that follows (include/ssr_hip.h, ssr_conv_desc.fix_*)
             d.fix_list = self._fix_list()
             d.fix_cap, d.fix_thr = X3_FIX_CAP, X3_FIX_THR[0]
-            d.w_ref, d.w_ref_cin = self.store.ptr(name + (".weight_orig" if s.sn else ".weight")), s.cin
-            d.w_ref_sigma = (self.store.sigma.data_ptr() + 4 * self.store.sn_names.index(name)) if s.sn else None
+            d.w_ref, d.w_ref_cin = st.ptr(st.wkey(name)), s.cin
+            d.w_ref_sigma = (st.sigma.data_ptr() + 4 * st.sn_names.index(name)) if s.sn else None
         L.add(hip.lib().ssr_conv2d, C.byref(d), what=f"conv fwd {name}")
         if fix:
             L.add(hip.lib().ssr_conv2d_fixup, C.byref(d), what=f"lrelu decision fix-up {name}")
@@ -393,15 +409,15 @@ class _ConvBuilder:
     def _fix_list(self) -> int:
         """device address of a zeroed fix-up list (4 header words + X3_FIX_CAP (pixel, channel) pairs) of its own"""
         words = 4 + 2 * X3_FIX_CAP
-        if not getattr(self, "_fix_pool", None) or self._fix_used == self._fix_pool[-1].shape[0]:
-            self._fix_pool = getattr(self, "_fix_pool", []) + [torch.zeros(64, words, dtype=torch.int32, device=self.store.device)]
+        if not self._fix_pool or self._fix_used == self._fix_pool[-1].shape[0]:
+            self._fix_pool.append(torch.zeros(64, words, dtype=torch.int32, device=self.store.device))
             self._fix_used = 0
         self._fix_used += 1
         return self._fix_pool[-1][self._fix_used - 1].data_ptr()
 
     def fix_high_water(self) -> int:
         """largest number of outputs any fix-up list of this builder has held (diagnostics / tests: must stay below X3_FIX_CAP)"""
-        return max([int(p[:, 2].max()) for p in getattr(self, "_fix_pool", [])] or [0])
+        return max([int(p[:, 2].max()) for p in self._fix_pool] or [0])
 
     def dgrad(self, L: Launcher, name: str, dy: View, gh: int, gw: int, y: View, *, cout: Optional[int] = None,
               alpha=1.0, y1: View = hip.NULL_VIEW, r1: View = hip.NULL_VIEW, r1_nc=0, beta1=0.0,
@@ -413,68 +429,28 @@ class _ConvBuilder:
         _, _, cin_pad_o, cout_pad_i = self.store.pad[name]
         wbase = self.packed_dgrad[name].data_ptr()
         esz = 2 if self.dt == hip.BF16 else 4
-        classes = [(0, 0)] if s.stride == 1 else [(0, 0), (0, 1), (1, 0), (1, 1)]
-        arr = (ConvDesc * len(classes))()
-        for ic, (py, px) in enumerate(classes):
-            d = arr[ic]
-            d.dtype = self.dt
-            d.x, d.N, d.Hi, d.Wi, d.up = dy, self.N, gh, gw, 1
-            d.Cin = rup(s.cout, 8) if cin_dy is None else cin_dy
-            d.CoutPad = cin_pad_o
-            d.bias = None
-            d.Cout = s.cin if cout is None else cout
-            if s.stride == 1:
-                d.w = wbase
-                d.KH = d.KW = s.k
-                d.stride, d.pad_y, d.pad_x = 1, 1, 1
-                d.Gh, d.Gw = gh, gw
-                d.Ho, d.Wo, d.oys, d.oyo, d.oxs, d.oxo = gh, gw, 1, 0, 1, 0
-            else:
-                cls = py * 2 + px
-                d.w = wbase + cls * 4 * cin_pad_o * cout_pad_i * esz
-                d.KH = d.KW = 2
-                d.stride, d.pad_y, d.pad_x = 1, 1 - py, 1 - px
-                d.Gh, d.Gw = gh, gw
-                d.Ho, d.Wo, d.oys, d.oyo, d.oxs, d.oxo = 2 * gh, 2 * gw, 2, py, 2, px
-            d.y, d.y0, d.y1 = y, hip.NULL_VIEW, y1
-            d.alpha, d.act = alpha, hip.ACT_NONE
-            d.r1, d.r1_nc, d.beta1 = r1, r1_nc, beta1
-            d.r2, d.r2_nc, d.beta2 = r2, r2_nc, beta2
-            d.accumulate = accumulate
-            d.m, d.m_c0, d.m_c1 = m, m_c0, m_c1
-            d.m_relu = m_relu
-        self.keep.append(arr)
-        if len(classes) == 1:
-            L.add(hip.lib().ssr_conv2d, C.byref(arr[0]), what=f"conv dgrad {name}")
-        else:   # the four parity classes in one launch (csrc/conv.hip, ssr_conv2d_batch)
-            L.add(hip.lib().ssr_conv2d_batch, arr, len(classes), what=f"conv dgrad {name}")
+        common = dict(dtype=self.dt, x=dy, N=self.N, Hi=gh, Wi=gw, Cin=rup(s.cout, 8) if cin_dy is None else cin_dy, CoutPad=cin_pad_o,
+                      Cout=s.cin if cout is None else cout, Gh=gh, Gw=gw, y=y, y1=y1, alpha=alpha, r1=r1, r1_nc=r1_nc, beta1=beta1,
+                      r2=r2, r2_nc=r2_nc, beta2=beta2, accumulate=accumulate, m=m, m_c0=m_c0, m_c1=m_c1, m_relu=m_relu)
+        if s.stride == 1:
+            d = conv_desc(w=wbase, KH=s.k, **common)
+            self.keep.append(d)
+            L.add(hip.lib().ssr_conv2d, C.byref(d), what=f"conv dgrad {name}")
+            return
+        # class (py, px): the 2x2 taps of that parity, written to every second output row / column; the four in one launch
+        # (csrc/conv.hip, ssr_conv2d_batch)
+        arr = self.array([conv_desc(w=wbase + (py * 2 + px) * 4 * cin_pad_o * cout_pad_i * esz, KH=2, pad_y=1 - py, pad_x=1 - px,
+                                    Ho=2 * gh, Wo=2 * gw, oys=2, oyo=py, oxs=2, oxo=px, **common) for py in (0, 1) for px in (0, 1)])
+        L.add(hip.lib().ssr_conv2d_batch, arr, len(arr), what=f"conv dgrad {name}")
 
 
 def gather_dgrad(cb: "_ConvBuilder", L: Launcher, prefix: str, k: int, x1: View, c1: int, x2: View, c2: int, gh: int,
                  gw: int, y: View, cout: int, **epi):
-    """One launch of the gather-form dense-block backward (ParamStore.add_rdb_gather)."""
+    """One launch of the gather-form dense-block backward (ParamStore.add_rdb_gather): `epi` = r1 / r2 / m fields of the epilogue."""
     st = cb.store
-    d = ConvDesc()
-    d.dtype = cb.dt
-    d.N, d.Hi, d.Wi, d.up = cb.N, gh, gw, 1
-    if c1 > 0:
-        d.x, d.Cin, d.x2, d.Cin2 = x1, c1, x2, c2
-    else:
-        d.x, d.Cin, d.x2, d.Cin2 = x2, c2, hip.NULL_VIEW, 0
-    d.w = st.gather[(prefix, k)].data_ptr()
-    d.CoutPad = st.gather_rows[(prefix, k)]
-    d.bias = None
-    d.KH = d.KW = 3
-    d.stride, d.pad_y, d.pad_x = 1, 1, 1
-    d.Gh, d.Gw = gh, gw
-    d.Ho, d.Wo, d.oys, d.oyo, d.oxs, d.oxo = gh, gw, 1, 0, 1, 0
-    d.Cout = cout
-    d.y, d.y0, d.y1 = y, hip.NULL_VIEW, hip.NULL_VIEW
-    d.alpha, d.act = 1.0, hip.ACT_NONE
-    d.r1, d.r1_nc, d.beta1 = epi.get("r1", hip.NULL_VIEW), epi.get("r1_nc", 0), epi.get("beta1", 0.0)
-    d.r2, d.r2_nc, d.beta2 = epi.get("r2", hip.NULL_VIEW), epi.get("r2_nc", 0), epi.get("beta2", 0.0)
-    d.accumulate = 0
-    d.m, d.m_c0, d.m_c1 = epi.get("m", hip.NULL_VIEW), epi.get("m_c0", 0), epi.get("m_c1", 0)
+    src = dict(x=x1, Cin=c1, x2=x2, Cin2=c2) if c1 > 0 else dict(x=x2, Cin=c2)
+    d = conv_desc(dtype=cb.dt, N=cb.N, Hi=gh, Wi=gw, w=st.gather[(prefix, k)].data_ptr(), CoutPad=st.gather_rows[(prefix, k)], KH=3,
+                  Gh=gh, Gw=gw, Cout=cout, y=y, **src, **epi)
     cb.keep.append(d)
     L.add(hip.lib().ssr_conv2d, C.byref(d), what=f"conv dgrad-gather {prefix}.slice{k}")
     return d
@@ -487,11 +463,11 @@ def gather_dgrad(cb: "_ConvBuilder", L: Launcher, prefix: str, k: int, x1: View,
 # float64 oracle's, the same with a threshold of 1e-4 and of 1e-3 (gpurun_out/r04m_*; tests/test_gpu_baseline_shapes.py
 # "fp32x3-fix"), conv_first.weight 24.5 % -> 11.4 % of elements outside the 1e-3 gate.  Unconditional gradient parity needs
 # fp32-accurate products in EVERY layer (the exact fp32 mode; or six bf16 products per fp32 product).
-X3_FIXUP = [os.environ.get("SSR_X3_FIXUP", "0") == "1"]
-X3_FIX_THR = [float(os.environ.get("SSR_X3_FIX_THR", "1e-4"))]
+X3_FIXUP = [hip.env_on("SSR_X3_FIXUP")]
+X3_FIX_THR = [float(hip.env_str("SSR_X3_FIX_THR", "1e-4"))]
 X3_FIX_CAP = 8192
 
-_DET = [os.environ.get("SSR_DETERMINISTIC", "0") == "1"]
+_DET = [hip.env_on("SSR_DETERMINISTIC")]
 
 
 def deterministic() -> bool:
@@ -536,19 +512,21 @@ class WgradBatch:
     arena, after one ssr_split_bf16_multi pass over the distinct parent buffers)."""
 
     # by kernel size: the 4x4 layers have few (co, ci) tiles -> more pixel splits (SSR_WGRAD_T3 / _T4: tuning hooks)
-    MAX_TILES_PER_ITEM = {3: int(os.environ.get("SSR_WGRAD_T3", "128")), 4: int(os.environ.get("SSR_WGRAD_T4", "64"))}
+    MAX_TILES_PER_ITEM = {3: hip.env_int("SSR_WGRAD_T3", 128), 4: hip.env_int("SSR_WGRAD_T4", 64)}
 
-    def __init__(self, dtype: int, k: int, stride: int, force_atomic: bool = False, det: Optional[bool] = None):
-        self.dtype, self.k, self.stride = dtype, k, stride
+    def __init__(self, dtype: int, k: int, stride: int, force_atomic: bool = False, det: Optional[bool] = None, device="cuda"):
+        """`device`: where the tables and partial buffers go - the device of the buffers the layers point into"""
+        self.dtype, self.k, self.stride, self.device = dtype, k, stride, torch.device(device)
         self.force_atomic = force_atomic       # another launch accumulates into the same gradients concurrently
         # element type the wgrad kernel reads: bf16 planes of the fp32 buffers in the split passes, the fp32 buffers themselves in the fused 3x3 kernel
-        fused = dtype == hip.F32X3 and ((k == 3 and stride == 1 and os.environ.get("SSR_X3_WGRAD_FUSED", "1") == "1")
-                                        or (k == 4 and stride == 2 and os.environ.get("SSR_X3_WGRAD_FUSED4", "1") == "1"))
+        fused = dtype == hip.F32X3 and ((k == 3 and stride == 1 and hip.env_on("SSR_X3_WGRAD_FUSED", True))
+                                        or (k == 4 and stride == 2 and hip.env_on("SSR_X3_WGRAD_FUSED4", True)))
         self.kdt = hip.F32X3 if fused else hip.BF16 if dtype == hip.F32X3 else dtype
         self.layers: List[WgradLayer] = []
         self.items: List[WgradItem] = []
         self.layer_tab = self.item_tab = None
         self.split_tabs: List[torch.Tensor] = []
+        self.split_layers: List[List[WgradLayer]] = []      # the host list behind each of split_tabs
         self.split_tab = None
         self.splits: List[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = []
         # deterministic mode: a layer that is split over pixel ranges gets one layer-table entry PER SPLIT whose dw / db point
@@ -559,157 +537,41 @@ class WgradBatch:
         self.virtual = set()                  # indices of the per-split entries of self.layers
         self._partials = []                   # (dw_ptr, db_ptr, wsize, bsize, [virtual layer indices])
         self.partial = self.reduce_tab = None
+        self.reduce_items: List[ReduceItem] = []
         self.n_reduce = self.max_reduce = 0
 
-    def add(self, x: View, dy: View, N, hi, wi, up, cin, cout, gh, gw, alpha, dw_ptr, cin_w, db_ptr):
-        li = len(self.layers)
-        self.layers.append(WgradLayer(x, dy, N, hi, wi, up, cin, cout, 1, 1, gh, gw, alpha, dw_ptr, cin_w, db_ptr))
-        tiles = hip.lib().ssr_wgrad_tiles(N, gh, gw, self.kdt, self.k)
+    def add(self, x: View, dy: View, N, hi, wi, up, cin, cout, gh, gw, alpha, dw_ptr, cin_w, db_ptr, pad=1):
+        lib = hip.lib()
+        entry = lambda dw, db: WgradLayer(x, dy, N, hi, wi, up, cin, cout, pad, pad, gh, gw, alpha, dw, cin_w, db)    # noqa: E731
+        tiles = lib.ssr_wgrad_tiles(N, gh, gw, self.kdt, self.k)
         # (the fused fp32x3 kernel walks 8 x 16-pixel tiles, half the bf16 kernel's: the same pixels per item)
         splits = max(1, -(-tiles // (self.MAX_TILES_PER_ITEM.get(self.k, 128) * (2 if self.kdt == hip.F32X3 else 1))))
-        per = -(-tiles // splits)
-        lsp = [li] * splits                   # layer-table entry of split sp
-        if self.det and splits > 1:
-            lsp = []
-            for sp in range(splits):          # dw / db are patched in finalize(), when the partial buffer exists
-                lsp.append(len(self.layers))
-                self.virtual.add(len(self.layers))
-                self.layers.append(WgradLayer(x, dy, N, hi, wi, up, cin, cout, 1, 1, gh, gw, alpha, None, cin_w, None))
-            self._partials.append((dw_ptr, db_ptr, cout * cin_w * self.k * self.k, cout if db_ptr else 0, lsp))
-        for co0 in range(0, cout, 32):
-            for ci0 in range(0, cin_w, hip.lib().ssr_wgrad_ci_tile(self.kdt, self.k)):
-                for sp in range(splits):
-                    b, e = sp * per, min(tiles, (sp + 1) * per)
-                    if b < e:
-                        atomic = 1 if ((splits > 1 and not self.det) or self.force_atomic) else 0
-                        self.items.append(WgradItem(lsp[sp], co0, ci0, b, e, atomic, 1, lsp[sp], co0))
+        entries = [len(self.layers)] * splits         # layer-table entry of split sp
+        self.layers.append(entry(dw_ptr, db_ptr))
+        if self.det and splits > 1:                   # dw / db of the per-split entries are patched in finalize(), when the partial buffer exists
+            entries = list(range(len(self.layers), len(self.layers) + splits))
+            self.virtual.update(entries)
+            self.layers += [entry(None, None) for _ in entries]
+            self._partials.append((dw_ptr, db_ptr, cout * cin_w * self.k * self.k, cout if db_ptr else 0, entries))
+        atomic = 1 if ((splits > 1 and not self.det) or self.force_atomic) else 0
+        self.items += wgrad_plan.cut(entries, cout, cin_w, lib.ssr_wgrad_ci_tile(self.kdt, self.k), tiles, atomic)
 
-    def _weight(self, it):
-        """MFMA work of an item in (tile, 32-ci half, 32-co plane) units"""
-        L = self.layers[it.layer]
-        return (it.tile_end - it.tile_begin) * (2 if L.Cin_w - it.ci0 > 32 else 1) * max(1, it.nco)
-
-    # cycles per 16 x 16-pixel tile and per write-out of the bf16 3x3 kernel (tools/wgrad_body_probe.hip, MI355X): the loaders'
-    # fetch rate (~12.5 B/clk per CU) bounds both kinds of item, so a single costs 3/4 of a pair for at most half of its products
-    COST_TILE = {2: 5900, 1: 4300}
-    COST_WRITEOUT = 25000
-
-    @property
-    def N_CU(self):
-        """compute units of the device the launch will run on (MI355X: 256) - from the device properties, not a constant"""
-        return _device_cus()[0]
-
-    @property
-    def N_XCD(self):
-        return _device_cus()[1]
+    # the planning is wgrad_plan's: these bind it to this batch's layers and to the CU / XCD counts of the device
+    def _pair(self, items):
+        return wgrad_plan.pair(self.layers, items)
 
     def _cost(self, it):
-        nco = max(1, it.nco)
-        return (it.tile_end - it.tile_begin) * self.COST_TILE[nco] + nco * self.COST_WRITEOUT
+        return wgrad_plan.cost(it)
 
     def _makespan(self, items):
-        """workgroups are handed to the CUs in index order as CUs become free: list scheduling, longest first"""
-        import heapq
-        free = [0] * self.N_CU
-        for c in sorted((self._cost(it) for it in items), reverse=True):
-            heapq.heapreplace(free, free[0] + c)
-        return max(free)
+        return wgrad_plan.makespan(items, _device_cus()[0])
 
     def _balance(self, items):
-        """Pixel-range granularity of the items, chosen by simulating the launch: a generator launch is ~2.2 paired items per
-        CU, and whole items left 19 % of the CU time idle at the end (the singles, 3/4 of a pair each, are dealt last).  Finer
-        items cost a write-out each (fp32 atomics of the whole (co, ci) tile), so the cut is as coarse as the simulation allows."""
-        def cut(its, t_pair, t_single):
-            out = []
-            for it in its:
-                n, t = it.tile_end - it.tile_begin, (t_pair if it.nco == 2 else t_single)
-                parts = max(1, -(-n // t))
-                per = -(-n // parts)
-                for b in range(it.tile_begin, it.tile_end, per):
-                    out.append(WgradItem(it.layer, it.co0, it.ci0, b, min(it.tile_end, b + per), 1 if parts > 1 else it.atomic,
-                                         it.nco, it.layer_b, it.co0_b))
-            return out
-        best = None
-        for t_pair in (128, 64, 32):
-            for t_single in (128, 64, 32, 16):
-                cand = cut(items, t_pair, t_single)
-                m = self._makespan(cand)
-                if best is None or m < best[0] * 0.98:         # finer only if it buys 2 %
-                    best = (m, cand, t_pair, t_single)
-        self.balance_choice = best[2:] + (best[0], self._makespan(items))
-        return best[1]
-
-    def _pair(self, items):
-        """Two 32-channel blocks of output gradients that are contracted with the SAME input patch share one work item
-        (csrc/wgrad_bf16.hip, Wg3: every X fragment read from LDS then feeds two MFMAs).  Same x view, ci0, geometry, pixel
-        tiles and the same number of valid input channels; the blocks may belong to different layers — a dense block's
-        conv1..conv4 all read x and produce dpre1..dpre4 (rrdbnet_arch.py:37-41) — or be the halves of one 64-output conv."""
-        groups = {}
-        for it in items:
-            L = self.layers[it.layer]
-            key = (L.x.p, L.x.cs, L.x.coff, it.ci0, it.tile_begin, it.tile_end, L.N, L.Hi, L.Wi, L.up, L.Gh, L.Gw, L.pad_y, L.pad_x,
-                   min(64, L.Cin_w - it.ci0) > 32, min(64, L.Cin - it.ci0), it.atomic)
-            groups.setdefault(key, []).append(it)
-        out = []
-        for g in groups.values():
-            for a, b in zip(g[0::2], g[1::2]):
-                out.append(WgradItem(a.layer, a.co0, a.ci0, a.tile_begin, a.tile_end, a.atomic, 2, b.layer, b.co0))
-            if len(g) % 2:
-                out.append(g[-1])
-        return out
-
-
-    def _xcd_order(self, items):
-        """Workgroup b runs on XCD b % 8 and every XCD has its own L2.  Items that read the same input buffer over the same
-        pixel tiles (a dense block: 14 (conv, co, ci) items over one 192-channel buffer and its gradient) are dealt to ONE
-        XCD, next to each other in its queue, so that they walk the tiles together and a line of x / dy is fetched once per
-        group instead of once per item (layer-major order spread the 14 over all eight L2s: 3.39 GB per launch for
-        ~0.6 GB of distinct lines, profiles/r03k_traffic.json)."""
-        weight = self._weight
-        groups = {}
-        for it in items:
-            groups.setdefault((self.layers[it.layer].x.p, it.tile_begin, it.tile_end), []).append(it)
-        queues, load = [[] for _ in range(self.N_XCD)], [0] * self.N_XCD
-        for g in sorted(groups.values(), key=lambda g: -sum(weight(i) for i in g)):      # heaviest group first, to the least loaded XCD
-            q = min(range(self.N_XCD), key=lambda j: (load[j], j))
-            queues[q] += sorted(g, key=lambda i: -weight(i))
-            load[q] += sum(weight(i) for i in g)
-        # block index = 8 * position + xcd has to be dense: level the queue lengths with items from the tails
-        while True:
-            lo, hi = min(queues, key=len), max(queues, key=len)
-            if len(hi) - len(lo) <= 1:
-                break
-            lo.append(hi.pop())
-        queues.sort(key=lambda q: -len(q))
-        return [q[j] for j in range(len(queues[0])) for q in queues if j < len(q)]
+        items, self.balance_choice = wgrad_plan.balance(items, _device_cus()[0])
+        return items
 
     def _cost_xcd_order(self, items):
-        """Longest items first - what list scheduling over 256 CUs needs - and INSIDE every run of equal-cost items (a generator launch is a few
-        cost classes of hundreds of identical items: the dense blocks are all alike) the items that read the same buffers over the same tiles are
-        dealt to ONE XCD (block b runs on XCD b % 8), next to each other in its queue: the L2 saving of `_xcd_order` (round 6: 4.43 -> 3.02 GB of
-        HBM reads per 3x3 launch) without its cost (+0.7 ms per step: whole groups per XCD unbalance the tail)."""
-        items = sorted(items, key=lambda it: -self._cost(it))
-        nx = self.N_XCD
-        out = []
-        i = 0
-        while i < len(items):
-            c = self._cost(items[i])
-            j = i
-            while j < len(items) and self._cost(items[j]) == c:
-                j += 1
-            groups = {}
-            for it in items[i:j]:
-                groups.setdefault((self.layers[it.layer].x.p, it.tile_begin, it.tile_end), []).append(it)
-            queues = [[] for _ in range(nx)]
-            for g in sorted(groups.values(), key=len, reverse=True):
-                min(queues, key=len).extend(g)
-            for pos in range(len(out), len(out) + (j - i)):
-                q = queues[pos % nx]
-                if not q:
-                    q = max(queues, key=len)
-                out.append(q.pop(0))
-            i = j
-        return out
+        return wgrad_plan.order_hybrid(self.layers, items, _device_cus()[1])
 
     def _twin(self, v: View, which: int) -> View:
         parent = hip.parent_of(v)
@@ -725,15 +587,14 @@ class WgradBatch:
         """one fp32 buffer [layer][split][dW | db] for the per-split partial gradients + the table of fixed-order sums"""
         if not self._partials:
             return
-        dev = torch.device("cuda", torch.cuda.current_device())
         total, plan = 0, []
         for dw_ptr, db_ptr, wsize, bsize, lsp in self._partials:
             stride = rup(wsize + bsize, 4)
             plan.append((total, stride))
             total += stride * len(lsp)
-        self.partial = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.partial = torch.zeros(total, dtype=torch.float32, device=self.device)
         base = self.partial.data_ptr()
-        red = []
+        red = self.reduce_items = []
         for (dw_ptr, db_ptr, wsize, bsize, lsp), (off, stride) in zip(self._partials, plan):
             for sp, li in enumerate(lsp):
                 self.layers[li].dw = base + 4 * (off + sp * stride)
@@ -741,26 +602,22 @@ class WgradBatch:
             red.append(ReduceItem(dw_ptr, base + 4 * off, wsize, stride, len(lsp), 0))
             if bsize:
                 red.append(ReduceItem(db_ptr, base + 4 * (off + wsize), bsize, stride, len(lsp), 0))
-        self.reduce_tab, self.n_reduce = hip.device_table(red), len(red)
+        self.reduce_tab, self.n_reduce = hip.device_table(red, self.device), len(red)
         self.max_reduce = max(r.n for r in red)
 
     def finalize(self):
         if not self.layers:
             return
         self._alloc_partials()
-        if hip.lib().ssr_wgrad_co_tile(self.kdt, self.k) == 64 and os.environ.get("SSR_WGRAD_PAIR", "1") == "1":
+        if hip.lib().ssr_wgrad_co_tile(self.kdt, self.k) == 64 and hip.env_on("SSR_WGRAD_PAIR", True):
             self.items = self._pair(self.items)
-            if os.environ.get("SSR_WGRAD_BALANCE", "0") == "1":
+            if hip.env_on("SSR_WGRAD_BALANCE"):
                 self.items = self._balance(self.items)
-        # hybrid (default since round 6): longest items first, equal-cost runs dealt to the XCDs by buffer group - 4.44 -> 3.09 GB of HBM reads per
-        # 3x3 launch at the same step time (25.36 / 25.42 / 25.40 against 25.40 / 25.46 / 25.35 ms, call r06x3); heavy: longest first only (rounds 3-5);
-        # xcd: whole buffer groups per XCD (3.02 GB, +0.7 ms per step: the tail is unbalanced)
-        order = os.environ.get("SSR_WGRAD_ORDER", "hybrid")
-        self.items = self._xcd_order(self.items) if order == "xcd" else self._cost_xcd_order(self.items) if order == "hybrid" else \
-            sorted(self.items, key=lambda it: -self._cost(it))
-        self.item_tab = hip.device_table(self.items)
+        order = wgrad_plan.ORDERS.get(hip.env_str("SSR_WGRAD_ORDER", "hybrid"), wgrad_plan.order_heavy)
+        self.items = order(self.layers, self.items, _device_cus()[1])
+        self.item_tab = hip.device_table(self.items, self.device)
         if self.kdt != hip.BF16 or self.dtype == hip.BF16:
-            self.layer_tab = hip.device_table(self.layers)
+            self.layer_tab = hip.device_table(self.layers, self.device)
             return
         # three passes over hi/lo planes; the bias gradient (sum of dy) comes out of the first two (dy_hi + dy_lo)
         for xi, dyi, with_bias in ((0, 0, True), (0, 1, True), (1, 0, False)):
@@ -768,7 +625,8 @@ class WgradBatch:
             for L in self.layers:
                 tab.append(WgradLayer(self._twin(L.x, xi), self._twin(L.dy, dyi), L.N, L.Hi, L.Wi, L.up, L.Cin, L.Cout, L.pad_y,
                                       L.pad_x, L.Gh, L.Gw, L.alpha, L.dw, L.Cin_w, L.db if with_bias else None))
-            self.split_tabs.append(hip.device_table(tab))
+            self.split_layers.append(tab)
+            self.split_tabs.append(hip.device_table(tab, self.device))
         self.layer_tab = self.split_tabs[0]
 
     def launch(self, L: Launcher):
@@ -785,7 +643,7 @@ class WgradBatch:
         if self.dtype == hip.F32X3 and self.kdt == hip.BF16:
             if all(p.numel() % 8 == 0 for p, _, _ in self.splits):          # every buffer of the batch in ONE launch (ssr_split_bf16_multi)
                 if self.split_tab is None:
-                    self.split_tab = hip.device_table([hip.SplitItem(p.data_ptr(), h.data_ptr(), l.data_ptr(), p.numel()) for p, h, l in self.splits])
+                    self.split_tab = hip.device_table([hip.SplitItem(p.data_ptr(), h.data_ptr(), l.data_ptr(), p.numel()) for p, h, l in self.splits], self.device)
                 L.add(lib.ssr_split_bf16_multi, self.split_tab.data_ptr(), len(self.splits), max(p.numel() for p, _, _ in self.splits),
                       what="split bf16")
             else:
@@ -827,6 +685,87 @@ def generator_specs(num_in_ch, num_out_ch=3, scale=4, num_feat=64, num_block=23,
     return specs
 
 
+class _WgradSchedule:
+    """When the weight gradients of the generator's 3x3 layers are launched.  The backward records its dgrad chain on `launcher` and
+    the layers whose gradient buffers it has finished on `batch`; close() ends the batch and opens the next:
+      default          ONE batched launch after the last dgrad;
+      SSR_WGRAD_CHUNKS n batches, each forked onto a side stream as soon as the gradient buffers it reads are final, beside the
+                       remaining (strictly sequential) dgrad chain;
+      segments > 1     data parallel: the backward is cut into SEGMENTS, each = a stretch of the dgrad chain followed IN LINE by the
+                       weight-gradient batch of the layers it has finished; the caller exchanges a segment's slice of the gradient
+                       arena while the next segment runs (train_step: one all-reduce per segment on the comm stream) — the bucketed
+                       overlap of the reference's DDP (README.md:159, options.py:65-81) on flat arenas.  Arena order is the
+                       state_dict's (conv_first, body.0 .. body.nb-1, conv_body, conv_up*, conv_hr, conv_last) and the backward
+                       walks it from the end, so a segment's parameters are one contiguous range."""
+
+    def __init__(self, store: ParamStore, B: int, n_rdb: int, atomic: bool, det: bool, segments: int):
+        self.store, self.B = store, B
+        self.n_seg = max(1, int(segments))
+        self.n_chunks = self.n_seg if self.n_seg > 1 else max(1, hip.env_int("SSR_WGRAD_CHUNKS", 1))
+        self.cuts = {round(n_rdb * q / self.n_chunks) for q in range(1, self.n_chunks)}     # close a batch before RDB index r in `cuts`
+        self._new = lambda: WgradBatch(store.dtype, 3, 1, atomic, det=det, device=store.device)
+        self.launcher, self.batch = Launcher(), self._new()
+        self.batches: List[WgradBatch] = []         # the closed ones, in launch order
+        self.segments = []                          # [(Launcher, arena offset, arena elements)]
+        self._hi = store.numel
+
+    def add(self, name, x: View, dy: View, hi, wi, up, gh, gw, alpha=1.0, cin=None):
+        self.batch.add(x, dy, self.B, hi, wi, up, gh=gh, gw=gw, alpha=alpha, **wgrad_args(self.store, name, cin))
+
+    def close(self, next_first_key=None):
+        """`next_first_key`: the first parameter (arena order) of the layers added so far - where this segment's slice begins"""
+        st, wgb = self.store, self.batch
+        wgb.finalize()
+        if self.n_seg > 1:
+            wgb.launch(self.launcher)                      # in line: the segment ends when its weight gradients are final
+            lo = st.offsets[next_first_key][0] if next_first_key else 0
+            hi = self._hi
+            # the slice [lo, hi) of the gradient arena is what the caller exchanges behind this segment: it must be non-empty
+            # and hold EVERY gradient this segment's batch writes (arena order = backward walk from the end; a spec order
+            # that stopped matching it would all-reduce the wrong slice silently)
+            assert 0 <= lo < hi <= st.numel, (next_first_key, lo, hi)
+            g0, esz = st.grad.data_ptr(), st.grad.element_size()
+            for iw, Lw in enumerate(wgb.layers):
+                if iw in wgb.virtual:          # per-split partial buffers of the deterministic mode (reduced into the arena in line)
+                    continue
+                for ptr in (Lw.dw, Lw.db):
+                    if ptr:
+                        off = (int(ptr) - g0) // esz
+                        assert lo <= off < hi, f"weight gradient at arena offset {off} outside its segment [{lo}, {hi})"
+            self.segments.append((self.launcher, lo, hi - lo))
+            self._hi = lo
+            self.launcher = Launcher()
+        elif self.n_chunks > 1:
+            sub = Launcher()
+            wgb.launch(sub)
+            self.launcher.fork(sub, what="wgrad chunk")
+        else:
+            wgb.launch(self.launcher)
+        self.batches.append(wgb)
+        self.batch = self._new()
+
+    def finish(self) -> Launcher:
+        """close the last batch -> the whole backward"""
+        self.close()
+        if self.n_seg == 1:
+            if self.n_chunks > 1:
+                self.launcher.join()
+            return self.launcher
+        whole = Launcher()      # the segments in order (eager / instrumented runs; the step runs them one by one)
+        for L, _, _ in self.segments:
+            whole.calls.extend(L.calls)
+        assert sum(n for _, _, n in self.segments) == self.store.numel and self.segments[-1][1] == 0
+        return whole
+
+
+def rdb_epilogue(j: int, x_rrdb: View, backward: bool = False):
+    """(alpha5, beta1, r2, beta2) of the launch that closes RDB j (0..2) of an RRDB.  Forward: x5*0.2 + x (rrdbnet_arch.py:44); the third
+    also closes the RRDB, (x5*0.2 + x)*0.2 + x_rrdb (:44,:68).  Backward (alpha5 scales conv5's part of the gathered weights and its
+    weight gradient; beta1 the gradient arriving over the `+ x` path): d x_rrdb += d out_rrdb (:68) lands in the FIRST RDB's launch."""
+    alpha5, beta1 = (0.04, 0.2) if j == 2 else (0.2, 1.0)
+    return (alpha5, beta1, x_rrdb, 1.0) if j == (0 if backward else 2) else (alpha5, beta1, hip.NULL_VIEW, 0.0)
+
+
 class GeneratorPlan:
     """SSR_RRDBNet on NHWC buffers for a fixed (B, H, W)."""
 
@@ -835,7 +774,7 @@ class GeneratorPlan:
         (ssr_rdb_desc.w_next).  Measured r01 (B=16): the warm-up loads compete with the weight stream of the running
         launch, dense-block kernels 3.73 -> 4.08 ms per step, so it is opt-in (SSR_RDB_PREFETCH=1)."""
         esz = 2  # bf16
-        if os.environ.get("SSR_RDB_PREFETCH", "0") != "1":
+        if not hip.env_on("SSR_RDB_PREFETCH"):
             return
         for cur, nxt in zip(descs[:-1], descs[1:]):
             for k in range(5):
@@ -876,8 +815,10 @@ class GeneratorPlan:
         self.hr = z(B, self.Ho, self.Wo, nf)
         self.out = out_buf if out_buf is not None else z(B, self.Ho, self.Wo, rup(num_out_ch, 8))
         assert self.out.shape[:3] == (B, self.Ho, self.Wo)
-        cb = self._cb = _ConvBuilder(store, B)
-        self._cb = cb
+        # feat must survive until conv_body's trunk add; with rotating buffers (inference) keep a copy
+        self.feat = self.bufs[0] if n_bufs == n_rdb else z(B, H, W, nf)
+        self._cb = _ConvBuilder(store, B)
+        self._rdb_descs = []
         # fp32x3, SSR_X3_CHAIN=1 (OFF by default): the dense block's conv1..conv4 (and slices 4..1 of its backward) as one persistent
         # chain launch each (csrc/conv_x3c.hip); the chain's tickets / epoch / flag words live in a small device buffer owned by THIS
         # plan's launches (one stream at a time).  Built and measured in round 6 - and slower than the four
@@ -885,66 +826,15 @@ class GeneratorPlan:
         # (call r06i, same box): what the removed launch boundaries save (gap + wave start + first loads) the hand-over spends again
         # (write-through stores drained before the flag, flag visibility, the neighbours' skew) - DESIGN.md lesson 63.
         self._chain_state = None
-        if (self.dt == hip.F32X3 and nf == 64 and gc == 32 and not X3_FIXUP[0] and os.environ.get("SSR_X3_CHAIN", "0") == "1"):
+        if (self.dt == hip.F32X3 and nf == 64 and gc == 32 and not X3_FIXUP[0] and hip.env_on("SSR_X3_CHAIN")):
             nbytes = int(hip.lib().ssr_conv2d_chain_state_bytes(B, H, W))
             self._chain_state = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=dev)
-        # ------------------------------------------------------------------ forward
-        F = Launcher()
-        buf = lambda r: self.bufs[r % n_bufs]
-        # feat must survive until conv_body's trunk add; with rotating buffers (inference) keep a copy
-        self.feat = self.bufs[0] if n_bufs == n_rdb else z(B, H, W, nf)
-        cb.conv(F, "conv_first", view(self.xin), H, W, view(buf(0), 0),
-                y0=hip.NULL_VIEW if n_bufs == n_rdb else view(self.feat))
         # bf16, nf = 64, gc = 32: one fused launch per dense block (csrc/rdb_fwd.hip); otherwise 5 convs
-        self.fused_rdb = (self.dt == hip.BF16 and nf == 64 and gc == 32 and os.environ.get("SSR_FUSED_RDB", "1") != "0")
-        self._rdb_descs = []
-        for r in range(n_rdb):
-            i, j = divmod(r, 3)
-            p = f"body.{i}.rdb{j + 1}"
-            cur = buf(r)
-            dst = view(self.body_out) if r == n_rdb - 1 else view(buf(r + 1), 0)
-            if self.fused_rdb:
-                rd = hip.RdbDesc()
-                rd.dtype, rd.N, rd.H, rd.W = self.dt, B, H, W
-                rd.inp, rd.slices, rd.out, rd.mask = view(cur, 0), view(cur, 0), dst, hip.NULL_VIEW
-                for k in range(5):
-                    rd.w[k] = store.packed_fwd[f"{p}.conv{k + 1}"].data_ptr()
-                    rd.bias[k] = store.ptr(f"{p}.conv{k + 1}.bias")
-                rd.w[4] = store.add_repack(f"{p}.conv5", 16).data_ptr()   # conv5 streams in 16-channel half chunks
-                if j < 2:
-                    rd.alpha5, rd.beta1, rd.r2, rd.beta2 = 0.2, 1.0, hip.NULL_VIEW, 0.0
-                else:
-                    rd.alpha5, rd.beta1, rd.r2, rd.beta2 = 0.04, 0.2, view(buf(r - 2), 0), 1.0
-                self._rdb_descs.append(rd)
-                F.add(hip.lib().ssr_rdb_forward, C.byref(rd), what=f"rdb fwd {p}")
-                continue
-            # conv1..conv4: each reads the channel prefix the earlier ones extend.  fp32x3: ONE persistent launch for the four
-            # (csrc/conv_x3c.hip, ssr_conv2d_chain; falls back to four launches by itself where the chain does not qualify)
-            tmp = Launcher() if self._chain_state is not None else F
-            ds = [cb.conv(tmp, f"{p}.conv{k}", view(cur, 0), H, W, view(cur, nf + (k - 1) * gc), act=hip.ACT_LRELU,
-                          cin=nf + (k - 1) * gc) for k in range(1, 5)]
-            if tmp is not F:
-                self._add_chain(F, ds, f"conv chain fwd {p}.conv1-4")
-            if j < 2:   # x5*0.2 + x                                            (rrdbnet_arch.py:44)
-                cb.conv(F, f"{p}.conv5", view(cur, 0), H, W, dst, alpha=0.2, r1=view(cur, 0), r1_nc=nf, beta1=1.0,
-                        cin=cd)
-            else:       # (x5*0.2 + x)*0.2 + x_rrdb                              (rrdbnet_arch.py:44,68)
-                cb.conv(F, f"{p}.conv5", view(cur, 0), H, W, dst, alpha=0.04, r1=view(cur, 0), r1_nc=nf, beta1=0.2,
-                        r2=view(buf(r - 2), 0), r2_nc=nf, beta2=1.0, cin=cd)
-        self._link_rdb_prefetch(self._rdb_descs)
-        # feat + conv_body(body)                                                 (rrdbnet_arch.py:124-125)
-        cb.conv(F, "conv_body", view(self.body_out), H, W, view(self.trunk), r1=view(self.feat, 0), r1_nc=nf, beta1=1.0)
-        src, sh, sw = self.trunk, H, W
-        for i, nm in enumerate(self.up_names):  # lrelu(conv(nearest x2))       (rrdbnet_arch.py:127-128)
-            cb.conv(F, nm, view(src), sh, sw, view(self.ups[i]), up=2, act=hip.ACT_LRELU)
-            src, sh, sw = self.ups[i], sh * 2, sw * 2
-        cb.conv(F, "conv_hr", view(src), sh, sw, view(self.hr), act=hip.ACT_LRELU)
-        cb.conv(F, "conv_last", view(self.hr), sh, sw, view(self.out))
-        self.fwd = F
+        self.fused_rdb = (self.dt == hip.BF16 and nf == 64 and gc == 32 and not hip.env_off("SSR_FUSED_RDB"))
+        self.fwd = self._build_forward()
         if not training:
             return
         assert n_bufs == n_rdb
-        # ------------------------------------------------------------------ backward
         # dL/d out (valid: num_out_ch channels); may alias the discriminator's input-gradient buffer
         self.d_out = d_out_buf if d_out_buf is not None else z(B, self.Ho, self.Wo, self.out.shape[-1])
         assert self.d_out.shape == self.out.shape
@@ -955,72 +845,77 @@ class GeneratorPlan:
         self.g_body_out = z(B, H, W, nf)
         self.dbufs = [z(B, H, W, cd) for _ in range(n_rdb)]
         self.g_xin = z(B, H, W, self.xin.shape[-1]) if need_input_grad else None
-        Bk = Launcher()
-        st = store
-        # weight gradients: ONE batched launch after the last dgrad (default), or SSR_WGRAD_CHUNKS = n batches, each forked onto
-        # a side stream as soon as the gradient buffers it reads are final, beside the remaining (strictly sequential) dgrad chain
-        n_chunks = max(1, int(os.environ.get("SSR_WGRAD_CHUNKS", "1")))
-        # data parallel (bwd_segments > 1): the backward is cut into SEGMENTS, each = a stretch of the dgrad chain followed IN LINE
-        # by the weight-gradient batch of the layers it has finished; the caller exchanges a segment's slice of the gradient arena
-        # while the next segment runs (train_step: one all-reduce per segment on the comm stream) — the bucketed overlap of the
-        # reference's DDP (README.md:159, options.py:65-81) on flat arenas.  Arena order is the state_dict's (conv_first, body.0 ..
-        # body.nb-1, conv_body, conv_up*, conv_hr, conv_last) and the backward walks it from the end, so a segment's parameters
-        # are one contiguous range.
-        n_seg = max(1, int(bwd_segments))
-        if n_seg > 1:
-            n_chunks = n_seg
-        cuts = {round(n_rdb * q / n_chunks) for q in range(1, n_chunks)}     # close a batch before RDB index r in `cuts`
-        batches = [WgradBatch(self.dt, 3, 1, wgrad_atomic, det=self.det)]
-        self.bwd_segments = []        # [(Launcher, arena offset, arena elements)]
-        seg_state = {"launcher": Bk, "hi": st.numel}
+        ws = _WgradSchedule(store, B, n_rdb, wgrad_atomic, self.det, bwd_segments)
+        self.bwd = self._build_backward(ws)
+        self._wg_batches, self.bwd_segments = ws.batches, ws.segments
 
-        def add_wg(name, x: View, dy: View, hi, wi, up, gh, gw, alpha=1.0, cin=None):
-            s = st.specs[name]
-            batches[-1].add(x, dy, B, hi, wi, up, rup(s.cin, 8) if cin is None else cin, s.cout, gh, gw, alpha,
-                            st.ptr(name + ".weight", st.grad), s.cin, st.ptr(name + ".bias", st.grad) if s.bias else None)
+    def _rdb_desc(self, inp: View, slices: View, out: View, mask: View, w, bias, alpha5, beta1, r2: View, beta2) -> hip.RdbDesc:
+        """one fused dense-block launch (csrc/rdb_fwd.hip): `w`, `bias` = the five packed weights / biases in the order it runs them"""
+        rd = hip.RdbDesc()
+        rd.dtype, rd.N, rd.H, rd.W = self.dt, self.B, self.H, self.W
+        rd.inp, rd.slices, rd.out, rd.mask = inp, slices, out, mask
+        for k in range(5):
+            rd.w[k], rd.bias[k] = w[k], bias[k]
+        rd.alpha5, rd.beta1, rd.r2, rd.beta2 = alpha5, beta1, r2, beta2
+        self._rdb_descs.append(rd)
+        return rd
 
-        def close_batch(next_first_key=None):
-            nonlocal Bk
-            wgb = batches[-1]
-            wgb.finalize()
-            if n_seg > 1:
-                wgb.launch(Bk)                      # in line: the segment ends when its weight gradients are final
-                lo = st.offsets[next_first_key][0] if next_first_key else 0
-                hi = seg_state["hi"]
-                # the slice [lo, hi) of the gradient arena is what the caller exchanges behind this segment: it must be non-empty
-                # and hold EVERY gradient this segment's batch writes (arena order = backward walk from the end; a spec order
-                # that stopped matching it would all-reduce the wrong slice silently)
-                assert 0 <= lo < hi <= st.numel, (next_first_key, lo, hi)
-                g0, esz = st.grad.data_ptr(), st.grad.element_size()
-                for iw, Lw in enumerate(wgb.layers):
-                    if iw in wgb.virtual:          # per-split partial buffers of the deterministic mode (reduced into the arena in line)
-                        continue
-                    for ptr in (Lw.dw, Lw.db):
-                        if ptr:
-                            off = (int(ptr) - g0) // esz
-                            assert lo <= off < hi, f"weight gradient at arena offset {off} outside its segment [{lo}, {hi})"
-                self.bwd_segments.append((Bk, lo, hi - lo))
-                seg_state["hi"] = lo
-                Bk = Launcher()
-            else:
-                sub = Launcher()
-                wgb.launch(sub)
-                Bk.fork(sub, what="wgrad chunk")
-            batches.append(WgradBatch(self.dt, 3, 1, wgrad_atomic, det=self.det))
+    def _build_forward(self) -> Launcher:
+        cb, store, B, H, W, nf, gc = self._cb, self.store, self.B, self.H, self.W, self.nf, self.gc
+        cd, n_rdb = nf + 4 * gc, 3 * self.nb
+        rotating = len(self.bufs) < n_rdb
+        buf = lambda r: self.bufs[r % len(self.bufs)]      # noqa: E731
+        F = Launcher()
+        cb.conv(F, "conv_first", view(self.xin), H, W, view(buf(0), 0), y0=view(self.feat) if rotating else hip.NULL_VIEW)
+        for r in range(n_rdb):
+            i, j = divmod(r, 3)
+            p = f"body.{i}.rdb{j + 1}"
+            cur = buf(r)
+            dst = view(self.body_out) if r == n_rdb - 1 else view(buf(r + 1), 0)
+            alpha5, beta1, r2, beta2 = rdb_epilogue(j, view(buf(r - 2), 0))
+            if self.fused_rdb:
+                w = [store.packed_fwd[f"{p}.conv{k}"].data_ptr() for k in range(1, 5)]
+                w.append(store.add_repack(f"{p}.conv5", 16).data_ptr())    # conv5 streams in 16-channel half chunks
+                rd = self._rdb_desc(view(cur, 0), view(cur, 0), dst, hip.NULL_VIEW, w, [store.ptr(f"{p}.conv{k}.bias") for k in range(1, 6)],
+                                    alpha5, beta1, r2, beta2)
+                F.add(hip.lib().ssr_rdb_forward, C.byref(rd), what=f"rdb fwd {p}")
+                continue
+            # conv1..conv4: each reads the channel prefix the earlier ones extend.  fp32x3: ONE persistent launch for the four
+            # (csrc/conv_x3c.hip, ssr_conv2d_chain; falls back to four launches by itself where the chain does not qualify)
+            tmp = Launcher() if self._chain_state is not None else F
+            ds = [cb.conv(tmp, f"{p}.conv{k}", view(cur, 0), H, W, view(cur, nf + (k - 1) * gc), act=hip.ACT_LRELU,
+                          cin=nf + (k - 1) * gc) for k in range(1, 5)]
+            if tmp is not F:
+                self._add_chain(F, ds, f"conv chain fwd {p}.conv1-4")
+            cb.conv(F, f"{p}.conv5", view(cur, 0), H, W, dst, alpha=alpha5, r1=view(cur, 0), r1_nc=nf, beta1=beta1,
+                    r2=r2, r2_nc=nf if r2.p else 0, beta2=beta2, cin=cd)
+        self._link_rdb_prefetch(self._rdb_descs)
+        # feat + conv_body(body)                                                 (rrdbnet_arch.py:124-125)
+        cb.conv(F, "conv_body", view(self.body_out), H, W, view(self.trunk), r1=view(self.feat, 0), r1_nc=nf, beta1=1.0)
+        src, sh, sw = self.trunk, H, W
+        for i, nm in enumerate(self.up_names):  # lrelu(conv(nearest x2))       (rrdbnet_arch.py:127-128)
+            cb.conv(F, nm, view(src), sh, sw, view(self.ups[i]), up=2, act=hip.ACT_LRELU)
+            src, sh, sw = self.ups[i], sh * 2, sw * 2
+        cb.conv(F, "conv_hr", view(src), sh, sw, view(self.hr), act=hip.ACT_LRELU)
+        cb.conv(F, "conv_last", view(self.hr), sh, sw, view(self.out))
+        return F
 
-        Ho, Wo = self.Ho, self.Wo
+    def _build_backward(self, ws: _WgradSchedule) -> Launcher:
+        cb, store, B, H, W, nf, gc = self._cb, self.store, self.B, self.H, self.W, self.nf, self.gc
+        cd, n_rdb, Ho, Wo = nf + 4 * gc, 3 * self.nb, self.Ho, self.Wo
+        Bk = ws.launcher
         last_up = self.ups[-1]
         # conv_last / conv_hr
-        add_wg("conv_last", view(self.hr), view(self.d_out), Ho, Wo, 1, Ho, Wo)
+        ws.add("conv_last", view(self.hr), view(self.d_out), Ho, Wo, 1, Ho, Wo)
         cb.dgrad(Bk, "conv_last", view(self.d_out), Ho, Wo, view(self.g_hr), m=view(self.hr), m_c0=0, m_c1=nf)
-        add_wg("conv_hr", view(last_up), view(self.g_hr), Ho, Wo, 1, Ho, Wo)
+        ws.add("conv_hr", view(last_up), view(self.g_hr), Ho, Wo, 1, Ho, Wo)
         cb.dgrad(Bk, "conv_hr", view(self.g_hr), Ho, Wo, view(self.g_ups[-1]), m=view(last_up), m_c0=0, m_c1=nf)
         # upsampling convs, last to first
         for i in reversed(range(self.n_up)):
             nm = self.up_names[i]
             hh, ww = H << (i + 1), W << (i + 1)          # output dims of this conv
             src = self.ups[i - 1] if i > 0 else self.trunk
-            add_wg(nm, view(src), view(self.g_ups[i]), hh // 2, ww // 2, 2, hh, ww)
+            ws.add(nm, view(src), view(self.g_ups[i]), hh // 2, ww // 2, 2, hh, ww)
             cb.dgrad(Bk, nm, view(self.g_ups[i]), hh, ww, view(self.g_tmp[i]))
             if i > 0:   # 2x2 sum back to the pre-upsample grid, masked by lrelu'(ups[i-1])
                 Bk.add(hip.lib().ssr_nearest2x_bwd, view(self.g_tmp[i]), hip.NULL_VIEW, hip.NULL_VIEW,
@@ -1029,43 +924,30 @@ class GeneratorPlan:
             else:       # trunk = feat + conv_body(...) is linear: no mask
                 Bk.add(hip.lib().ssr_nearest2x_bwd, view(self.g_tmp[i]), hip.NULL_VIEW, hip.NULL_VIEW,
                        view(self.g_trunk), hip.NULL_VIEW, self.dt, B, H, W, nf, what="nearest2x_bwd")
-        add_wg("conv_body", view(self.body_out), view(self.g_trunk), H, W, 1, H, W)
+        ws.add("conv_body", view(self.body_out), view(self.g_trunk), H, W, 1, H, W)
         cb.dgrad(Bk, "conv_body", view(self.g_trunk), H, W, view(self.g_body_out))
         # body, last RDB to first
+        fused_bwd = self.fused_rdb and not hip.env_off("SSR_FUSED_RDB_BWD")
         bwd_descs = []
+        d_of = lambda r: view(self.g_body_out) if r == n_rdb - 1 else view(self.dbufs[r + 1], 0)   # noqa: E731  gradient w.r.t. RDB r's output
         for r in reversed(range(n_rdb)):
             i, j = divmod(r, 3)
             p = f"body.{i}.rdb{j + 1}"
-            cur, dcur = self.bufs[r], self.dbufs[r]
-            d_out_r = view(self.g_body_out) if r == n_rdb - 1 else view(self.dbufs[r + 1], 0)
-            if j == 2:
-                d_rrdb = d_out_r            # gradient w.r.t. this RRDB's output
-                a5, b5 = 0.04, 0.2
-            else:
-                rr = 3 * i + 2
-                d_rrdb = view(self.g_body_out) if rr == n_rdb - 1 else view(self.dbufs[rr + 1], 0)
-                a5, b5 = 0.2, 1.0
-            fused_bwd = self.fused_rdb and os.environ.get("SSR_FUSED_RDB_BWD", "1") != "0"
-            if n_chunks > 1 and (r + 1) in cuts:      # everything recorded so far reads buffers of blocks > r: final by now
+            cur, dcur, d_out_r = self.bufs[r], self.dbufs[r], d_of(r)
+            a5, b5, r2, beta2 = rdb_epilogue(j, d_of(3 * i + 2), backward=True)     # (r2: the gradient w.r.t. this RRDB's output)
+            if (r + 1) in ws.cuts:      # everything recorded so far reads buffers of blocks > r: final by now
                 ir, jr = divmod(r + 1, 3)
-                close_batch(f"body.{ir}.rdb{jr + 1}.conv1.weight")   # first parameter (arena order) of the blocks finished so far
+                ws.close(f"body.{ir}.rdb{jr + 1}.conv1.weight")   # first parameter (arena order) of the blocks finished so far
+                Bk = ws.launcher
             store.add_rdb_gather(p, nf, gc, a5, ck0=16 if fused_bwd else 0)
-            add_wg(f"{p}.conv5", view(cur, 0), d_out_r, H, W, 1, H, W, alpha=a5, cin=cd)
+            ws.add(f"{p}.conv5", view(cur, 0), d_out_r, H, W, 1, H, W, alpha=a5, cin=cd)
             for k in (4, 3, 2, 1):
-                add_wg(f"{p}.conv{k}", view(cur, 0), view(dcur, nf + (k - 1) * gc), H, W, 1, H, W,
-                       cin=nf + (k - 1) * gc)
+                ws.add(f"{p}.conv{k}", view(cur, 0), view(dcur, nf + (k - 1) * gc), H, W, 1, H, W, cin=nf + (k - 1) * gc)
             if fused_bwd:
                 # one launch for the whole dense-block backward (csrc/rdb_fwd.hip, rdb_kernel<true>)
-                rd = hip.RdbDesc()
-                rd.dtype, rd.N, rd.H, rd.W = self.dt, B, H, W
-                rd.inp, rd.slices, rd.out, rd.mask = d_out_r, view(dcur, 0), view(dcur, 0), view(cur, 0)
-                for jj in range(5):
-                    rd.w[jj] = store.gather[(p, 4 - jj)].data_ptr()
-                    rd.bias[jj] = None
-                rd.w[4] = store.gather[(p, "k0", 16)].data_ptr()   # slice 0 streams in 16-channel half chunks
-                rd.alpha5, rd.beta1 = 1.0, b5
-                rd.r2, rd.beta2 = (d_rrdb, 1.0) if j == 0 else (hip.NULL_VIEW, 0.0)
-                self._rdb_descs.append(rd)
+                w = [store.gather[(p, k)].data_ptr() for k in (4, 3, 2, 1)]
+                w.append(store.gather[(p, "k0", 16)].data_ptr())          # slice 0 streams in 16-channel half chunks
+                rd = self._rdb_desc(d_out_r, view(dcur, 0), view(dcur, 0), view(cur, 0), w, [None] * 5, 1.0, b5, r2, beta2)
                 bwd_descs.append(rd)
                 Bk.add(hip.lib().ssr_rdb_backward, C.byref(rd), what=f"rdb bwd {p}")
                 continue
@@ -1076,43 +958,22 @@ class GeneratorPlan:
                                view(dcur, nf + (k - 1) * gc), gc, m=view(cur, nf + (k - 1) * gc), m_c0=0, m_c1=gc) for k in (4, 3, 2, 1)]
             if tmp is not Bk:
                 self._add_chain(Bk, ds, f"conv chain dgrad-gather {p}.slice4-1")
-            kw = dict(r1=d_out_r, r1_nc=nf, beta1=b5)        # the `+ x` path of this RDB         (rrdbnet_arch.py:44)
-            if j == 0:                                          # d x_rrdb += d out_rrdb             (rrdbnet_arch.py:68)
-                kw.update(r2=d_rrdb, r2_nc=nf, beta2=1.0)
-            gather_dgrad(cb, Bk, p, 0, view(dcur, nf), 4 * gc, d_out_r, nf, H, W, view(dcur, 0), nf, **kw)
+            # r1: the `+ x` path of this RDB (rrdbnet_arch.py:44); r2: d x_rrdb += d out_rrdb (:68)
+            gather_dgrad(cb, Bk, p, 0, view(dcur, nf), 4 * gc, d_out_r, nf, H, W, view(dcur, 0), nf, r1=d_out_r, r1_nc=nf, beta1=b5,
+                         r2=r2, r2_nc=nf if r2.p else 0, beta2=beta2)
         self._link_rdb_prefetch(bwd_descs)
         # d feat += d trunk                                                                      (rrdbnet_arch.py:125)
         Bk.add(hip.lib().ssr_add_views, view(self.dbufs[0], 0), view(self.g_trunk), self.dt, B * H * W, nf,
                what="add d_trunk")
-        add_wg("conv_first", view(self.xin), view(self.dbufs[0], 0), H, W, 1, H, W, cin=self.xin.shape[-1])
-        if need_input_grad:
+        ws.add("conv_first", view(self.xin), view(self.dbufs[0], 0), H, W, 1, H, W, cin=self.xin.shape[-1])
+        if self.g_xin is not None:
             cb.dgrad(Bk, "conv_first", view(self.dbufs[0], 0), H, W, view(self.g_xin), cout=self.xin.shape[-1],
                      cin_dy=nf)
-        if n_chunks > 1:
-            close_batch()
-            if n_seg == 1:
-                Bk.join()
-            batches.pop()
-        else:
-            batches[0].finalize()
-            batches[0].launch(Bk)
-        self._wg_batches = batches
-        if n_seg > 1:          # the whole backward = the segments in order (eager / instrumented runs; the step runs them one by one)
-            whole = Launcher()
-            for L, _, _ in self.bwd_segments:
-                whole.calls.extend(L.calls)
-            self.bwd = whole
-            assert sum(n for _, _, n in self.bwd_segments) == st.numel and self.bwd_segments[-1][1] == 0
-        else:
-            self.bwd = Bk
+        return ws.finish()
 
     def _add_chain(self, L: Launcher, descs, what: str):
         """one ssr_conv2d_chain call for a list of already filled descriptors (copied into one ctypes array)"""
-        arr = (ConvDesc * len(descs))()
-        for i, d in enumerate(descs):
-            C.memmove(C.byref(arr[i]), C.byref(d), C.sizeof(ConvDesc))
-        self._cb.keep.append(arr)
-        L.add(hip.lib().ssr_conv2d_chain, arr, len(descs), self._chain_state.data_ptr(), what=what)
+        L.add(hip.lib().ssr_conv2d_chain, self._cb.array(descs), len(descs), self._chain_state.data_ptr(), what=what)
 
     # ---- boundary: NCHW fp32 tensors of the reference API ----
     def load_input(self, x_nchw: torch.Tensor, scale: float = 1.0):
@@ -1240,6 +1101,7 @@ class DiscriminatorPlan:
         self._cb = _ConvBuilder(store, B)
         self._fwd_cache: Dict[Tuple[int, int], Launcher] = {}
         self._bwd_cache: Dict[Tuple, Launcher] = {}
+        self._keep: List[WgradBatch] = []           # the weight-gradient batches of the backward plans
         self.training = training
         if training:
             self.d_logits = z(B, H, W, 8)
@@ -1298,16 +1160,11 @@ class DiscriminatorPlan:
         H2, W2, H4, W4, H8, W8 = H // 2, W // 2, H // 4, W // 4, H // 8, W // 8
         lib = hip.lib()
         L = Launcher()
-        wg3, wg4 = WgradBatch(dt, 3, 1, det=self.det), WgradBatch(dt, 4, 2, det=self.det)
+        wg3, wg4 = WgradBatch(dt, 3, 1, det=self.det, device=st.device), WgradBatch(dt, 4, 2, det=self.det, device=st.device)
 
         def add_wg(name, x, dy, hi, wi, gh, gw, cin=None):
-            if not param_grads:
-                return
-            s = st.specs[name]
-            arena = st.grad_sn if s.sn else st.grad
-            (wg3 if s.k == 3 else wg4).add(x, dy, B, hi, wi, 1, rup(s.cin, 8) if cin is None else cin, s.cout, gh, gw,
-                                           1.0, st.ptr(st.wkey(name), arena), s.cin,
-                                           st.ptr(name + ".bias", st.grad) if s.bias else None)
+            if param_grads:
+                (wg3 if st.specs[name].k == 3 else wg4).add(x, dy, B, hi, wi, 1, gh=gh, gw=gw, alpha=1.0, **wgrad_args(st, name, cin))
 
         NV = hip.NULL_VIEW
         add_wg("conv9", view(self.o8), view(self.d_logits), H, W, H, W)
@@ -1347,7 +1204,7 @@ class DiscriminatorPlan:
             cb.dgrad(L, "conv0", view(self.g0), H, W, view(self.g_in), cout=self.cdp, cin_dy=nf, **kw)
         wg3.finalize(); wg4.finalize()
         wg3.launch(L); wg4.launch(L)
-        self._keep = getattr(self, "_keep", []) + [wg3, wg4]
+        self._keep += [wg3, wg4]
         self._bwd_cache[key] = L
         return L
 
@@ -1416,6 +1273,7 @@ class ObjectBranchPlan:
         cb.conv(F, "o_conv4", view(self.a2), *hs[3], view(self.out), act=RELU)
         self.fwd = F
         self._bwd_cache: Dict[Tuple[bool, bool], Launcher] = {}
+        self._keep: List[WgradBatch] = []
         if not training:
             return
         self.d_out = z(Bo, *hs[4], 8)                    # dL/d o_out, channel 0 (the caller fills it)
@@ -1450,14 +1308,11 @@ class ObjectBranchPlan:
             return self._bwd_cache[key]
         cb, st, Bo, hs, lib = self._cb, self.store, self.Bo, self.hs, hip.lib()
         L = Launcher()
-        wg = WgradBatch(hip.F32, 4, 2, det=self.det)
+        wg = WgradBatch(hip.F32, 4, 2, det=self.det, device=st.device)
 
         def add_wg(name, x, dy, hw_in, hw_out, cin=None):
-            if not param_grads:
-                return
-            s = st.specs[name]
-            wg.add(x, dy, Bo, hw_in[0], hw_in[1], 1, rup(s.cin, 8) if cin is None else cin, s.cout, hw_out[0], hw_out[1], 1.0,
-                   st.ptr(name + ".weight", st.grad), s.cin, st.ptr(name + ".bias", st.grad))
+            if param_grads:
+                wg.add(x, dy, Bo, *hw_in, 1, gh=hw_out[0], gw=hw_out[1], alpha=1.0, **wgrad_args(st, name, cin))
 
         def attention_bwd(d):
             e = hip.AttnDesc()
@@ -1484,6 +1339,6 @@ class ObjectBranchPlan:
             cb.dgrad(L, "o_conv1", view(self.g_o1), *hs[1], view(self.g_in), cout=8, cin_dy=64)
         wg.finalize()
         wg.launch(L)
-        self._keep = getattr(self, "_keep", []) + [wg]
+        self._keep.append(wg)
         self._bwd_cache[key] = L
         return L

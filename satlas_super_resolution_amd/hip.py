@@ -372,13 +372,31 @@ def view(t: Optional[torch.Tensor], coff: int = 0) -> View:
     return View(t.data_ptr(), t.shape[-1], coff)
 
 
-def device_table(items) -> torch.Tensor:
-    """Copy a list of ctypes structs to a device byte tensor (descriptor tables)."""
+def device_table(items, device="cuda") -> torch.Tensor:
+    """Copy a list of ctypes structs to a byte tensor on `device` (descriptor tables)."""
     arr_t = type(items[0]) * len(items)
     arr = arr_t(*items)
     raw = bytes(memoryview(arr).cast("B"))
     host = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
-    return host.cuda()
+    return host.to(device)
+
+
+# the switches (SSR_*): the Python twins of ssr_env_off / _on / _int / _now (csrc/common.h)
+def env_off(name: str) -> bool:
+    return os.environ.get(name) == "0"
+
+
+def env_on(name: str, dflt: bool = False) -> bool:
+    e = os.environ.get(name)
+    return dflt if e is None else e == "1"
+
+
+def env_int(name: str, dflt: int) -> int:
+    return int(os.environ.get(name, dflt))
+
+
+def env_str(name: str, dflt: str) -> str:
+    return os.environ.get(name, dflt)
 
 
 def device_info() -> str:
