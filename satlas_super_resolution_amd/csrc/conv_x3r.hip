@@ -16,13 +16,16 @@
 //     cdone[w]; a wave polls only when the count it saw last no longer covers the chunk it needs (one ds_read_b128 = all four words).
 // Work split: the 3 x nchunks (chunk, tap row) items go round-robin to the four MFMA waves (item g -> wave g & 3), three taps each;
 // every wave walks the chunks at the same pace.  The four K-quarters of a tile are summed in wave order 0 .. 3 through LDS (fixed
-// order: an image's bytes do not depend on the batch or on timing), wave m finishes pixel tile m; NT = 2: the four producer waves
-// finish the second 32-channel tile, so eight waves run the epilogue.
-// Epilogue: the dense block's three forms (bias + LeakyReLU; alpha (acc + bias) + beta1 r1 + beta2 r2; LeakyReLU-backward mask)
-// are straight-line code in the TRANSPOSED domain - the finished 32 x 32 tile goes through a 4-KB LDS slab, then every lane owns
-// 4 channels of 4 pixels: residual / mask loads and the result stores are whole 128-byte pixel rows by 16-byte buffer
-// instructions, absent operands read zeros through an out-of-range offset (DESIGN.md lessons 2, 52).  Everything else takes
-// conv_epilogue<float, 14> (conv_epilogue.h), the contract's generic form.
+// order: an image's bytes do not depend on the batch or on timing).
+// Finish, the dense block's three forms (bias + LeakyReLU; alpha (acc + bias) + beta1 r1 + beta2 r2; LeakyReLU-backward mask), every
+// <NTW, NU, TH, AM>: ALL waves.  Every MFMA wave stores all its partial tiles into its quarter's slots TRANSPOSED ([32 pixel slots]
+// [32 channels] fp32), one barrier, then the MT x NTT tiles are dealt over the NTHR threads as items of one pixel x four channels:
+// four 16-byte LDS reads added as ((p0 + p1) + p2) + p3, the form, one 16-byte buffer store - a quarter wave writes a whole
+// 128-byte pixel row.  One LDS round trip per accumulator value instead of two (partial slot, then transpose slab), eight (twelve)
+// waves instead of MT, and the bias / residual / mask vectors of an item - its thread is known at entry - are requested while the
+// ring still runs (absent operands read zeros through an out-of-range offset, DESIGN.md lessons 2, 52; no branch around a load).
+// Everything else takes conv_epilogue<float, 14> (conv_epilogue.h), the contract's generic form, with the one-wave finish: wave m
+// sums and finishes pixel tile m (NT = 2: the four producer waves the second 32-channel tile) through a 4-KB transpose slab.
 //
 // Same tile, packed weights and per-acc product order (a_lo w_hi + a_hi w_lo + a_hi w_hi) as conv_x3q_kernel; results agree with it
 // up to the fp32 summation order of the K-quarters.
@@ -79,6 +82,31 @@ __global__ __launch_bounds__((XrT<NTW, NU, TH>::NTHR)) void conv_x3r_kernel(cons
         for (int u = 0; u < NT; ++u)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][u][r] = 0.f;
+
+    // the finish of the straight-line epilogues: the MT x NTT finished tiles are MT NTT 256 ITEMS of one pixel x four channels (tile
+    // it >> 8 = [pixel tile][channel tile], pixel slot (it >> 3) & 31, channels 4 (it & 7) ..), thread tid takes items tid + NTHR k.
+    // The map is static, so every thread requests the bias / residual / mask vectors of its items while the ring still runs: a producer
+    // once its last chunk is stored; an MFMA wave behind its first weights - at TH = 4, where 128 registers keep two workgroups on a CU,
+    // only the mask / first residual (part 0: four registers), the rest (part 1) when it leaves the MFMA loop; the 64-channel forms
+    // (two tiles per wave: 256 registers, twelve waves: 168 - both full) request everything there.
+    constexpr bool ITEMS = EP != XR_EP_GENERIC;
+    constexpr int OPS_EARLY = (NTW == 1 && NU == 1) ? ((TH == 8 || EP == XR_EP_LRELU) ? 2 : 1) : 0;       // parts an MFMA wave requests ahead of its loop
+    constexpr int NITEMS = MT * NTT * 256, NIT = ITEMS ? (NITEMS + T::NTHR - 1) / T::NTHR : 1;
+    XrItemOps ops[NIT];
+    auto fetch_ops = [&](auto pc) {
+        if constexpr (ITEMS) {
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < NIT; ++k) {
+                const int it = tid + T::NTHR * k, tl = it >> 8, pix = (it >> 3) & 31;
+                xr_item_fetch<EP, decltype(pc)::value>(d, co0 + 32 * (tl % NTT) + 4 * (it & 7), n, gy0 + 2 * (tl / NTT) + (pix >> 4),
+                                                       gx0 + epi_col<XR_ROT>(pix), it < NITEMS, ops[k]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    using P0 = std::integral_constant<int, 0>;
+    using P1 = std::integral_constant<int, 1>;
 
     if (wave >= NMF) {
         // =============================== producer waves: the patch ===============================
@@ -179,6 +207,8 @@ __global__ __launch_bounds__((XrT<NTW, NU, TH>::NTHR)) void conv_x3r_kernel(cons
             });
         }
         RPROBE(pt == 0, 9);
+        fetch_ops(P0{});                                       // the last chunk is stored: the MFMA waves still have chunks to go
+        fetch_ops(P1{});
     } else {
         // =============================== MFMA waves: all four pixel tiles, a quarter of K ===============================
         const int w = wave & 3, ug = wave >> 2;                             // K quarter, channel-tile group
@@ -191,6 +221,8 @@ __global__ __launch_bounds__((XrT<NTW, NU, TH>::NTHR)) void conv_x3r_kernel(cons
         const int glast = w + 4 * (nj - 1);
         if (nj == 0) {
             if (lane == 0) *(xr_lds_int)(uintptr_t)(ctl_addr + 16 + 4 * wave) = 0x3fffffff;
+            fetch_ops(P0{});
+            fetch_ops(P1{});
         } else {
             bf16x8 wf[WR][NT][2];                                          // weight fragments of WR (chunk, tap) steps: [hi | lo]
             constexpr int TPS = T::TPS, SPT = T::SPT, NSUB = 3 * SPT, NSETS = T::NSETS, PD = NSETS - 1;
@@ -241,6 +273,8 @@ __global__ __launch_bounds__((XrT<NTW, NU, TH>::NTHR)) void conv_x3r_kernel(cons
                 load_w(w + 4 * (s / 3), std::integral_constant<int, s % 3>{}, sc);
                 __builtin_amdgcn_sched_barrier(0);
             });
+            if constexpr (OPS_EARLY >= 1) fetch_ops(P0{});                 // behind the first weights, under the wait for the first chunk
+            if constexpr (OPS_EARLY >= 2) fetch_ops(P1{});
             RPROBE(tid == 0, 1);
             int g = w, c_cur = g / 3;
             int base_cur = base_of(g);
@@ -350,80 +384,128 @@ __global__ __launch_bounds__((XrT<NTW, NU, TH>::NTHR)) void conv_x3r_kernel(cons
             }
             asm volatile("" ::: "memory");
             if (lane == 0) *(xr_lds_int)(uintptr_t)(ctl_addr + 16 + 4 * wave) = 0x3fffffff;
+            if constexpr (OPS_EARLY < 1) fetch_ops(P0{});                  // the fragment registers are free now
+            if constexpr (OPS_EARLY < 2) fetch_ops(P1{});
         }
     }
     __syncthreads();                                           // every wave is out of the ring: it becomes the partial-sum slots
     RPROBE(tid == 0, 10);
 
-    // ---- sum the four K-quarters in wave order through LDS: slot [source wave][pixel tile][channel tile] = 16 registers x 64 lanes,
-    //      as four 16-byte vectors per lane ([q][lane][4]: contiguous, conflict-free); wave m keeps tile (m, 0) in registers ----
-    const bool is_mfma = wave < NMF;
-    const int me = is_mfma ? (wave & 3) : wave - NMF;          // the pixel tile this wave finishes (if it is one of the MT tiles) = its K quarter
-    const int ut = is_mfma ? NTW * (wave >> 2) : 1;            // ... and the channel tile (producers: the second tile of the one group, NTW = 2)
+    if constexpr (ITEMS) {
+        // ---- the four K-quarters through LDS, once: every MFMA wave stores ALL its partial tiles into slot [source quarter][pixel tile]
+        //      [channel tile] TRANSPOSED, as [32 pixel slots][32 channels] fp32 (register r of lane (i, g) = pixel slot mfma32_row(r, g),
+        //      channel i: a ds_write_b32 puts the 32 lanes of a half wave on 32 consecutive words - conflict-free without a swizzle).
+        //      One barrier, then all NTHR threads finish their items: four contiguous 16-byte reads (quarters 0 .. 3, added in that
+        //      order), the unscale, the epilogue form on operands requested long ago, one 16-byte store ----
 #ifndef XR_X_NORED     // (probe switch: no partial tiles through LDS - the sums below read whatever the ring left there)
-    if (is_mfma) {
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-            for (int u = 0; u < NT; ++u)
-                if (!(t == me && u == 0)) {
-                    char* sp = smem + ((me * MT + t) * NTT + ut + u) * XR_SLOT + lane * 16;      // source K quarter = wave & 3 = me
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        f32x4 v = {acc[t][u][4 * q], acc[t][u][4 * q + 1], acc[t][u][4 * q + 2], acc[t][u][4 * q + 3]};
-                        *reinterpret_cast<f32x4*>(sp + q * 1024) = v;
-                    }
-                }
-    }
-#endif
-    __syncthreads();
-    if ((is_mfma || NTW == 2) && me < MT) {
-        f32x16 own;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) own[r] = 0.f;
-        if (is_mfma) {                                         // runtime tile index -> static register selection
+        if (wave < NMF) {
+            char* sp = smem + ((wave & 3) * MT * NTT + NTW * (wave >> 2)) * XR_SLOT + (lane >> 5) * 512 + (lane & 31) * 4;
 #pragma unroll
             for (int t = 0; t < MT; ++t)
-                if (t == me) own = acc[t][0];
-        }
-        f32x16 sum;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            f32x16 part;
-            const char* sp = smem + ((s * MT + me) * NTT + ut) * XR_SLOT + lane * 16;
+                for (int u = 0; u < NT; ++u)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        *reinterpret_cast<float*>(sp + (t * NTT + u) * XR_SLOT + mfma32_row(r, 0) * 128) = acc[t][u][r];
+        }
+#endif
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < NIT; ++k) {
+            const int it = tid + T::NTHR * k;
+            if ((NITEMS % T::NTHR) == 0 || it < NITEMS) {          // (twelve-wave form: the last round is short by whole waves)
+                const char* rp = smem + (it >> 8) * XR_SLOT + (it & 255) * 16;
+                f32x4 v = *reinterpret_cast<const f32x4*>(rp);
+#pragma unroll
+                for (int s = 1; s < 4; ++s) {
+                    const f32x4 p = *reinterpret_cast<const f32x4*>(rp + s * MT * NTT * XR_SLOT);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] += p[e];
+                }
+                if constexpr (H) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] *= SSR_F32H_UNSCALE;  // the packed weights carry 2^SSR_F32H_WSHIFT
+                    asm volatile("" : "+v"(v));                        // (a rounding of its own, as when the sum went through the slab: no fma with the bias)
+                }
+#ifdef XR_X_NOEPI      // (probe switch: the sums leave through one plain store per lane instead of the epilogue)
+                const float keep = (v[0] + v[1]) + (v[2] + v[3]);
+                if (keep == 123.456f) reinterpret_cast<float*>(d.y.p)[tid] = keep;
+#else
+                xr_item_finish<EP>(d, v, ops[k]);
+#endif
+            }
+        }
+    } else {
+        // ---- the generic epilogue: the four K-quarters summed in wave order through LDS: slot [source wave][pixel tile][channel tile] = 16
+        //      registers x 64 lanes, as four 16-byte vectors per lane ([q][lane][4]: contiguous, conflict-free); wave m keeps tile (m, 0) in
+        //      registers and finishes pixel tile m (NTW = 2: the producer waves the second channel tile) ----
+        const bool is_mfma = wave < NMF;
+        const int me = is_mfma ? (wave & 3) : wave - NMF;          // the pixel tile this wave finishes (if it is one of the MT tiles) = its K quarter
+        const int ut = is_mfma ? NTW * (wave >> 2) : 1;            // ... and the channel tile (producers: the second tile of the one group, NTW = 2)
+#ifndef XR_X_NORED     // (probe switch: no partial tiles through LDS - the sums below read whatever the ring left there)
+        if (is_mfma) {
+#pragma unroll
+            for (int t = 0; t < MT; ++t)
+#pragma unroll
+                for (int u = 0; u < NT; ++u)
+                    if (!(t == me && u == 0)) {
+                        char* sp = smem + ((me * MT + t) * NTT + ut + u) * XR_SLOT + lane * 16;      // source K quarter = wave & 3 = me
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            f32x4 v = {acc[t][u][4 * q], acc[t][u][4 * q + 1], acc[t][u][4 * q + 2], acc[t][u][4 * q + 3]};
+                            *reinterpret_cast<f32x4*>(sp + q * 1024) = v;
+                        }
+                    }
+        }
+#endif
+        __syncthreads();
+        if ((is_mfma || NTW == 2) && me < MT) {
+            f32x16 own;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) own[r] = 0.f;
+            if (is_mfma) {                                         // runtime tile index -> static register selection
+#pragma unroll
+                for (int t = 0; t < MT; ++t)
+                    if (t == me) own = acc[t][0];
+            }
+            f32x16 sum;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                f32x16 part;
+                const char* sp = smem + ((s * MT + me) * NTT + ut) * XR_SLOT + lane * 16;
 #ifdef XR_X_NORED
-            part = own;
-            asm volatile("" : "+v"(part));
+                part = own;
+                asm volatile("" : "+v"(part));
 #else
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(sp + q * 1024);
-                part[4 * q] = v[0]; part[4 * q + 1] = v[1]; part[4 * q + 2] = v[2]; part[4 * q + 3] = v[3];
-            }
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(sp + q * 1024);
+                    part[4 * q] = v[0]; part[4 * q + 1] = v[1]; part[4 * q + 2] = v[2]; part[4 * q + 3] = v[3];
+                }
 #endif
-            const bool mine = is_mfma && s == me;              // (that slot was never written: its bytes are not used)
+                const bool mine = is_mfma && s == me;              // (that slot was never written: its bytes are not used)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = mine ? own[r] : part[r];
-                sum[r] = s == 0 ? p : sum[r] + p;
+                for (int r = 0; r < 16; ++r) {
+                    const float p = mine ? own[r] : part[r];
+                    sum[r] = s == 0 ? p : sum[r] + p;
+                }
             }
-        }
-        if constexpr (H) {
+            if constexpr (H) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) sum[r] *= SSR_F32H_UNSCALE;       // the packed weights carry 2^SSR_F32H_WSHIFT
-        }
-        // the transpose slab: a slot no other wave reads (an MFMA wave's own, never written, slot of its tile; a producer's: source quarter 0's)
-        char* slab = smem + (((is_mfma ? me : 0) * MT + me) * NTT + ut) * XR_SLOT;
-        const int cb = co0 + 32 * ut;
+                for (int r = 0; r < 16; ++r) sum[r] *= SSR_F32H_UNSCALE;       // the packed weights carry 2^SSR_F32H_WSHIFT
+            }
+            // the transpose slab: a slot no other wave reads (an MFMA wave's own, never written, slot of its tile; a producer's: source quarter 0's)
+            char* slab = smem + (((is_mfma ? me : 0) * MT + me) * NTT + ut) * XR_SLOT;
+            const int cb = co0 + 32 * ut;
 #ifdef XR_X_NOEPI      // (probe switch: the sums leave through one plain store per lane instead of the transposing epilogue)
-        float keep = 0.f;
+            float keep = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) keep += sum[r];
-        if (keep == 123.456f) reinterpret_cast<float*>(d.y.p)[tid] = keep;
+            for (int r = 0; r < 16; ++r) keep += sum[r];
+            if (keep == 123.456f) reinterpret_cast<float*>(d.y.p)[tid] = keep;
 #else
-        if constexpr (EP == XR_EP_GENERIC) conv_epilogue<float, XR_ROT>(d, sum, cb, n, gy0 + 2 * me, gx0, lane, slab);
-        else xr_epilogue<EP>(d, sum, cb, n, gy0 + 2 * me, gx0, lane, slab);
+            conv_epilogue<float, XR_ROT>(d, sum, cb, n, gy0 + 2 * me, gx0, lane, slab);
 #endif
+        }
     }
     RPROBE(tid == 0, 11);
 }

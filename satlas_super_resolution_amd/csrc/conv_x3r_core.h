@@ -157,4 +157,62 @@ __device__ __forceinline__ void xr_epilogue(const ssr_conv_desc& d, const f32x16
     }
 }
 
+// The same epilogues per ITEM = one pixel x four channels (conv_x3r.hip: every thread of the workgroup finishes its items).  The operands
+// of an item depend on nothing the kernel computes: xr_item_fetch requests them (no branch around a load: an invalid item and an absent
+// operand read zeros through XR_OOB / an empty range) long before xr_item_finish applies the form to the summed K quarters and stores.
+struct XrItemOps {
+    f32x4 bv;
+    u32x4 q1, q2;                                              // LIN: r1, r2; MASK: m (q2 unused)
+    int yoff;                                                  // byte offset of the result, XR_OOB where nothing is stored
+};
+
+// PART 0: the operand that comes from far (q1: four registers a thread can afford to hold through the MFMA loop at any tile height);
+// PART 1: the rest (bias: 128 bytes every workgroup reads; q2; the offset of the result)
+template <int EP, int PART>
+__device__ __forceinline__ void xr_item_fetch(const ssr_conv_desc& d, int c, int n, int gy, int gx, bool live, XrItemOps& o) {
+    const long npix = (long)d.N * d.Ho * d.Wo * 4;
+    const bool ok = live && c < d.Cout && gy < d.Gh && gx < d.Gw;
+    const int pp = (n * d.Ho + gy) * d.Wo + gx;
+    if constexpr (PART == 0) {
+        if constexpr (EP == XR_EP_LIN) {
+            const __amdgpu_buffer_rsrc_t rs_r1 = xr_rsrc(d.r1.p, d.r1.p ? npix * d.r1.cs : 0);
+            o.q1 = __builtin_amdgcn_raw_buffer_load_b128(rs_r1, ok && d.r1.p ? (pp * d.r1.cs + d.r1.coff + c) * 4 : XR_OOB, 0, 0);
+        }
+        if constexpr (EP == XR_EP_MASK) {
+            const __amdgpu_buffer_rsrc_t rs_m = xr_rsrc(d.m.p, npix * d.m.cs);
+            o.q1 = __builtin_amdgcn_raw_buffer_load_b128(rs_m, ok ? (pp * d.m.cs + d.m.coff + c) * 4 : XR_OOB, 0, 0);
+        }
+    } else {
+        o.yoff = ok ? (pp * d.y.cs + d.y.coff + c) * 4 : XR_OOB;
+        // (Cout % 4 == 0 on these forms, xr_pick_epilogue: the four channels lie inside Cout together, beyond it the row reads zeros)
+        const __amdgpu_buffer_rsrc_t rs_b = xr_rsrc(d.bias, d.bias ? (long)d.Cout * 4 : 0);
+        o.bv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_b, c * 4, 0, 0));
+        if constexpr (EP == XR_EP_LIN) {
+            const __amdgpu_buffer_rsrc_t rs_r2 = xr_rsrc(d.r2.p, d.r2.p ? npix * d.r2.cs : 0);
+            o.q2 = __builtin_amdgcn_raw_buffer_load_b128(rs_r2, ok && d.r2.p ? (pp * d.r2.cs + d.r2.coff + c) * 4 : XR_OOB, 0, 0);
+        }
+    }
+}
+
+template <int EP, int AUX = 0>
+__device__ __forceinline__ void xr_item_finish(const ssr_conv_desc& d, f32x4 v, const XrItemOps& o) {
+    const __amdgpu_buffer_rsrc_t rs_y = xr_rsrc(d.y.p, (long)d.N * d.Ho * d.Wo * 4 * d.y.cs);
+    const float alpha = d.alpha, beta1 = d.beta1, beta2 = d.beta2;
+    if constexpr (EP == XR_EP_LRELU) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = lrelu_max(v[k] + o.bv[k]);
+    } else if constexpr (EP == XR_EP_LIN) {
+        const f32x4 a = __builtin_bit_cast(f32x4, o.q1), b = __builtin_bit_cast(f32x4, o.q2);
+        // the contraction xr_epilogue's expression gets, spelled out: left to the compiler, WHICH product is fused differs from one
+        // instantiation to the next (half-height: fma(beta2, b, beta1 a)) and an image's bytes would depend on the tiling
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = __builtin_fmaf(alpha, v[k] + o.bv[k], __builtin_fmaf(beta1, a[k], beta2 * b[k]));
+    } else {
+        const f32x4 m = __builtin_bit_cast(f32x4, o.q1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = (v[k] + o.bv[k]) * lrelu_grad_from_out(m[k]);
+    }
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_y, o.yoff, 0, AUX);
+}
+
 }  // namespace
