@@ -797,6 +797,35 @@ int64_t ssr_self_attention_scratch_floats(int32_t Bo, int32_t N, int32_t C);
  * from its output (torch.relu at osm_obj_discriminator_arch.py:79, whose input gradient arrives from outside the plan) */
 int ssr_relu_bwd(ssr_view g, ssr_view y, ssr_view dst, int64_t npix, int32_t C, void* stream);
 
+/* ---- object crops of OSMObjESRGANModel (ssr/models/osm_objs_esrgan_model.py:166-181): cut a box out of an image, resize it to
+ *      SSR_OBJ_CROP x SSR_OBJ_CROP as torchvision.transforms.functional.resize does (bilinear, align_corners = False), and the
+ *      transpose of that.  csrc/obj_crop.hip; plain fp32 FMA.
+ * Tap rule, per axis of n_in source pixels, scale = n_in / 32: support = scale if antialias and scale >= 1, else 1; center =
+ * scale * (i + 0.5); first = max(int(center - support + 0.5), 0); count = min(int(center + support + 0.5), n_in) - first;
+ * w_j = max(0, 1 - |(j + first - center + 0.5) / support|), normalised to sum 1.  The 2-D weight is the product of the axes' weights.
+ * boxes: DEVICE int32 [Bo][5] = (b, x1, y1, x2, y2), the crop being image b, rows y1 .. y2 - 1, columns x1 .. x2 - 1.  The kernels
+ * read them from memory when they run: a captured graph replays with whatever the array holds then.  Because they are data, a bad
+ * box cannot be a return code: a box that is empty, reaches outside [B, H, W] or has a side above SSR_OBJ_MAX_SIDE is REFUSED on the
+ * device - its crop is written as zeros, it receives no gradient, and nothing is read or written through it.
+ *   ssr_obj_crop_resize_fwd: src is an NHWC fp32 view of [B, H, W] pixels whose channels 0..2 (from src.coff) are read; dst an NHWC
+ *       fp32 view of [Bo, 32, 32] pixels whose channels 0..2 receive the crop and 3..7 are written as 0 (the first object
+ *       convolution reads 8 channels).
+ *   ssr_obj_crop_resize_bwd: g is the crops' gradient (a view like dst; channels 0..2 read); dimg[b, y, x, c] += grad_scale * sum
+ *       over the objects o of image b in index order, first[b] <= o < first[b + 1] (first: DEVICE int32 [B + 1]; an object whose box
+ *       names another image is skipped), then over the outputs (oy, ox) in row-major order whose taps reach (y, x), for c = 0..2.  One
+ *       writer per image pixel, no atomics: two runs give the same bytes.  Channels >= 3 and pixels no served box covers are not
+ *       written at all.
+ * dtype is the storage code of the views: SSR_F32 / SSR_F32X3 (fp32).  SSR_EUNSUP: SSR_BF16 (as the object branch), more than 65535
+ * images or tile rows.  SSR_EINVAL without a launch: any other dtype, a null pointer, B, H, W or Bo <= 0, an image view that is not
+ * 4-byte aligned or narrower than coff + 3, a crop view that is not 16-byte aligned (p, cs % 4, coff % 4) or narrower than coff + 8,
+ * g aliasing dimg. */
+#define SSR_OBJ_CROP 32
+#define SSR_OBJ_MAX_SIDE 128
+int ssr_obj_crop_resize_fwd(ssr_view src, int32_t dtype, int32_t B, int32_t H, int32_t W, const int32_t* boxes, int32_t Bo,
+                            ssr_view dst, int32_t antialias, void* stream);
+int ssr_obj_crop_resize_bwd(ssr_view g, const int32_t* boxes, const int32_t* first, int32_t Bo, ssr_view dimg, int32_t dtype,
+                            int32_t B, int32_t H, int32_t W, float grad_scale, int32_t antialias, void* stream);
+
 /* library / device info: writes "gfx950 CUs=256 ..." style text */
 int ssr_device_info(char* buf, int32_t buflen);
 int ssr_abi_version(void);

@@ -9,7 +9,9 @@ uint8 all the way: SSRESRGANModel.feed_data uploads bytes and scales by 1/255 on
 torchvision.io.read_image, which is not a dependency here); the frame selection consumes Python's `random` exactly as the reference
 does (one `random.sample`, then one `random.randint` under rand_crop), so a seeded run picks the same frames.
 
-Not implemented (raise): OSM-object filtering (`osm_objs_path`; OSMObjESRGANModel is outside the hot path)."""
+OSM-object filtering (`osm_objs_path`, with `n_osm_objs`; ssr/data/s2-naip_dataset.py:87-91,:116-118): on the train split only, a chip
+stays when the JSON file lists it with at least n_osm_objs boxes over all its classes; the order of the remaining chips is unchanged.
+Other splits ignore the option, as the reference does."""
 from __future__ import annotations
 
 import glob
@@ -64,8 +66,10 @@ class S2NAIPDataset(data.Dataset):
         self.scale = int(opt["scale"])
         self.use_3d = bool(opt.get("use_3d", False))
         self.old_naip_path = opt.get("old_naip_path")
-        if opt.get("osm_objs_path"):
-            raise NotImplementedError("datasets.*.osm_objs_path: the OSM-object model is outside the MI355X hot path")
+        osm_obj_data = None
+        if opt.get("osm_objs_path") is not None and train:       # (:89-91)
+            with open(opt["osm_objs_path"]) as f:
+                osm_obj_data = json.load(f)
         bands = list(opt.get("s2_bands", ["tci"]))
         bands.insert(0, bands.pop(bands.index("tci")))           # tci first (:73-75)
         self.s2_bands = bands
@@ -83,6 +87,9 @@ class S2NAIPDataset(data.Dataset):
         self.datapoints = []
         for n in naip:
             chip = n.split("/")[-2]
+            if osm_obj_data is not None:      # (:116-118) fewer than n_osm_objs boxes: random.sample in the model could not draw
+                if not (chip in osm_obj_data and sum(len(v) for v in osm_obj_data[chip].values()) >= opt["n_osm_objs"]):
+                    continue
             s2 = [os.path.join(self.s2_path, chip, b + ".png") for b in bands]
             self.datapoints.append([n, s2, chip] + ([old_by_chip[chip][0]] if self.old_naip_path else []))
         self.data_len = len(self.datapoints)

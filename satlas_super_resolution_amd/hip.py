@@ -177,8 +177,10 @@ ABI_SYMBOLS = [
     "ssr_prelu_reflect_fwd", "ssr_prelu_reflect_bwd", "ssr_sr_tail_fwd", "ssr_sr_tail_bwd", "ssr_sr_tail_scratch_bytes",
     "ssr_dropout_mask", "ssr_mse_l1_loss",
     "ssr_self_attention_fwd", "ssr_self_attention_bwd", "ssr_self_attention_save_floats", "ssr_self_attention_scratch_floats", "ssr_relu_bwd",
+    "ssr_obj_crop_resize_fwd", "ssr_obj_crop_resize_bwd",
     "ssr_device_info", "ssr_abi_version",
 ]
+OBJ_CROP, OBJ_MAX_SIDE = 32, 128   # SSR_OBJ_CROP, SSR_OBJ_MAX_SIDE: side of a resized object crop, largest box side served (csrc/obj_crop.hip)
 SCAN_MAX_RANGES = 8           # SSR_SCAN_MAX_RANGES: ranges per ssr_nonfinite_scan call
 
 _lib: Optional[C.CDLL] = None
@@ -284,6 +286,8 @@ def lib() -> C.CDLL:
     l.ssr_self_attention_save_floats.argtypes = [i32, i32]
     l.ssr_self_attention_scratch_floats.argtypes = [i32, i32, i32]
     l.ssr_relu_bwd.argtypes = [View, View, View, i64, i32, vp]
+    l.ssr_obj_crop_resize_fwd.argtypes = [View, i32, i32, i32, i32, vp, i32, View, i32, vp]
+    l.ssr_obj_crop_resize_bwd.argtypes = [View, vp, vp, i32, View, i32, i32, i32, i32, f32, i32, vp]
     l.ssr_device_info.argtypes = [C.c_char_p, i32]
     l.ssr_abi_version.argtypes = []
     for s in ABI_SYMBOLS:

@@ -152,6 +152,8 @@ def train_config_from_opt(opt: dict) -> StepConfig:
 
 @MODEL_REGISTRY.register()
 class SSRESRGANModel:
+    D_ARCH = "SSR_UNetDiscriminatorSN"      # network_d.type this model drives (a subclass with another discriminator names its own)
+
     def __init__(self, opt: dict):
         self.opt = opt
         self.is_train = opt.get("is_train", True)
@@ -168,7 +170,7 @@ class SSRESRGANModel:
         self.compute_dtype = self.g_kwargs.pop("compute_dtype", opt.get("compute_dtype", "fp32h"))
         self.feed_disc_lr = bool(opt.get("feed_disc_lr", False))
         if self.is_train:      # test.py builds the model with is_train=False: generator only (SRGANModel.__init__ / init_training_settings)
-            self.d_kwargs = _arch_kwargs(opt["network_d"], "SSR_UNetDiscriminatorSN")
+            self.d_kwargs = _arch_kwargs(opt["network_d"], self.D_ARCH)
             self.d_kwargs.pop("compute_dtype", None)
             self.cfg = train_config_from_opt(opt)
         else:
@@ -192,14 +194,14 @@ class SSRESRGANModel:
         old, self.ts, self._infer = self.ts, None, None
         carry = None
         if old is not None:     # a ragged last batch / another tile size: carry every piece of state over, then free the old step
-            carry = dict(g=old.g_store.state_dict(), d=old.d_store.state_dict(),
+            carry = dict(g=old.g_store.state_dict(), d=self._net_d_state_dict(old),
                          opt=[({k: t.clone() for k, t in o.arenas.items()}, o.step.clone(), o.skipped.clone()) for o in (old.opt_g, old.opt_d)],
                          ema=None if old.opt_g.ema is None else old.opt_g.ema.clone(), it=old.iter)
             del old
             import gc
             gc.collect()
             torch.cuda.empty_cache()
-        self.ts = ESRGANTrainStep(self.g_kwargs, self.d_kwargs, B, h, w, self.compute_dtype, self.cfg, dp=self.dp)
+        self.ts = self._build_step(B, h, w)
         if carry is None:
             self._init_params()
         else:
@@ -218,9 +220,25 @@ class SSRESRGANModel:
         self.ts.opt_g.set_lr(self.current_lrs[0])
         self.ts.opt_d.set_lr(self.current_lrs[1])
 
+    # ---- what a subclass with another discriminator replaces ----
+    def _build_step(self, B, h, w):
+        return ESRGANTrainStep(self.g_kwargs, self.d_kwargs, B, h, w, self.compute_dtype, self.cfg, dp=self.dp)
+
+    def _new_net_d(self):
+        from ..archs.discriminator_arch import SSR_UNetDiscriminatorSN
+        return SSR_UNetDiscriminatorSN(**self.d_kwargs)
+
+    @staticmethod
+    def _net_d_state_dict(ts):
+        return ts.d_store.state_dict()
+
+    @staticmethod
+    def _optimizer_slots(o):
+        """(store, key, optimizer over that store) of the parameters an optimizer steps, in named_parameters() order"""
+        return [(o.store, k, o) for k in o.store.offsets]
+
     def _init_params(self):
         from ..archs.rrdbnet_arch import SSR_RRDBNet
-        from ..archs.discriminator_arch import SSR_UNetDiscriminatorSN
         path = self.opt.get("path", {})
         seed = self.opt.get("manual_seed")
         # initialise under a forked RNG: the caller's global stream (seeded manual_seed + rank by options.py:81 and consumed
@@ -229,7 +247,7 @@ class SSRESRGANModel:
             if seed is not None:
                 torch.manual_seed(int(seed))
             g_sd = SSR_RRDBNet(**self.g_kwargs).state_dict()
-            d_sd = SSR_UNetDiscriminatorSN(**self.d_kwargs).state_dict()
+            d_sd = self._new_net_d().state_dict()
         ema_sd = None
         if path.get("pretrain_network_g"):   # load_network(net_g, path, strict_load_g, param_key_g) + net_g_ema <- 'params_ema'
             ck = torch.load(path["pretrain_network_g"], map_location="cpu")
@@ -350,14 +368,14 @@ class SSRESRGANModel:
     def _optimizer_state_dict(self, o, lr, betas):
         """torch.optim.Adam.state_dict() over the parameters in named_parameters() order (BasicSR setup_optimizers); the other
         optimizers (o.spec): optimizers.optimizer_state_dict."""
-        st = o.store
-        keys = list(st.offsets)
+        slots = self._optimizer_slots(o)
+        keys = [k for _, k, _ in slots]
         if o.spec is not None:
-            per = [{a: st.tensor(k, t) for a, t in o.arenas.items()} for k in keys]
+            per = [{a: st.tensor(k, t) for a, t in part.arenas.items()} for st, k, part in slots]
             return optimizers.optimizer_state_dict(o.spec, lr, per, int(o.step.item()))
         step = float(o.step.item())
-        state = {i: {"step": torch.tensor(step), "exp_avg": st.tensor(k, o.exp_avg).detach().cpu().clone(),
-                     "exp_avg_sq": st.tensor(k, o.exp_avg_sq).detach().cpu().clone()} for i, k in enumerate(keys)}
+        state = {i: {"step": torch.tensor(step), "exp_avg": st.tensor(k, part.exp_avg).detach().cpu().clone(),
+                     "exp_avg_sq": st.tensor(k, part.exp_avg_sq).detach().cpu().clone()} for i, (st, k, part) in enumerate(slots)}
         group = {"lr": lr, "betas": tuple(betas), "eps": self.cfg.eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
                  "foreach": None, "capturable": False, "differentiable": False, "fused": None, "initial_lr": lr,
                  "params": list(range(len(keys)))}
@@ -382,7 +400,7 @@ class SSRESRGANModel:
         if self.ts.opt_g.ema is not None:
             g["params_ema"] = cpu(self.ts.ema_state_dict())
         torch.save(g, os.path.join(mdir, f"net_g_{it}.pth"))
-        torch.save({"params": cpu(self.ts.d_store.state_dict())}, os.path.join(mdir, f"net_d_{it}.pth"))
+        torch.save({"params": cpu(self._net_d_state_dict(self.ts))}, os.path.join(mdir, f"net_d_{it}.pth"))
         cfg = self.cfg
         state = {"epoch": epoch, "iter": current_iter,
                  "optimizers": [self._optimizer_state_dict(self.ts.opt_g, self.current_lrs[0], cfg.betas),
@@ -406,28 +424,30 @@ class SSRESRGANModel:
 
     def _apply_resume_state(self, resume_state: dict):
         for o, s, name in zip((self.ts.opt_g, self.ts.opt_d), resume_state["optimizers"], ("optim_g", "optim_d")):
-            st = o.store
-            keys = list(st.offsets)
+            slots = self._optimizer_slots(o)
+            parts = getattr(o, "parts", (o,))        # (an optimizer over two arenas keeps one step counter per arena)
             per = s["state"]
-            assert len(per) in (0, len(keys)), f"optimizer state has {len(per)} entries, network has {len(keys)} parameters"
+            assert len(per) in (0, len(slots)), f"optimizer state has {len(per)} entries, network has {len(slots)} parameters"
             spec = o.spec if o.spec is not None else dict(optimizers.OPTIM_DEFAULTS["Adam"], type="Adam")
             optimizers.check_resume_type(name, spec, s)      # another optimizer type's state: refused by name
             if o.spec is not None:
-                for i, k in enumerate(keys):
+                for i, (st, k, part) in enumerate(slots):
                     if i in per:
-                        for a, t in o.arenas.items():
+                        for a, t in part.arenas.items():
                             st.tensor(k, t).copy_(per[i][a].to(self.device, torch.float32))
-                o.step.fill_(optimizers.resumed_step(o.spec, s))
+                for part in parts:
+                    part.step.fill_(optimizers.resumed_step(o.spec, s))
                 continue
             step = 0
-            for i, k in enumerate(keys):
+            for i, (st, k, part) in enumerate(slots):
                 if i not in per:
                     continue
                 e = per[i]
-                st.tensor(k, o.exp_avg).copy_(e["exp_avg"].to(self.device, torch.float32))
-                st.tensor(k, o.exp_avg_sq).copy_(e["exp_avg_sq"].to(self.device, torch.float32))
+                st.tensor(k, part.exp_avg).copy_(e["exp_avg"].to(self.device, torch.float32))
+                st.tensor(k, part.exp_avg_sq).copy_(e["exp_avg_sq"].to(self.device, torch.float32))
                 step = int(float(e["step"]))
-            o.step.fill_(step)
+            for part in parts:
+                part.step.fill_(step)
         self.ts.iter = int(resume_state.get("iter", 0))
 
     # ---- validation (ssr_esrgan_model.py:269-352; metrics: psnr / ssim as BasicSR, cpsnr as ssr/metrics/cpsnr.py, lpips as ssr/metrics/lpips.py) ----

@@ -8,12 +8,24 @@ osm_obj_discriminator_arch.py:8-31 SelfAttentionBlock, :49-54 and :74-79 the obj
     object_branch(sd, osm_objs)                o_out of the network from a state_dict; differentiable, any float dtype
     attention_params(sd, prefix)               the dict `p` of one block from a state_dict
 
+and the object crops of OSMObjESRGANModel (ssr/models/osm_objs_esrgan_model.py:166-200), what csrc/obj_crop.hip and the model's host
+side are tested against:
+
+    resize_taps(n_in, n_out, antialias)        the tap rule of the bilinear resize, per output: (first, count, weights)
+    resize_matrix(n_in, n_out, antialias)      the same as a dense [n_out, n_in] matrix
+    crop_resize_reference(img, boxes, aa)      [Bo, C, 32, 32] crops of img [B, C, H, W] for boxes (b, x1, y1, x2, y2); differentiable
+    crop_resize_backward(g, boxes, shape, aa)  its closed-form gradient w.r.t. img (the transpose)
+    fix_box(box) / resolve_boxes(...)          the reference's repair of degenerate boxes, then Python slice semantics
+    flatten_objects(chip_objs)                 the boxes of one chip in dict order, then list order
+    sample_objects(chip_objs, n, rng=random)   the indices the reference keeps, consuming `rng` exactly as it does
+
 Token order is the reference's view(B, -1, W * H): token i = h * W + w.  Every function computes in the dtype of its inputs: pass
 float64 tensors for the float64 statement.
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+import random
+from typing import Dict, List, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -94,3 +106,95 @@ def object_branch(sd: Dict[str, torch.Tensor], osm_objs: torch.Tensor, return_at
         with torch.no_grad():
             return o_out, (attention_forward(to_tokens(o2), p1)[1]["a"], attention_forward(to_tokens(o3), p2)[1]["a"])
     return o_out
+
+
+# =====================================================================================================
+# Object crops of OSMObjESRGANModel
+# =====================================================================================================
+OBJ_CROP = 32             # every crop is resized to 32 x 32 (osm_objs_esrgan_model.py:180-181)
+FIX_LIMIT = 128           # the literal of the fix-up at :173-176: the reference's own, whatever the image size
+
+
+def resize_taps(n_in: int, n_out: int = OBJ_CROP, antialias: bool = False) -> List[Tuple[int, int, List[float]]]:
+    """torchvision.transforms.functional.resize of a float tensor (bilinear, align_corners=False) along one axis: for every output
+    i the first source index, the number of taps and their weights (Python floats = float64), normalised to sum 1.  Without
+    antialiasing, or when enlarging, the support is one source pixel (at most 2 taps); with it and scale >= 1 the triangle is `scale`
+    wide (at most 8 taps at 128 -> 32)."""
+    scale = n_in / n_out
+    support = scale if (antialias and scale >= 1.0) else 1.0
+    out = []
+    for i in range(n_out):
+        center = scale * (i + 0.5)
+        first = max(int(center - support + 0.5), 0)
+        count = min(int(center + support + 0.5), n_in) - first
+        w = [max(0.0, 1.0 - abs((j + first - center + 0.5) / support)) for j in range(count)]
+        total = sum(w)
+        out.append((first, count, [v / total for v in w]))
+    return out
+
+
+def resize_matrix(n_in: int, n_out: int = OBJ_CROP, antialias: bool = False, dtype=torch.float64) -> torch.Tensor:
+    m = torch.zeros(n_out, n_in, dtype=torch.float64)
+    for i, (first, count, w) in enumerate(resize_taps(n_in, n_out, antialias)):
+        m[i, first:first + count] = torch.tensor(w, dtype=torch.float64)
+    return m.to(dtype)
+
+
+def crop_resize_reference(img: torch.Tensor, boxes: Sequence[Sequence[int]], antialias: bool = False) -> torch.Tensor:
+    """img [B, C, H, W], boxes (b, x1, y1, x2, y2) already fixed up and slice-resolved -> [Bo, C, 32, 32] in img's dtype; the 2-D weight
+    is the product of the two axes' weights.  Plain tensor algebra: autograd differentiates it."""
+    out = []
+    for b, x1, y1, x2, y2 in boxes:
+        my = resize_matrix(y2 - y1, OBJ_CROP, antialias, img.dtype)
+        mx = resize_matrix(x2 - x1, OBJ_CROP, antialias, img.dtype)
+        out.append(my @ img[b, :, y1:y2, x1:x2] @ mx.t())
+    return torch.stack(out)
+
+
+def crop_resize_backward(g: torch.Tensor, boxes: Sequence[Sequence[int]], shape: Sequence[int], antialias: bool = False) -> torch.Tensor:
+    """the gradient of sum(crop_resize_reference(img) * g) w.r.t. img of `shape` [B, C, H, W]: every box adds My^T g Mx to its window"""
+    d = torch.zeros(*shape, dtype=g.dtype)
+    for o, (b, x1, y1, x2, y2) in enumerate(boxes):
+        my = resize_matrix(y2 - y1, OBJ_CROP, antialias, g.dtype)
+        mx = resize_matrix(x2 - x1, OBJ_CROP, antialias, g.dtype)
+        d[b, :, y1:y2, x1:x2] += my.t() @ g[o] @ mx
+    return d
+
+
+def fix_box(box: Sequence[int]) -> Tuple[int, int, int, int]:
+    """osm_objs_esrgan_model.py:173-176: a box of zero width / height is widened by one pixel, to the right / downwards unless its far
+    edge is at 128 or beyond"""
+    x1, y1, x2, y2 = (int(v) for v in box)
+    if x1 == x2:
+        x1, x2 = (x1, x2 + 1) if x2 < FIX_LIMIT else (x1 - 1, x2)
+    if y1 == y2:
+        y1, y2 = (y1, y2 + 1) if y2 < FIX_LIMIT else (y1 - 1, y2)
+    return x1, y1, x2, y2
+
+
+def flatten_objects(chip_objs: Dict[str, Sequence[Sequence[int]]]) -> List[Sequence[int]]:
+    """:168-169: every box of a chip in dict order, then list order"""
+    return [o for v in chip_objs.values() for o in v]
+
+
+def resolve_boxes(objs: Sequence[Sequence[int]], H: int, W: int, chip: str = "?") -> List[Tuple[int, int, int, int]]:
+    """fix_box, then `[:, y1:y2, x1:x2]` under Python slice semantics (negative and over-long indices as slice.indices resolves
+    them) -> (x1, y1, x2, y2) with 0 <= x1 < x2 <= W, 0 <= y1 < y2 <= H.  An empty crop, on which the reference's resize crashes,
+    raises ValueError naming the chip."""
+    out = []
+    for i, o in enumerate(objs):
+        x1, y1, x2, y2 = fix_box(o)
+        ys, ye, _ = slice(y1, y2).indices(H)
+        xs, xe, _ = slice(x1, x2).indices(W)
+        if ye <= ys or xe <= xs:
+            raise ValueError(f"chip {chip!r}: object {i} with box {list(o)} is an empty crop of a {H} x {W} image")
+        out.append((xs, ys, xe, ye))
+    return out
+
+
+def sample_objects(chip_objs: Dict[str, Sequence[Sequence[int]]], n: int, rng=random) -> List[int]:
+    """:195-198: random.sample over the index list, once per image; the chosen objects stay in ascending index order.  Fewer than n
+    objects: random.sample's own ValueError."""
+    total = len(flatten_objects(chip_objs))
+    picked = rng.sample([i for i in range(0, total)], n)
+    return [g for g in range(total) if g in picked]
