@@ -671,6 +671,28 @@ int ssr_lpips_layer_blocks(int32_t N, int32_t HW, int32_t C);
 int ssr_lpips_layer(ssr_view fa, ssr_view fb, const float* w, int32_t dtype, int32_t N, int32_t HW, int32_t C, int32_t relu,
                     double* partial, void* stream);
 
+/* ---- The geometries of LPIPS's AlexNet backbone outside ssr_conv2d's families (csrc/conv_direct.hip; `calculate_lpips`, lpips_model
+ *      'alexnet'; additive: the ABI version stays 3) ----
+ * ssr_conv_direct: exact-fp32 direct convolution, y = [relu](conv(x, w) + bias).  x is an NHWC fp32 view (SSR_F32 / SSR_F32X3
+ *   storage) of N x Hi x Wi pixels of which the Cin channels from x.coff on are contracted; y an NHWC fp32 view of N x Ho x Wo pixels,
+ *   Ho = (Hi + 2 pad - K) / stride + 1 (floor; Wo likewise), of which the Cout channels from y.coff on are written and no other.  w is
+ *   ONE device array [K * K][Cin][Cout] of fp32 (tap ky * K + kx; the reference layout [Cout][Cin][K][K] permuted (2, 3, 1, 0) on the
+ *   host; a layer with fewer input channels than the view, as the 3 of ssr_lpips_input's 8, pads Cin with ZERO weights), bias Cout
+ *   floats or NULL.  Square odd kernels K <= 11, stride 1 .. 4, symmetric zero padding pad <= K / 2, Cin % 8 == 0, Cout % 32 == 0,
+ *   both <= 512; any input grid with at least one output pixel, grids smaller than the kernel included.  Arithmetic:
+ *   v_mfma_f32_32x32x2_f32, per output ONE fp32 accumulator chain over ky, kx, c ascending (tap rows wholly in the padding skipped),
+ *   bias added last; no split of K, no atomics: two launches give the same bytes, and an image's bytes depend neither on N nor on the
+ *   other images of the launch.  Both views 16-byte aligned (cs % 4 == 0, coff % 4 == 0), w 16-byte aligned.
+ *   SSR_EINVAL: a null x, y or w, a size <= 0, pad < 0, Hi + 2 pad < K (or Wi), a view narrower than coff + channels or misaligned.
+ *   SSR_EUNSUP: bf16 storage, K even or > 11, stride > 4, pad > K / 2, Cin % 8, Cout % 32, Cin or Cout > 512.  No launch in either case.
+ * ssr_maxpool3s2_fwd: P[N, (H - 3) / 2 + 1, (W - 3) / 2 + 1, C] = maxpool 3x3 stride 2 of F[N, H, W, C], no padding, floor mode
+ *   (trailing rows and columns that do not fill a window are dropped), after max(0, .) when relu != 0; fp32 NHWC views, 16-byte
+ *   aligned as above; bit-exact (a NaN in a window gives NaN).  SSR_EINVAL: a null view, N or C <= 0, H or W < 3, a view narrower
+ *   than coff + C or misaligned; SSR_EUNSUP: bf16 storage, C % 4 != 0.  No launch in either case. */
+int ssr_conv_direct(ssr_view x, ssr_view y, const float* w, const float* bias, int32_t dtype, int32_t N, int32_t Hi, int32_t Wi,
+                    int32_t Cin, int32_t Cout, int32_t K, int32_t stride, int32_t pad, int32_t relu, void* stream);
+int ssr_maxpool3s2_fwd(ssr_view f, ssr_view p, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t relu, void* stream);
+
 /* SSR_F32X3 weight gradients: split an fp32 buffer (n % 4 == 0 elements) into bf16 planes hi = bf16(x), lo = bf16(x - hi); the
  * bf16 wgrad kernel then accumulates (x_hi, dy_hi) + (x_hi, dy_lo) + (x_lo, dy_hi) into the fp32 gradient. */
 int ssr_split_bf16(const float* x, void* hi, void* lo, int64_t n, void* stream);

@@ -174,6 +174,7 @@ ABI_SYMBOLS = [
     "ssr_scene_support_add", "ssr_scene_apply_nodata",
     "ssr_scene_gather_tf", "ssr_scene_blend_add_tf", "ssr_scene_blend_finish_scaled",
     "ssr_lpips_input", "ssr_lpips_layer_blocks", "ssr_lpips_layer",
+    "ssr_conv_direct", "ssr_maxpool3s2_fwd",
     "ssr_prelu_reflect_fwd", "ssr_prelu_reflect_bwd", "ssr_sr_tail_fwd", "ssr_sr_tail_bwd", "ssr_sr_tail_scratch_bytes",
     "ssr_dropout_mask", "ssr_mse_l1_loss",
     "ssr_self_attention_fwd", "ssr_self_attention_bwd", "ssr_self_attention_save_floats", "ssr_self_attention_scratch_floats", "ssr_relu_bwd",
@@ -274,6 +275,8 @@ def lib() -> C.CDLL:
     l.ssr_lpips_input.argtypes = [vp, View, i32, i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(i32), i32, vp]
     l.ssr_lpips_layer_blocks.argtypes = [i32, i32, i32]
     l.ssr_lpips_layer.argtypes = [View, View, vp, i32, i32, i32, i32, i32, vp, vp]
+    l.ssr_conv_direct.argtypes = [View, View, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    l.ssr_maxpool3s2_fwd.argtypes = [View, View, i32, i32, i32, i32, i32, i32, vp]
     l.ssr_prelu_reflect_fwd.argtypes = [C.POINTER(PreluReflectDesc), vp]
     l.ssr_prelu_reflect_bwd.argtypes = [C.POINTER(PreluReflectDesc), vp]
     l.ssr_sr_tail_fwd.argtypes = [C.POINTER(SrTailDesc), vp]

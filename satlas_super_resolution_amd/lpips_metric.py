@@ -19,7 +19,18 @@ Two quirks of the reference are the defaults here, because users compare against
 The VGG16 forward runs on the conv kernels in exact fp32 whatever the model's compute_dtype (a reported number, and validation is
 not the hot loop); the scaling layer and the per-tap arithmetic are csrc/lpips.hip.
 
+The second backbone of the reference's function, `lpips_model: alexnet` (net 'alex' of the package, its default), shares the scaling
+layer, the `lin{k}` layers and the formula; only F_k differs:
+
+    F_k             the post-ReLU outputs of the five convolutions of torchvision's AlexNet `features` (indices 0, 3, 6, 8, 10):
+                    3->64 11x11 s4 p2 | maxpool 3x3 s2 | 64->192 5x5 p2 | maxpool 3x3 s2 | 192->384, 384->256, 256->256 3x3 p1      [recalled]
+                    (the package's slices features[0:2], [2:5], [5:8], [8:10], [10:12])                                          [recalled]
+
+Its first two convolutions and its pooling are csrc/conv_direct.hip (ssr_conv_direct, ssr_maxpool3s2_fwd); the three 3x3 layers run
+through ssr_conv2d in exact fp32 like VGG's.  Every function below takes the backbone as `net` ('vgg' by default, 'alex').
+
     vgg16_layers / vgg16_specs     the layer table
+    alexnet_layers / alexnet_specs / alexnet_tap_sizes      the second backbone's
     load_lpips_state               torchvision + lpips files, one lpips state_dict, or the flat layout -> flat layout
     lpips_random_state             random weights of the same architecture (tests, throughput runs)
     lpips_reference                the definition in torch on the CPU
@@ -44,9 +55,23 @@ LPIPS_EPS = 1e-10
 # (block, convs in the block, width)
 VGG16_BLOCKS = ((1, 2, 64), (2, 2, 128), (3, 3, 256), (4, 3, 512), (5, 3, 512))
 LPIPS_TAPS = ("conv1_2", "conv2_2", "conv3_3", "conv4_3", "conv5_3")
+LPIPS_ALEX_PRETRAIN_PATH = "experiments/pretrained_models/lpips_alex.pth"
+# (name, torchvision features index, cin, cout, kernel, stride, pad, pooled_before); every layer is a tap       [recalled]
+ALEXNET_LAYERS = (("conv1", 0, 3, 64, 11, 4, 2, False), ("conv2", 3, 64, 192, 5, 1, 2, True), ("conv3", 6, 192, 384, 3, 1, 1, True),
+                  ("conv4", 8, 384, 256, 3, 1, 1, False), ("conv5", 10, 256, 256, 3, 1, 1, False))
+LPIPS_ALEX_TAPS = tuple(l[0] for l in ALEXNET_LAYERS)
+ALEXNET_MIN_SIDE = 31              # the smallest side that leaves a pixel behind both poolings: taps of 7, 3, 1, 1, 1
 # keys of a `calculate_lpips` metric entry: the reference's **kwargs swallows the first four
 _IGNORED_KEYS = ("crop_border", "test_y_channel", "input_order", "better", "type")
-_OUR_KEYS = ("lpips_model", "lpips_weights", "vgg16_path", "lin_path", "rgb", "normalize")
+_OUR_KEYS = ("lpips_model", "lpips_weights", "vgg16_path", "alexnet_path", "lin_path", "rgb", "normalize")
+_NETS = {"vgg": "vgg", "vgg16": "vgg", "alex": "alex", "alexnet": "alex"}
+
+
+def _net(net: str) -> str:
+    """'vgg' | 'alex' from an option value (`lpips_model: vgg | alexnet`) or the package's name (net='vgg' | 'alex')"""
+    if net not in _NETS:
+        raise NotImplementedError(f"metric type 'calculate_lpips': lpips_model={net!r}: the reference offers 'alexnet' and 'vgg'")
+    return _NETS[net]
 
 
 def vgg16_layers():
@@ -67,20 +92,66 @@ def vgg16_specs():
     return [engine.ConvSpec(f"features.{idx}", cout, cin, 3, 1, True, False, dgrad_packed=False) for _, idx, cin, cout, _ in vgg16_layers()]
 
 
-def _tap_widths() -> List[int]:
+def alexnet_layers():
+    """[(name 'convJ', torchvision features index, cin, cout, kernel, stride, pad, pooled_before)]"""
+    return list(ALEXNET_LAYERS)
+
+
+def alexnet_specs():
+    """the 3x3 layers, which ssr_conv2d runs (conv1 and conv2 go through ssr_conv_direct and are not in a ParamStore)"""
+    from . import engine
+    return [engine.ConvSpec(f"features.{idx}", cout, cin, 3, 1, True, False, dgrad_packed=False)
+            for _, idx, cin, cout, k, _, _, _ in ALEXNET_LAYERS if k == 3]
+
+
+def alexnet_tap_sizes(H: int, W: int) -> List[Tuple[int, int]]:
+    """(h, w) of the five taps of an H x W image; ValueError below 31 (no divisibility is needed above it)"""
+    if H < ALEXNET_MIN_SIDE or W < ALEXNET_MIN_SIDE:
+        raise ValueError(f"LPIPS (AlexNet: 11x11 stride-4 convolution, two 3x3 stride-2 poolings) needs H and W >= {ALEXNET_MIN_SIDE}, "
+                         f"got {H} x {W}")
+    out, h, w = [], H, W
+    for _, _, _, _, k, s, p, pooled_before in ALEXNET_LAYERS:
+        if pooled_before:
+            h, w = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+        h, w = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+        out.append((h, w))
+    return out
+
+
+def _conv_table(net: str = "vgg") -> List[Tuple[int, Tuple[int, int, int, int]]]:
+    """[(torchvision features index, weight shape)] of the backbone's convolutions"""
+    if _net(net) == "alex":
+        return [(idx, (cout, cin, k, k)) for _, idx, cin, cout, k, _, _, _ in ALEXNET_LAYERS]
+    return [(idx, (cout, cin, 3, 3)) for _, idx, cin, cout, _ in vgg16_layers()]
+
+
+def _tap_names(net: str = "vgg") -> Tuple[str, ...]:
+    return LPIPS_ALEX_TAPS if _net(net) == "alex" else LPIPS_TAPS
+
+
+def _tap_widths(net: str = "vgg") -> List[int]:
+    if _net(net) == "alex":
+        return [l[3] for l in ALEXNET_LAYERS]
     width = {n: cout for n, _, _, cout, _ in vgg16_layers()}
     return [width[t] for t in LPIPS_TAPS]
 
 
-def lpips_random_state(seed: int = 0) -> Dict[str, torch.Tensor]:
-    """Flat layout.  Convolutions as torchvision's VGG._initialize_weights (kaiming_normal_(fan_out, relu), zero bias), `lin`
-    weights from U[0, 1) (the package's are non-negative: the metric is a weighted sum of squares)."""
+def lpips_random_state(seed: int = 0, net: str = "vgg") -> Dict[str, torch.Tensor]:
+    """Flat layout.  VGG: convolutions as torchvision's VGG._initialize_weights (kaiming_normal_(fan_out, relu), zero bias).
+    AlexNet: torchvision's AlexNet keeps nn.Conv2d's default, weights and biases from U(-b, b), b = 1 / sqrt(fan_in) [recalled], so
+    its biases are not zero.  `lin` weights from U[0, 1) (the package's are non-negative: the metric is a weighted sum of squares)."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
-    for _, idx, cin, cout, _ in vgg16_layers():
-        sd[f"features.{idx}.weight"] = torch.randn(cout, cin, 3, 3, generator=g) * math.sqrt(2.0 / (cout * 9))
-        sd[f"features.{idx}.bias"] = torch.zeros(cout)
-    for k, c in enumerate(_tap_widths()):
+    if _net(net) == "alex":
+        for idx, shape in _conv_table("alex"):
+            b = 1.0 / math.sqrt(shape[1] * shape[2] * shape[3])
+            sd[f"features.{idx}.weight"] = (2 * torch.rand(*shape, generator=g) - 1) * b
+            sd[f"features.{idx}.bias"] = (2 * torch.rand(shape[0], generator=g) - 1) * b
+    else:
+        for _, idx, cin, cout, _ in vgg16_layers():
+            sd[f"features.{idx}.weight"] = torch.randn(cout, cin, 3, 3, generator=g) * math.sqrt(2.0 / (cout * 9))
+            sd[f"features.{idx}.bias"] = torch.zeros(cout)
+    for k, c in enumerate(_tap_widths(net)):
         sd[f"lin{k}"] = torch.rand(c, generator=g)
     return sd
 
@@ -93,18 +164,20 @@ def _torch_load(path: str) -> Dict[str, torch.Tensor]:
     return sd
 
 
-def load_lpips_state(backbone_path: str, lin_path: Optional[str] = None) -> Dict[str, torch.Tensor]:
+def load_lpips_state(backbone_path: str, lin_path: Optional[str] = None, net: str = "vgg") -> Dict[str, torch.Tensor]:
     """-> {features.{idx}.weight / .bias (13 convolutions), lin{k} [C_k] (5 taps)}, float32, from any of   [recalled]
       * torchvision's vgg16-397923af.pth (`features.{idx}.*`) + the lpips package's weights/v0.1/vgg.pth (`lin{k}.model.1.weight`);
       * one file saved from lpips.LPIPS(net='vgg').state_dict(): `net.slice{s}.{idx}.*` with the same torchvision indices and
         `lin{k}.model.1.weight` (the duplicate `lins.{k}.*` and the `scaling_layer.*` keys are ignored);
       * the flat layout itself.
-    KeyError / ValueError name the key that is missing / mis-shaped."""
+    net='alex': the same three with torchvision's alexnet-owt-7be5be79.pth (`features.{0,3,6,8,10}.*`, 5 convolutions), the package's
+    weights/v0.1/alex.pth and lpips.LPIPS(net='alex').state_dict() (`net.slice{1..5}.{0,3,6,8,10}.*`).                     [recalled]
+    KeyError / ValueError name the key that is missing / mis-shaped; the other backbone's file fails so on its first key."""
     sd = dict(_torch_load(backbone_path))
     lin_sd = _torch_load(lin_path) if lin_path else {}
     out = {}
-    for _, idx, cin, cout, _ in vgg16_layers():
-        for leaf, shape in (("weight", (cout, cin, 3, 3)), ("bias", (cout,))):
+    for idx, wshape in _conv_table(net):
+        for leaf, shape in (("weight", wshape), ("bias", wshape[:1])):
             key = f"features.{idx}.{leaf}"
             cands = [key] + [f"net.slice{s}.{idx}.{leaf}" for s in range(1, 6)]
             src = next((c for c in cands if c in sd), None)
@@ -114,7 +187,7 @@ def load_lpips_state(backbone_path: str, lin_path: Optional[str] = None) -> Dict
             if tuple(t.shape) != shape:
                 raise ValueError(f"{src}: shape {tuple(t.shape)}, expected {shape}")
             out[key] = t.detach().to(torch.float32).clone()
-    for k, c in enumerate(_tap_widths()):
+    for k, c in enumerate(_tap_widths(net)):
         key = f"lin{k}"
         cands = [(lin_sd, f"lin{k}.model.1.weight"), (lin_sd, key), (sd, key), (sd, f"lin{k}.model.1.weight")]
         hit = next(((d, n) for d, n in cands if n in d), None)
@@ -154,6 +227,18 @@ def vgg16_tap_features(x: torch.Tensor, state: Dict[str, torch.Tensor]) -> Dict[
     return feats
 
 
+def alexnet_tap_features(x: torch.Tensor, state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """the five post-ReLU taps of an NCHW input, AlexNet backbone"""
+    feats = {}
+    for name, idx, _, _, _, stride, pad, pooled_before in ALEXNET_LAYERS:
+        if pooled_before:
+            x = F.max_pool2d(x, 3, 2)
+        x = F.relu(F.conv2d(x, state[f"features.{idx}.weight"].to(x.dtype), state[f"features.{idx}.bias"].to(x.dtype), stride=stride,
+                            padding=pad))
+        feats[name] = x
+    return feats
+
+
 def lpips_from_features(feats0: Dict[str, torch.Tensor], feats1: Dict[str, torch.Tensor], lins: Dict[str, torch.Tensor]) -> torch.Tensor:
     """step 3 and 4 of the definition for any set of taps: feats*[name] is [N, C, H, W] (post-ReLU), lins[name] is [C] -> [N]"""
     total = None
@@ -167,24 +252,30 @@ def lpips_from_features(feats0: Dict[str, torch.Tensor], feats1: Dict[str, torch
 
 
 def lpips_reference(a_u8, b_u8, state: Dict[str, torch.Tensor], bgr: bool = True, normalize: bool = False,
-                    dtype=torch.float64) -> torch.Tensor:
-    """LPIPS(net='vgg', version='0.1') of uint8 [N, H, W, 3] RGB image pairs as the reference feeds it (module docstring) -> [N]"""
+                    dtype=torch.float64, net: str = "vgg") -> torch.Tensor:
+    """LPIPS(net='vgg' | 'alex', version='0.1') of uint8 [N, H, W, 3] RGB image pairs as the reference feeds it (module docstring) -> [N]"""
+    taps = alexnet_tap_features if _net(net) == "alex" else vgg16_tap_features
     with torch.no_grad():
-        f0 = vgg16_tap_features(lpips_scaled_input(a_u8, bgr, normalize, dtype), state)
-        f1 = vgg16_tap_features(lpips_scaled_input(b_u8, bgr, normalize, dtype), state)
-        return lpips_from_features(f0, f1, {t: state[f"lin{k}"] for k, t in enumerate(LPIPS_TAPS)})
+        f0 = taps(lpips_scaled_input(a_u8, bgr, normalize, dtype), state)
+        f1 = taps(lpips_scaled_input(b_u8, bgr, normalize, dtype), state)
+        return lpips_from_features(f0, f1, {t: state[f"lin{k}"] for k, t in enumerate(_tap_names(net))})
 
 
 # ---------------------------------------------------------------- the device path
 class LPIPSPlan:
     """One static launch list for N image pairs of H x W: ssr_lpips_input for both images (one batch of 2N), the 13 convolutions
     with the ReLU epilogue (the tapped ones stored before their ReLU), ssr_relu_maxpool2_fwd behind taps 1-4, five ssr_lpips_layer.
-    The ParamStore is the exact fp32 mode's; `store` shares one (already loaded and packed) between the plans of a LPIPSModel."""
+    The ParamStore is the exact fp32 mode's; `store` shares one (already loaded and packed) between the plans of a LPIPSModel.
+    net='alex': the AlexNet launch list (_init_alex), any H, W >= 31."""
 
     def __init__(self, N: int, H: int, W: int, state: Optional[Dict[str, torch.Tensor]], device="cuda", bgr: bool = True,
-                 normalize: bool = False, store=None, lins: Optional[torch.Tensor] = None):
+                 normalize: bool = False, store=None, lins: Optional[torch.Tensor] = None, net: str = "vgg", direct=None):
         from . import engine, hip
         from .hip import view
+        self.net = _net(net)
+        if self.net == "alex":
+            self._init_alex(N, H, W, state, device, bgr, normalize, store, lins, direct)
+            return
         if N <= 0 or H <= 0 or W <= 0 or H % 16 or W % 16:
             raise ValueError(f"LPIPS (VGG16, four poolings) needs H and W divisible by 16, got {N} x {H} x {W}")
         dev = torch.device(device)
@@ -225,19 +316,84 @@ class LPIPSPlan:
                     self.pooled[name] = z(B, h // 2, w // 2, cout)
                     L.add(lib.ssr_relu_maxpool2_fwd, view(dst), view(self.pooled[name]), hip.F32, B, h, w, cout, what=f"relu+pool {name}")
                     src = self.pooled[name]
-        # partials: per tap [N][nblk] doubles, one buffer, one download
+        self._add_taps(L, taps, relu=1)
+        self.launcher = L
+
+    def _add_taps(self, L, taps, relu: int):
+        """the five ssr_lpips_layer launches over self.acts; partials: per tap [N][nblk] doubles, one buffer, one download"""
+        from . import hip
+        from .hip import view
+        lib, N = hip.lib(), self.N
         self.slices, off, woff = [], 0, 0
         for name, hw, c in taps:
             nblk = lib.ssr_lpips_layer_blocks(N, hw, c)
             hip.check(min(nblk, 0), f"ssr_lpips_layer_blocks {name}")
             self.slices.append((off, nblk))
             off += N * nblk
-        self.partial = torch.zeros(off, dtype=torch.float64, device=dev)
+        self.partial = torch.zeros(off, dtype=torch.float64, device=self.lins.device)
         for (name, hw, c), (poff, nblk) in zip(taps, self.slices):
             f = self.acts[name]
-            L.add(lib.ssr_lpips_layer, view(f[:N]), view(f[N:]), self.lins.data_ptr() + 4 * woff, hip.F32, N, hw, c, 1,
+            L.add(lib.ssr_lpips_layer, view(f[:N]), view(f[N:]), self.lins.data_ptr() + 4 * woff, hip.F32, N, hw, c, relu,
                   self.partial.data_ptr() + 8 * poff, what=f"lpips layer {name}")
             woff += c
+
+    def _init_alex(self, N, H, W, state, device, bgr, normalize, store, lins, direct):
+        """AlexNet: ssr_lpips_input for both images (one batch of 2N), conv1 and conv2 through ssr_conv_direct, ssr_maxpool3s2_fwd
+        behind taps 1 and 2, conv3..5 through ssr_conv2d in exact fp32 (ssr_conv_direct where ssr_conv2d answers SSR_EUNSUP for the
+        grid: asked once here through ssr_conv2d_variant, a question of the shape and never of the batch), every tap stored AFTER its
+        ReLU, five ssr_lpips_layer with relu = 0.  `direct`: {layer name: (weights [K*K][Cin][Cout], bias)} on the device."""
+        from . import engine, hip
+        from .hip import view
+        if N <= 0:
+            raise ValueError(f"LPIPS needs at least one image pair, got N = {N}")
+        sizes = alexnet_tap_sizes(H, W)                  # ValueError below 31
+        dev = torch.device(device)
+        self.N, self.H, self.W = N, H, W
+        if store is None:
+            store, lins, direct = _device_weights(state, dev, "alex")
+        self.store, self.lins, self.direct = store, lins, direct
+        lib = hip.lib()
+        B = 2 * N
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)      # noqa: E731
+        self.a_u8 = torch.zeros(N, H, W, 3, dtype=torch.uint8, device=dev)
+        self.b_u8 = torch.zeros(N, H, W, 3, dtype=torch.uint8, device=dev)
+        self.xn = z(B, H, W, 8)
+        self._shift = (C.c_float * 3)(*LPIPS_SHIFT)
+        self._scale = (C.c_float * 3)(*LPIPS_SCALE)
+        self._perm = (C.c_int32 * 3)(*((2, 1, 0) if bgr else (0, 1, 2)))
+        cb = engine._ConvBuilder(store, B)
+        self._cb = cb
+        L = engine.Launcher()
+        npix = N * H * W
+        L.add(lib.ssr_lpips_input, self.a_u8.data_ptr(), view(self.xn[:N]), hip.F32, npix, self._shift, self._scale, self._perm,
+              1 if normalize else 0, what="lpips input (image 1)")
+        L.add(lib.ssr_lpips_input, self.b_u8.data_ptr(), view(self.xn[N:]), hip.F32, npix, self._shift, self._scale, self._perm,
+              1 if normalize else 0, what="lpips input (image 2)")
+        self.acts, self.pooled, taps = {}, {}, []
+        src, h, w = self.xn, H, W
+        for (name, idx, cin, cout, k, stride, pad, pooled_before), (ho, wo) in zip(ALEXNET_LAYERS, sizes):
+            if pooled_before:
+                ph, pw = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+                p = self.pooled[name] = z(B, ph, pw, src.shape[-1])
+                L.add(lib.ssr_maxpool3s2_fwd, view(src), view(p), hip.F32, B, h, w, src.shape[-1], 0, what=f"pool in front of {name}")
+                src, h, w = p, ph, pw
+            dst = self.acts[name] = z(B, ho, wo, cout)
+            use_direct = k != 3
+            if not use_direct:
+                cb.conv(L, f"features.{idx}", view(src), h, w, view(dst), act=hip.ACT_RELU)
+                rc = lib.ssr_conv2d_variant(C.byref(cb.keep[-1]))
+                if rc == -2:                              # SSR_EUNSUP for this grid: the generic kernel
+                    L.calls.pop()
+                    use_direct = True
+                elif rc < 0:
+                    hip.check(rc, f"ssr_conv2d_variant {name}")
+            if use_direct:
+                wd, bd = self.direct[name]
+                L.add(lib.ssr_conv_direct, view(src), view(dst), wd.data_ptr(), bd.data_ptr(), hip.F32, B, h, w, wd.shape[1], cout, k,
+                      stride, pad, 1, what=f"conv direct {name}")
+            taps.append((name, ho * wo, cout))
+            src, h, w = dst, ho, wo
+        self._add_taps(L, taps, relu=0)
         self.launcher = L
 
     def run(self, a_u8: torch.Tensor, b_u8: torch.Tensor) -> torch.Tensor:
@@ -252,39 +408,62 @@ class LPIPSPlan:
         return torch.from_numpy(total.copy())
 
 
-def _device_weights(state: Dict[str, torch.Tensor], dev):
-    """(ParamStore of the VGG16 convolutions in the exact fp32 mode, loaded and packed; the five lin vectors as one fp32 tensor)"""
+def _device_weights(state: Dict[str, torch.Tensor], dev, net: str = "vgg"):
+    """VGG: (ParamStore of the VGG16 convolutions in the exact fp32 mode, loaded and packed; the five lin vectors as one fp32 tensor).
+    AlexNet: (ParamStore of its three 3x3 layers, the same; the lin vectors; {layer: (weights [K*K][CinPad][Cout], bias)} in
+    ssr_conv_direct's layout for all five layers, permuted here in torch: conv1's 3 input channels padded with zero weights to the 8
+    channels ssr_lpips_input writes)."""
     from . import engine, hip
-    widths = _tap_widths()
+    net = _net(net)
+    widths = _tap_widths(net)
     for k, c in enumerate(widths):
         if f"lin{k}" not in state:
             raise KeyError(f"lin{k}")
         if tuple(state[f"lin{k}"].shape) != (c,):
             raise ValueError(f"lin{k}: shape {tuple(state[f'lin{k}'].shape)}, expected ({c},)")
-    store = engine.ParamStore(vgg16_specs(), hip.F32, device=dev)
+    direct = {}
+    if net == "alex":
+        for name, idx, cin, cout, k, _, _, _ in ALEXNET_LAYERS:
+            for leaf, shape in (("weight", (cout, cin, k, k)), ("bias", (cout,))):
+                key = f"features.{idx}.{leaf}"
+                if key not in state:
+                    raise KeyError(key)
+                if tuple(state[key].shape) != shape:
+                    raise ValueError(f"{key}: shape {tuple(state[key].shape)}, expected {shape}")
+            wd = torch.zeros(k * k, -(-cin // 8) * 8, cout, dtype=torch.float32)
+            wd[:, :cin] = state[f"features.{idx}.weight"].detach().to(torch.float32).permute(2, 3, 1, 0).reshape(k * k, cin, cout)
+            direct[name] = (wd.to(dev), state[f"features.{idx}.bias"].detach().to(torch.float32).contiguous().to(dev))
+    store = engine.ParamStore(alexnet_specs() if net == "alex" else vgg16_specs(), hip.F32, device=dev)
     store.load_state_dict(state)
     store.pack()
     lins = torch.cat([state[f"lin{k}"].to(torch.float32) for k in range(len(widths))]).to(dev)
-    return store, lins
+    return (store, lins, direct) if net == "alex" else (store, lins)
 
 
 class LPIPSModel:
-    """The weights on the device and the plans that use them, cached per (N, H, W, bgr, normalize)."""
+    """The weights of one backbone on the device and the plans that use them, cached per (N, H, W, bgr, normalize)."""
 
-    def __init__(self, state: Dict[str, torch.Tensor], device="cuda"):
+    def __init__(self, state: Dict[str, torch.Tensor], device="cuda", net: str = "vgg"):
         self.device = torch.device(device)
-        self.store, self.lins = _device_weights(state, self.device)
+        self.net = _net(net)
+        self.direct = None
+        if self.net == "alex":
+            self.store, self.lins, self.direct = _device_weights(state, self.device, "alex")
+        else:
+            self.store, self.lins = _device_weights(state, self.device)
         self.plans: Dict[Tuple, LPIPSPlan] = {}
 
     def plan(self, N: int, H: int, W: int, bgr: bool = True, normalize: bool = False) -> LPIPSPlan:
         key = (N, H, W, bool(bgr), bool(normalize))
         if key not in self.plans:
-            self.plans[key] = LPIPSPlan(N, H, W, None, self.device, bgr=bgr, normalize=normalize, store=self.store, lins=self.lins)
+            self.plans[key] = LPIPSPlan(N, H, W, None, self.device, bgr=bgr, normalize=normalize, store=self.store, lins=self.lins,
+                                        net=self.net, direct=self.direct)
         return self.plans[key]
 
 
 def lpips_distance(a_u8: torch.Tensor, b_u8: torch.Tensor, model: LPIPSModel, bgr: bool = True, normalize: bool = False) -> torch.Tensor:
-    """a_u8, b_u8: uint8 [N, H, W, 3] RGB device tensors as `tensor2img_u8` gives them -> float64 [N] on the host."""
+    """a_u8, b_u8: uint8 [N, H, W, 3] RGB device tensors as `tensor2img_u8` gives them -> float64 [N] on the host.  The backbone is
+    the model's."""
     if not (a_u8.shape == b_u8.shape and a_u8.dtype == torch.uint8 and b_u8.dtype == torch.uint8 and a_u8.is_cuda and b_u8.is_cuda):
         raise ValueError(f"Image shapes are different: {tuple(a_u8.shape)}, {tuple(b_u8.shape)} (uint8 device tensors)")
     if a_u8.dim() != 4 or a_u8.shape[-1] != 3:
@@ -295,50 +474,62 @@ def lpips_distance(a_u8: torch.Tensor, b_u8: torch.Tensor, model: LPIPSModel, bg
 
 # ---------------------------------------------------------------- the metric entry
 _MODELS: Dict[Tuple, LPIPSModel] = {}
+# per backbone: (option value, the backbone key, the other backbone's key, environment variable, default file, the package's net name,
+#                torchvision's file, the package's lin file)
+_BACKBONES = {
+    "vgg": ("vgg", "vgg16_path", "alexnet_path", "SSR_LPIPS_WEIGHTS", LPIPS_PRETRAIN_PATH, "vgg", "vgg16-397923af.pth", "vgg.pth"),
+    "alex": ("alexnet", "alexnet_path", "vgg16_path", "SSR_LPIPS_ALEX_WEIGHTS", LPIPS_ALEX_PRETRAIN_PATH, "alex", "alexnet-owt-7be5be79.pth",
+             "alex.pth"),
+}
 
 
 def check_lpips_opt(lpips_model="vgg", **kw) -> Tuple[str, Optional[str]]:
     """Validates the keys of a `calculate_lpips` entry and finds the weights -> (backbone or combined file, lin file or None).
     Touches no device: the model plugin calls it before the first validation image is processed."""
-    if lpips_model != "vgg":
-        raise NotImplementedError(f"metric type 'calculate_lpips': lpips_model={lpips_model!r}: only 'vgg' (alexnet needs 11x11 stride-4 "
-                                  "and 5x5 convolutions and 3x3 stride-2 pooling; no shipped option file asks for it)")
+    if lpips_model not in ("vgg", "alexnet"):             # the reference's two branches, by their names there
+        raise NotImplementedError(f"metric type 'calculate_lpips': lpips_model={lpips_model!r}: the reference offers 'alexnet' and 'vgg'")
+    net = _net(lpips_model)
+    model, bkey, other, env, default, pkg, tv_file, lin_file = _BACKBONES[net]
     for k in kw:
         if k not in _IGNORED_KEYS and k not in _OUR_KEYS:
             raise NotImplementedError(f"metric type 'calculate_lpips': option {k!r} (have {sorted(_OUR_KEYS)})")
-    combined, vgg, lin = kw.get("lpips_weights"), kw.get("vgg16_path"), kw.get("lin_path")
-    if combined and (vgg or lin):
-        raise ValueError("metric type 'calculate_lpips': give lpips_weights (one combined file) or vgg16_path + lin_path, not both")
-    if bool(vgg) != bool(lin):
-        raise ValueError("metric type 'calculate_lpips': vgg16_path and lin_path go together (the backbone and the lpips package's linear layers)")
-    for key, path in (("lpips_weights", combined), ("vgg16_path", vgg), ("lin_path", lin)):
+    if kw.get(other):
+        raise ValueError(f"metric type 'calculate_lpips': {other} belongs to the other backbone: lpips_model={model!r} takes {bkey} + lin_path")
+    combined, backbone, lin = kw.get("lpips_weights"), kw.get(bkey), kw.get("lin_path")
+    if combined and (backbone or lin):
+        raise ValueError(f"metric type 'calculate_lpips': give lpips_weights (one combined file) or {bkey} + lin_path, not both")
+    if bool(backbone) != bool(lin):
+        raise ValueError(f"metric type 'calculate_lpips': {bkey} and lin_path go together (the backbone and the lpips package's linear layers)")
+    for key, path in (("lpips_weights", combined), (bkey, backbone), ("lin_path", lin)):
         if path and not os.path.exists(path):
             raise FileNotFoundError(f"metric type 'calculate_lpips': {key}={path!r} does not exist")
     if combined:
         return os.path.abspath(combined), None
-    if vgg:
-        return os.path.abspath(vgg), os.path.abspath(lin)
-    for cand in (os.environ.get("SSR_LPIPS_WEIGHTS"), LPIPS_PRETRAIN_PATH):
+    if backbone:
+        return os.path.abspath(backbone), os.path.abspath(lin)
+    for cand in (os.environ.get(env), default):
         if cand and os.path.exists(cand):
             return os.path.abspath(cand), None
     raise NotImplementedError(
-        "metric type 'calculate_lpips': no LPIPS weights found.  Put them in one of three places: the metric's options (`lpips_weights: "
-        "<file saved from lpips.LPIPS(net='vgg').state_dict()>`, or `vgg16_path: <torchvision vgg16-397923af.pth>` + `lin_path: <lpips "
-        f"weights/v0.1/vgg.pth>`), the environment variable SSR_LPIPS_WEIGHTS=<combined file>, or {LPIPS_PRETRAIN_PATH}.  "
+        "metric type 'calculate_lpips': no LPIPS weights found" + ("" if net == "vgg" else f" for lpips_model={model!r}") +
+        ".  Put them in one of three places: the metric's options (`lpips_weights: "
+        f"<file saved from lpips.LPIPS(net='{pkg}').state_dict()>`, or `{bkey}: <torchvision {tv_file}>` + `lin_path: <lpips "
+        f"weights/v0.1/{lin_file}>`), the environment variable {env}=<combined file>, or {default}.  "
         "There is no silent random network: a metric from random weights is not LPIPS")
 
 
 def calculate_lpips(img, img2, lpips_model="vgg", **kw) -> float:
     """One image pair per call (uint8 [1, H, W, 3] or [H, W, 3] RGB on the device), as the other entries of metrics.METRICS.
-    Keys: lpips_model ('vgg'); ours: lpips_weights | vgg16_path + lin_path, rgb (default false: the reference's BGR feed),
-    normalize (default false: the reference's [0, 1] feed).  rgb + normalize is what the lpips package documents for RGB images in
-    [0, 1].  The loaded weights and their plans are cached per resolved path."""
+    Keys: lpips_model ('vgg' | 'alexnet'); ours: lpips_weights | vgg16_path (alexnet_path) + lin_path, rgb (default false: the
+    reference's BGR feed), normalize (default false: the reference's [0, 1] feed).  rgb + normalize is what the lpips package documents
+    for RGB images in [0, 1].  The loaded weights and their plans are cached per backbone and resolved path."""
     paths = check_lpips_opt(lpips_model, **kw)
+    net = _net(lpips_model)
     a, b = (t if t.dim() == 4 else t[None] for t in (img, img2))
     if a.shape[0] != 1:
         raise ValueError("one image per call (the reference validates with batch size 1)")
-    key = paths + (a.device.index,)
+    key = (net,) + paths + (a.device.index,)
     if key not in _MODELS:
-        _MODELS[key] = LPIPSModel(load_lpips_state(*paths), a.device)
+        _MODELS[key] = LPIPSModel(load_lpips_state(*paths, net=net), a.device, net=net)
     d = lpips_distance(a.contiguous(), b.contiguous(), _MODELS[key], bgr=not kw.get("rgb", False), normalize=bool(kw.get("normalize", False)))
     return float(d[0])
