@@ -848,6 +848,63 @@ int ssr_obj_crop_resize_fwd(ssr_view src, int32_t dtype, int32_t B, int32_t H, i
 int ssr_obj_crop_resize_bwd(ssr_view g, const int32_t* boxes, const int32_t* first, int32_t Bo, ssr_view dimg, int32_t dtype,
                             int32_t B, int32_t H, int32_t W, float grad_scale, int32_t antialias, void* stream);
 
+/* ---- The vision tower of the CLIPScore validation metric (csrc/vit.hip; `calculate_clipscore`: SigLIP ViT-SO400M-14, CLIP ViT-B/16;
+ *      clipscore_metric.py; additive: the ABI version stays 3) ----
+ * Every tensor is an fp32 ROW view: row i, channel c of view v is ((float*)v.p)[i * v.cs + v.coff + c], so a buffer can be a channel
+ * slice of a wider one (q, k, v: three slices of one packed [rows, 3 C] buffer) or a strided row set (the class-token rows of a batch:
+ * cs = T * C).  16-byte aligned (p, cs % 4 == 0, coff % 4 == 0) unless said otherwise.  dtype is the storage code: SSR_F32 / SSR_F32X3
+ * (fp32); SSR_BF16: SSR_EUNSUP; any other code: SSR_EINVAL.  No float atomics and no split reductions: two launches give the same
+ * bytes, and an image's bytes depend neither on the batch size nor on its place in the batch.  A refused call launches nothing.
+ *
+ * ssr_linear: Y[M, Nout] = act(X[M, K] W[Nout, K]^T + bias) (+ R).  w is a contiguous row-major [Nout][K] device array (16-byte
+ *   aligned: what a state_dict's nn.Linear weight is; no packing step), bias Nout floats or NULL, r a view like y or a null view
+ *   (r.p == NULL).  act: SSR_VIT_ACT_NONE | _QUICK_GELU (v / (1 + expf(-1.702 v))) | _GELU_TANH (0.5 v (1 + tanhf(sqrt(2 / pi) (v +
+ *   0.044715 v^3)))) | _GELU_ERF (0.5 v (1 + erff(v / sqrt 2))), evaluated in fp32.  Arithmetic: v_mfma_f32_32x32x2_f32, per output ONE
+ *   fp32 accumulator chain over k ascending (pairs (0, 1), (2, 3), ..), then the bias, then the activation, then the residual last,
+ *   one fp32 rounding each.  Any M >= 1; K % 4 == 0 and Nout % 4 == 0 (SSR_EUNSUP otherwise, as M or Nout above 2^22); the tails of
+ *   all three dimensions are masked: nothing outside X[M, K], W[Nout, K], R and Y[M, Nout] is read or written.  r may alias y (each
+ *   element is read before it is written, by the same thread); x must not alias y.
+ *   SSR_EINVAL: a null x, y or w, a size <= 0, an unknown act, a view narrower than its channels or misaligned.
+ * ssr_layernorm_fwd: y[i, :] = (x[i, :] - mean_i) / sqrt(var_i + eps) * gamma + beta over C channels, biased variance; mean, then the
+ *   sum of squared deviations from it, then the affine map are all formed in fp64 and the result rounded to fp32 once (rows with a
+ *   large mean and a small variance lose nothing).  gamma, beta: C floats, 16-byte aligned.  y may alias x.
+ *   SSR_EUNSUP: C % 4 != 0 or C > 2048.  SSR_EINVAL: a null pointer, rows or C <= 0, eps < 0, a bad view.
+ * ssr_mha_fwd: y = softmax_j(q_i . k_j * scale) v per (image n, head h): q, y have N * Tq rows (row n * Tq + i), k, v N * Tk rows, and
+ *   head h is channels h * d .. h * d + d - 1 of each view.  Max-subtracted softmax in fp32 (expf), plain fp32 FMA, the keys taken 64 at
+ *   a time with a running maximum and sum, so any Tk works (K and V need not fit the LDS); Tq = 1 is the attention-pooling head.
+ *   SSR_EUNSUP: d % 8 != 0 or d > 128, N or heads > 65535, Tq or Tk > 2^20.  SSR_EINVAL: a size <= 0, a NaN scale, a bad view.
+ *   y must not alias q, k or v.
+ * ssr_vit_patch_input: uint8 images u [N][H][W][3] -> the patch matrix y [N * grid^2, 3 p^2], row n * grid^2 + gy * grid + gx, column
+ *   c * p^2 + py * p + px (the flattening of a patch-embedding weight [C, 3, p, p], so the embedding is ssr_linear):
+ *       v = (float)u[n][rowidx[gy p + py]][colidx[gx p + px]][perm[c]] / 255.0f;   if (mean) v = (v - mean[c]) / std[c];
+ *   every step rounded to fp32 (IEEE division; no fused multiply-add).  rowidx, colidx: DEVICE int32 [grid * p], the source row /
+ *   column of every row / column of the resized image: the caller builds them by running the resize it wants to match (F.interpolate,
+ *   mode 'nearest') over an index ramp, so the device restates no rounding rule.  An entry outside the image writes 0 and reads
+ *   nothing.  perm (3 ints in 0 .. 2; {2, 1, 0} feeds an RGB image as BGR), mean, std (3 floats each, both or neither; std != 0) are
+ *   host arrays copied into the launch.  y needs 3 p^2 channels.  SSR_EUNSUP: p > 64, grid > 1024.
+ * ssr_vit_tokens: x[n T + t, :] = (t < ncls ? cls : e[n G + t - ncls, :]) + pos[t, :] over C channels, ncls = (cls != NULL), T = G +
+ *   ncls; cls C floats or NULL, pos a contiguous [T][C] array; one fp32 addition.  C % 4 (SSR_EUNSUP otherwise).
+ * ssr_cosine_pairs: f holds 2 N rows of E channels (rows 0 .. N - 1: the first image of every pair, N .. 2 N - 1: the second; 4-byte
+ *   alignment is enough).  out[n] = dot / max(sqrt(na) * sqrt(nb), 1e-8) with dot, na, nb fp64 sums in index order of exact products:
+ *   torch.nn.functional.cosine_similarity as torch <= 1.11 computes it; later versions clamp each norm on its own, which differs only
+ *   for a norm below 1e-8 [recalled].  out: N doubles, 8-byte aligned. */
+#define SSR_VIT_ACT_NONE 0
+#define SSR_VIT_ACT_QUICK_GELU 1
+#define SSR_VIT_ACT_GELU_TANH 2
+#define SSR_VIT_ACT_GELU_ERF 3
+int ssr_linear(ssr_view x, const float* w, const float* bias, ssr_view r, ssr_view y, int32_t dtype, int32_t M, int32_t K,
+               int32_t Nout, int32_t act, void* stream);
+int ssr_layernorm_fwd(ssr_view x, const float* gamma, const float* beta, ssr_view y, int32_t dtype, int32_t rows, int32_t C,
+                      double eps, void* stream);
+int ssr_mha_fwd(ssr_view q, ssr_view k, ssr_view v, ssr_view y, int32_t dtype, int32_t N, int32_t Tq, int32_t Tk, int32_t heads,
+                int32_t d, float scale, void* stream);
+int ssr_vit_patch_input(const uint8_t* u, int32_t N, int32_t H, int32_t W, const int32_t* rowidx, const int32_t* colidx,
+                        int32_t grid, int32_t p, ssr_view y, int32_t dtype, const int32_t* perm, const float* mean,
+                        const float* std, void* stream);
+int ssr_vit_tokens(ssr_view e, const float* cls, const float* pos, ssr_view x, int32_t dtype, int32_t N, int32_t G, int32_t C,
+                   void* stream);
+int ssr_cosine_pairs(ssr_view f, int32_t dtype, int32_t N, int32_t E, double* out, void* stream);
+
 /* library / device info: writes "gfx950 CUs=256 ..." style text */
 int ssr_device_info(char* buf, int32_t buflen);
 int ssr_abi_version(void);

@@ -179,8 +179,10 @@ ABI_SYMBOLS = [
     "ssr_dropout_mask", "ssr_mse_l1_loss",
     "ssr_self_attention_fwd", "ssr_self_attention_bwd", "ssr_self_attention_save_floats", "ssr_self_attention_scratch_floats", "ssr_relu_bwd",
     "ssr_obj_crop_resize_fwd", "ssr_obj_crop_resize_bwd",
+    "ssr_linear", "ssr_layernorm_fwd", "ssr_mha_fwd", "ssr_vit_patch_input", "ssr_vit_tokens", "ssr_cosine_pairs",
     "ssr_device_info", "ssr_abi_version",
 ]
+VIT_ACTS = {"none": 0, "quick_gelu": 1, "gelu_tanh": 2, "gelu_erf": 3}      # SSR_VIT_ACT_*: `act` of ssr_linear (csrc/vit.hip)
 OBJ_CROP, OBJ_MAX_SIDE = 32, 128   # SSR_OBJ_CROP, SSR_OBJ_MAX_SIDE: side of a resized object crop, largest box side served (csrc/obj_crop.hip)
 SCAN_MAX_RANGES = 8           # SSR_SCAN_MAX_RANGES: ranges per ssr_nonfinite_scan call
 
@@ -291,6 +293,13 @@ def lib() -> C.CDLL:
     l.ssr_relu_bwd.argtypes = [View, View, View, i64, i32, vp]
     l.ssr_obj_crop_resize_fwd.argtypes = [View, i32, i32, i32, i32, vp, i32, View, i32, vp]
     l.ssr_obj_crop_resize_bwd.argtypes = [View, vp, vp, i32, View, i32, i32, i32, i32, f32, i32, vp]
+    l.ssr_linear.argtypes = [View, vp, vp, View, View, i32, i32, i32, i32, i32, vp]
+    l.ssr_layernorm_fwd.argtypes = [View, vp, vp, View, i32, i32, i32, C.c_double, vp]
+    l.ssr_mha_fwd.argtypes = [View, View, View, View, i32, i32, i32, i32, i32, i32, f32, vp]
+    l.ssr_vit_patch_input.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, View, i32, C.POINTER(i32), C.POINTER(C.c_float),
+                                      C.POINTER(C.c_float), vp]
+    l.ssr_vit_tokens.argtypes = [View, vp, vp, View, i32, i32, i32, i32, vp]
+    l.ssr_cosine_pairs.argtypes = [View, i32, i32, i32, vp, vp]
     l.ssr_device_info.argtypes = [C.c_char_p, i32]
     l.ssr_abi_version.argtypes = []
     for s in ABI_SYMBOLS:

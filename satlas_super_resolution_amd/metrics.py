@@ -1,6 +1,7 @@
 """Validation metrics of the shipped option files on the device (csrc/metrics.hip through the C ABI):
 psnr / ssim (basicsr.metrics, esrgan_s2naip_urban.yml:153-162) and cpsnr (/root/reference/ssr/metrics/cpsnr.py:8-59); lpips
-(/root/reference/ssr/metrics/lpips.py:7-21) is lpips_metric.py, registered in METRICS below.
+(/root/reference/ssr/metrics/lpips.py:7-21) is lpips_metric.py and clipscore (ssr/metrics/clipscore.py:9-38) is clipscore_metric.py, both
+registered in METRICS below.
 
 Images are uint8 [B, H, W, C] device tensors as `tensor2img_u8` produces them (BasicSR's tensor2img quantisation: clamp to
 [0, 1], * 255, round half to even; kept RGB — the three metrics are invariant to the channel order when test_y_channel is false)."""
@@ -117,12 +118,13 @@ def calculate_ssim(img, img2, crop_border, input_order="HWC", test_y_channel=Fal
 
 
 from .lpips_metric import calculate_lpips, check_lpips_opt  # noqa: E402  (ssr/metrics/lpips.py: VGG16 forward + csrc/lpips.hip)
+from .clipscore_metric import calculate_clipscore, check_clipscore_opt  # noqa: E402  (ssr/metrics/clipscore.py: ViT forward, csrc/vit.hip)
 
 METRICS = {"calculate_psnr": calculate_psnr, "calculate_ssim": calculate_ssim, "calculate_cpsnr": calculate_cpsnr,
-           "calculate_lpips": calculate_lpips}
+           "calculate_lpips": calculate_lpips, "calculate_clipscore": calculate_clipscore}
 # what a metric needs checked BEFORE the first image is processed (called with the entry's keys, without `type` / `better`):
-# calculate_lpips validates its keys and finds its weights file
-METRIC_CHECKS = {"calculate_lpips": check_lpips_opt}
+# calculate_lpips and calculate_clipscore validate their keys and find their weights files
+METRIC_CHECKS = {"calculate_lpips": check_lpips_opt, "calculate_clipscore": check_clipscore_opt}
 
 
 def imwrite_rgb(img_hwc_u8, path: str):
