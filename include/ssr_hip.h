@@ -905,6 +905,48 @@ int ssr_vit_tokens(ssr_view e, const float* cls, const float* pos, ssr_view x, i
                    void* stream);
 int ssr_cosine_pairs(ssr_view f, int32_t dtype, int32_t N, int32_t E, double* out, void* stream);
 
+/* ---- The tower's backward pass, for the CLIP loss of train.clip_opt (csrc/vit_bwd.hip; clip_loss.py; additive: the ABI version stays
+ *      3) ----  Row views, dtype codes and the determinism rule as above.  Only the gradient with respect to the IMAGE is formed: the
+ * linear data gradients dX = dY W are ssr_linear on a transposed weight copy, and there is no weight gradient.
+ *
+ * ssr_vit_float_input: as ssr_vit_patch_input for an fp32 NHWC image view img [N][H][W][img.cs] (4-byte aligned, any channel count >=
+ *   coff + 3), of which channels coff + perm[c] are read:  v = img[n][rowidx[..]][colidx[..]][perm[c]];  if (mean) v = (v - mean[c]) /
+ *   std[c].  There is no / 255: fed with (float)u / 255.0f (IEEE division) it gives ssr_vit_patch_input's bytes.  perm must be a
+ *   permutation of {0, 1, 2} (SSR_EINVAL otherwise).
+ * ssr_vit_float_input_bwd: its transpose in gather form.  rowrange [H][2], colrange [W][2] (DEVICE int32): the half-open range of
+ *   rows / columns of the resized image that read source row / column i (clip_loss.nearest_inverse_ranges; an empty range: nothing
+ *   reads it).  Ranges are clamped to 0 .. grid * p: rows and columns the patch matrix does not hold carry no gradient.  Per source
+ *   element (n, y, x, c): the fp64 sum of dpatch over its rows, then columns, ascending, divided by std[c] (std == NULL: by nothing),
+ *   rounded to fp32 once and ADDED to dimg[n][y][x][perm[c]] (one writer per element; other channels and prior content stay).
+ * ssr_layernorm_bwd: x is the forward's input; mean and rstd are recomputed from it in fp64 as ssr_layernorm_fwd forms them.  With
+ *   g = dy * gamma and xhat = (x - mean) rstd:  out = rstd (g - mean(g) - xhat mean(g xhat)) (+ r), formed in fp64 and rounded once;
+ *   the residual r (optional, r.p == NULL: none) is one fp32 addition.  out may alias dy or r.  SSR_EUNSUP: C % 4 or C > 2048.
+ * ssr_vit_act_fwd: post = act(pre), the very device function of ssr_linear's epilogue: ssr_linear with SSR_VIT_ACT_NONE followed by
+ *   this pass gives the bytes of ssr_linear with `act` (without a residual).  ssr_vit_act_bwd: dpre = dpost * act'(pre) in fp32.  rows
+ *   of C channels, C % 4 (SSR_EUNSUP otherwise); post may alias pre, dpre may alias dpost.
+ * ssr_mha_bwd: the backward of ssr_mha_fwd for head dims 64 and 72 (SSR_EUNSUP otherwise), any Tq and Tk (Tq = 1: the pooling head).
+ *   With S = q k^T scale, P = softmax(S), dP = dy v^T, delta_i = sum_j P_ij dP_ij, dS = P (dP - delta):  dv = P^T dy, dk = scale dS^T
+ *   q, dq = scale dS k.  The softmax statistics are recomputed here (the running maximum and sum of the forward, over the same key
+ *   tiles), nothing is taken from ssr_mha_fwd.  dq may be a null view (a query that is a parameter).  ws: ssr_mha_bwd_ws_floats(N, Tq,
+ *   heads) = 3 N heads Tq floats of scratch (maximum, 1 / sum, delta per query row), written by the first launch and read by the second.
+ *   dq comes from blocks that own 64 queries and walk the keys in order, dk and dv from blocks that own 64 keys and walk the queries
+ *   in order.  dq, dk, dv must not alias an input.  SSR_EINVAL: a size <= 0, a NaN scale, a null ws, a bad view.
+ * ssr_feature_l1: loss[0] += weight * mean|fx - fg| over B rows of E channels (4-byte aligned views), the sum of |fx - fg| formed in
+ *   fp64 in index order by one thread;  dfx (optional) = weight / (B E) * sign(fx - fg), sign(0) = 0.  flags: 0 or SSR_DETERMINISTIC; one
+ *   block and one writer either way, so the scalar lands in slot 0 of a slotted buffer.  B E <= 2^24 (SSR_EUNSUP beyond). */
+int ssr_vit_float_input(ssr_view img, int32_t N, int32_t H, int32_t W, const int32_t* rowidx, const int32_t* colidx, int32_t grid,
+                        int32_t p, ssr_view y, int32_t dtype, const int32_t* perm, const float* mean, const float* std, void* stream);
+int ssr_vit_float_input_bwd(ssr_view dpatch, int32_t N, int32_t H, int32_t W, const int32_t* rowrange, const int32_t* colrange,
+                            int32_t grid, int32_t p, ssr_view dimg, int32_t dtype, const int32_t* perm, const float* std, void* stream);
+int ssr_layernorm_bwd(ssr_view x, const float* gamma, ssr_view dy, ssr_view r, ssr_view out, int32_t dtype, int32_t rows, int32_t C,
+                      double eps, void* stream);
+int ssr_vit_act_fwd(ssr_view pre, ssr_view post, int32_t dtype, int32_t rows, int32_t C, int32_t act, void* stream);
+int ssr_vit_act_bwd(ssr_view pre, ssr_view dpost, ssr_view dpre, int32_t dtype, int32_t rows, int32_t C, int32_t act, void* stream);
+int64_t ssr_mha_bwd_ws_floats(int32_t N, int32_t Tq, int32_t heads);
+int ssr_mha_bwd(ssr_view q, ssr_view k, ssr_view v, ssr_view dy, ssr_view dq, ssr_view dk, ssr_view dv, float* ws, int32_t dtype,
+                int32_t N, int32_t Tq, int32_t Tk, int32_t heads, int32_t d, float scale, void* stream);
+int ssr_feature_l1(ssr_view fx, ssr_view fg, ssr_view dfx, int32_t B, int32_t E, float weight, float* loss, int32_t flags, void* stream);
+
 /* library / device info: writes "gfx950 CUs=256 ..." style text */
 int ssr_device_info(char* buf, int32_t buflen);
 int ssr_abi_version(void);

@@ -14,6 +14,7 @@
 // on the batch size nor on its place in the batch (ssr_linear's tile shape is chosen from M, but every output is the same chain
 // of MFMA steps over the same operands whatever the tile).
 #include "common.h"
+#include "vit_act.h"
 #include <math.h>
 
 namespace {
@@ -25,15 +26,7 @@ inline bool view_ok(const ssr_view& v, int c) {
 }
 
 // ---------------------------------------------------------------------------------------------- ssr_linear
-__device__ __forceinline__ float vit_act(float v, int act) {
-    switch (act) {
-        case SSR_VIT_ACT_QUICK_GELU: return v / (1.0f + expf(-1.702f * v));                         // x * sigmoid(1.702 x)
-        case SSR_VIT_ACT_GELU_TANH: return 0.5f * v * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v)));
-        case SSR_VIT_ACT_GELU_ERF: return 0.5f * v * (1.0f + erff(v * 0.7071067811865476f));
-        default: return v;
-    }
-}
-
+// vit_act: vit_act.h (shared with the activation pass of vit_bwd.hip)
 // Block: 256 threads = 2 x 2 waves, each wave TM x TN MFMA tiles of 32 x 32 -> a (64 TM) x (64 TN) tile of Y; K in steps of 16.
 // The MFMA's A operand is X (lane (i, g) supplies X[m = i][k = g]), its B operand W (W[n = i][k = g]), so a lane ends with column
 // n = lane & 31 and rows m = mfma32_row(r, g): the 32 lanes of a half wave store 128 contiguous bytes of one row of Y.

@@ -180,6 +180,8 @@ ABI_SYMBOLS = [
     "ssr_self_attention_fwd", "ssr_self_attention_bwd", "ssr_self_attention_save_floats", "ssr_self_attention_scratch_floats", "ssr_relu_bwd",
     "ssr_obj_crop_resize_fwd", "ssr_obj_crop_resize_bwd",
     "ssr_linear", "ssr_layernorm_fwd", "ssr_mha_fwd", "ssr_vit_patch_input", "ssr_vit_tokens", "ssr_cosine_pairs",
+    "ssr_vit_float_input", "ssr_vit_float_input_bwd", "ssr_layernorm_bwd", "ssr_vit_act_fwd", "ssr_vit_act_bwd", "ssr_mha_bwd_ws_floats",
+    "ssr_mha_bwd", "ssr_feature_l1",
     "ssr_device_info", "ssr_abi_version",
 ]
 VIT_ACTS = {"none": 0, "quick_gelu": 1, "gelu_tanh": 2, "gelu_erf": 3}      # SSR_VIT_ACT_*: `act` of ssr_linear (csrc/vit.hip)
@@ -300,11 +302,20 @@ def lib() -> C.CDLL:
                                       C.POINTER(C.c_float), vp]
     l.ssr_vit_tokens.argtypes = [View, vp, vp, View, i32, i32, i32, i32, vp]
     l.ssr_cosine_pairs.argtypes = [View, i32, i32, i32, vp, vp]
+    l.ssr_vit_float_input.argtypes = [View, i32, i32, i32, vp, vp, i32, i32, View, i32, C.POINTER(i32), C.POINTER(C.c_float),
+                                      C.POINTER(C.c_float), vp]
+    l.ssr_vit_float_input_bwd.argtypes = [View, i32, i32, i32, vp, vp, i32, i32, View, i32, C.POINTER(i32), C.POINTER(C.c_float), vp]
+    l.ssr_layernorm_bwd.argtypes = [View, vp, View, View, View, i32, i32, i32, C.c_double, vp]
+    l.ssr_vit_act_fwd.argtypes = [View, View, i32, i32, i32, i32, vp]
+    l.ssr_vit_act_bwd.argtypes = [View, View, View, i32, i32, i32, i32, vp]
+    l.ssr_mha_bwd_ws_floats.argtypes = [i32, i32, i32]
+    l.ssr_mha_bwd.argtypes = [View, View, View, View, View, View, View, vp, i32, i32, i32, i32, i32, i32, f32, vp]
+    l.ssr_feature_l1.argtypes = [View, View, View, i32, i32, f32, vp, i32, vp]
     l.ssr_device_info.argtypes = [C.c_char_p, i32]
     l.ssr_abi_version.argtypes = []
     for s in ABI_SYMBOLS:
         getattr(l, s).restype = i64 if s in ("ssr_conv2d_chain_state_bytes", "ssr_sr_tail_scratch_bytes", "ssr_self_attention_save_floats",
-                                              "ssr_self_attention_scratch_floats") else i32
+                                              "ssr_self_attention_scratch_floats", "ssr_mha_bwd_ws_floats") else i32
     _lib = l
     return l
 

@@ -54,6 +54,8 @@ def osm_config_from_opt(opt: dict) -> OSMObjConfig:
     if world > 1:
         raise NotImplementedError(f"OSMObjESRGANModel: world size {world} is not implemented (data-parallel training of this model); "
                                   "run it on one GPU")
+    if (opt.get("train") or {}).get("clip_opt"):
+        raise NotImplementedError("train.clip_opt: OSMObjESRGANModel does not run the CLIP loss (SSRESRGANModel does)")
     train_ds = (opt.get("datasets") or {}).get("train") or {}
     for k in ("osm_objs_path", "n_osm_objs"):
         if train_ds.get(k) is None:

@@ -8,10 +8,10 @@
 
 Same registry name and the same `opt` dictionary (YAML) keys.  Instead of autograd over ~41k ATen ops per
 step, optimize_parameters() replays the fused HIP-graph step of train_step.ESRGANTrainStep.
-Scope: BasicSR's pixel (L1 / MSE / Charbonnier) and GAN (vanilla / lsgan / wgan / wgan_softplus / hinge) losses (+ VGG19 perceptual: feature and Gram-style terms; + SSIM) losses, USM-sharpened ground truth,
+Scope: BasicSR's pixel (L1 / MSE / Charbonnier) and GAN (vanilla / lsgan / wgan / wgan_softplus / hinge) losses (+ VGG19 perceptual: feature and Gram-style terms; + SSIM; + the CLIP loss on ViT-B-16-SigLIP-256) losses, USM-sharpened ground truth,
 `feed_disc_lr` and `old_hr` discriminator inputs, BasicSR's optimizers (Adam / AdamW / SGD / RMSprop with their options) and
 schedulers (MultiStepRestartLR, CosineAnnealingRestartLR; optimizers.py).  Anything this path does not implement raises
-NotImplementedError naming the option (clip / ldl losses, Adamax / ASGD / Rprop, other schedulers) — nothing is silently ignored."""
+NotImplementedError naming the option (the ldl loss, other CLIP-loss towers, Adamax / ASGD / Rprop, other schedulers) — nothing is silently ignored."""
 from __future__ import annotations
 
 import math
@@ -78,7 +78,8 @@ def step_config_from_opt(opt: dict) -> StepConfig:
 
 
 def train_config_from_opt(opt: dict) -> StepConfig:
-    """step_config_from_opt plus `train.ssim_opt` (SSIMLoss: ssr/losses/basic_loss.py:50-60, built at ssr_esrgan_model.py:62-65) and
+    """step_config_from_opt plus `train.ssim_opt` (SSIMLoss: ssr/losses/basic_loss.py:50-60, built at ssr_esrgan_model.py:62-65),
+    `train.clip_opt` (CLIPLoss: clip_loss.check_clip_opt validates the block and finds the tower's weights; StepConfig.clip) and
     BasicSR's other pixel and GAN losses (`pixel_opt.type`: MSELoss, CharbonnierLoss; `gan_opt.gan_type`: lsgan, wgan, wgan_softplus,
     hinge - basicsr/losses/basic_loss.py, gan_loss.py): what SSRESRGANModel configures its step from.
 
@@ -108,6 +109,21 @@ def train_config_from_opt(opt: dict) -> StepConfig:
                 raise NotImplementedError(f"train.ssim_opt.{k}: SSIMLoss takes loss_weight only")
         del rest_train["ssim_opt"]
         ssim = {"loss_weight": float(so.get("loss_weight", 1.0))}
+    clip = None
+    co = train_opt.get("clip_opt")
+    if co:      # CLIPLoss (ssr/losses/basic_loss.py:19-48, built at ssr_esrgan_model.py:77-80): clip_loss.check_clip_opt names every refusal
+        from ..clip_loss import check_clip_opt
+        clip = check_clip_opt(co)
+        dtype = (opt.get("network_g") or {}).get("compute_dtype", opt.get("compute_dtype", "fp32h"))
+        if hip.dtype_code(dtype) == hip.BF16:
+            raise NotImplementedError("train.clip_opt with compute_dtype 'bf16': the tower reads fp32 images; use fp32, fp32x3, fp32f or fp32h")
+        world = int(os.environ.get("WORLD_SIZE", "1"))
+        if opt.get("dist", False):
+            world = int(opt.get("world_size", world))
+        if world > 1:
+            raise NotImplementedError(f"train.clip_opt with world size {world}: l_clip_sim is not part of the cross-rank reduction of the "
+                                      "logged scalars; run it on one GPU")
+        del rest_train["clip_opt"]
     pixel_type, pixel_eps = "L1Loss", 1e-12
     pix = train_opt.get("pixel_opt")
     if pix:
@@ -147,6 +163,7 @@ def train_config_from_opt(opt: dict) -> StepConfig:
     cfg = step_config_from_opt(rest)
     cfg.ssim, cfg.pixel_type, cfg.pixel_eps, cfg.gan_type = ssim, pixel_type, pixel_eps, gan_type
     cfg.optim_g, cfg.optim_d = specs["optim_g"], specs["optim_d"]
+    cfg.clip = clip
     return cfg
 
 

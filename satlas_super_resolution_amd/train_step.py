@@ -48,10 +48,13 @@ class StepConfig:
     optim_g: Optional[Dict] = None
     optim_d: Optional[Dict] = None
     deterministic: bool = False    # fixed-order reductions only: two runs give bit-identical parameters (engine.deterministic; SSR_DETERMINISTIC=1)
+    # train.clip_opt (CLIPLoss, ssr_esrgan_model.py:187-190; cliploss_esrgan_s2naip_urban.yml), as clip_loss.check_clip_opt returns it:
+    # {"model", "family", "path", "gelu", "loss_weight"}
+    clip: Optional[Dict] = None
 
 
 LOSS_KEYS = ("l_g_pix", "l_g_gan", "l_d_real", "out_d_real", "l_d_fake", "out_d_fake")
-N_LOSS = 9      # scalars of the loss arena: LOSS_KEYS, then 6 l_g_percep, 7 l_g_style, 8 l_g_ssim
+N_LOSS = 9      # scalars of the loss arena: LOSS_KEYS, then 6 l_g_percep, 7 l_g_style, 8 l_g_ssim (l_clip_sim: a buffer of its own)
 
 
 class AdamState:
@@ -112,7 +115,7 @@ class ESRGANTrainStep:
     def __init__(self, g_kwargs: Dict, d_kwargs: Dict, B: int, h: int, w: int, dtype="fp32",
                  cfg: StepConfig = StepConfig(), dp: Optional[DPContext] = None, use_graph: bool = True,
                  g_store: Optional[engine.ParamStore] = None, d_store: Optional[engine.ParamStore] = None,
-                 vgg_state: Optional[Dict[str, torch.Tensor]] = None):
+                 vgg_state: Optional[Dict[str, torch.Tensor]] = None, clip_state: Optional[Dict[str, torch.Tensor]] = None):
         assert g_kwargs.get("scale", 4) == 4, "the train step is defined for scale 4 (all shipped configs)"
         self.cfg, self.B, self.h, self.w = cfg, B, h, w
         self.mode = hip.dtype_code(dtype)          # arithmetic mode of the launch plans (hip.F32F: exact fp32 forward, split-bf16 backward)
@@ -195,6 +198,20 @@ class ESRGANTrainStep:
                                              loss_flags=self.loss_dt & hip.DETERMINISTIC,
                                              style_loss_ptr=self.losses.data_ptr() + 4 * 7 * self.loss_stride)   # l_g_style: slot 7
                 self.p_plan.pack()
+            self.c_plan = self.clip_loss = None
+            if cfg.clip:            # CLIP feature L1 (ssr_esrgan_model.py:187-190); its image gradient joins the L1 gradient buffer
+                from . import clip_loss as CL
+                if self.dt == hip.BF16:
+                    raise NotImplementedError("train.clip_opt with compute_dtype bf16: the tower reads fp32 images; use fp32, fp32x3, fp32f or fp32h")
+                if self.dp.active:
+                    raise NotImplementedError(f"train.clip_opt with world size {self.dp.world}: l_clip_sim is not part of the cross-rank "
+                                              "reduction of the logged scalars; run it on one GPU")
+                cmodel = CL.ClipLossModel(clip_state, dev, cfg.clip.get("gelu", "tanh")) if clip_state is not None else \
+                    CL.clip_loss_model(cfg.clip["path"], dev, cfg.clip.get("gelu", "tanh"))
+                self.clip_loss = torch.zeros(self.loss_stride, dtype=torch.float32, device=dev)      # the rule of the other loss scalars
+                self.c_plan = CL.ClipLossPlan(cmodel, B, H, W, view(self.fake_in), view(self.l1_tgt), view(self.grad_l1),
+                                              self.clip_loss.data_ptr(), float(cfg.clip.get("loss_weight", 1.0)),
+                                              self.loss_dt & hip.DETERMINISTIC)
             # SSR_NONFINITE_GUARD=0: the unguarded ssr_adam_step, as before the guard (same-call A/B timing; the reference applies a
             # non-finite update).  Otherwise each network's Adam skips a step whose gradient arena holds a NaN / Inf (AdamState).  It
             # runs inside update(), i.e. after every writer of the arena in every path, and under data parallelism after the
@@ -318,6 +335,9 @@ class ESRGANTrainStep:
             self.p_plan.fwd_target.run()
             self.p_plan.fwd.run()
             self.p_plan.bwd.run()
+        if self.c_plan is not None:                                        # :187-190, cri_clip(self.output, l1_gt)
+            self._zero(self.clip_loss)
+            self.c_plan.launcher.run()
         self._d_forward(self.fake_in)                                      # :181
         self._bce(True, cfg.gan_weight, 1, None, is_disc=False)            # :182
         self.d_plan.backward_plan(self.fake_in, param_grads=False, input_grad=True,
@@ -328,6 +348,8 @@ class ESRGANTrainStep:
     def _phase_g_skipped(self):
         """current_iter fails the gate at :144: only the forward runs (self.output is still needed)."""
         self._zero(self.losses)
+        if self.clip_loss is not None:
+            self._zero(self.clip_loss)
         self.g_store.pack()
         self.g_plan.fwd.run()
 
@@ -509,6 +531,9 @@ class ESRGANTrainStep:
         scal = self.losses if not self.det else self.losses.view(N_LOSS, self.loss_stride).double().cpu().sum(1).float().to(self.losses.device)
         vals = self.dp.reduce_scalars(scal).tolist()      # det: the per-block slots added in index order on the host
         out = OrderedDict((k, vals[i]) for i, k in enumerate(LOSS_KEYS))
+        if self.c_plan is not None:                            # logged right after l_g_gan (ssr_esrgan_model.py:187-190)
+            clip = float(self.clip_loss.double().cpu().sum())  # det: the slots added in index order on the host (slot 0 holds it all)
+            out = OrderedDict((k, v) for key, val in out.items() for k, v in (((key, val), ("l_clip_sim", clip)) if key == "l_g_gan" else ((key, val),)))
         if self.p_plan is not None and self.p_plan.feature:
             out["l_g_percep"] = vals[6]
         if self.p_plan is not None and self.p_plan.style:      # ssr_esrgan_model.py:157-160
