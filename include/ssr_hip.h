@@ -947,6 +947,33 @@ int ssr_mha_bwd(ssr_view q, ssr_view k, ssr_view v, ssr_view dy, ssr_view dq, ss
                 int32_t N, int32_t Tq, int32_t Tk, int32_t heads, int32_t d, float scale, void* stream);
 int ssr_feature_l1(ssr_view fx, ssr_view fg, ssr_view dfx, int32_t B, int32_t E, float weight, float* loss, int32_t flags, void* stream);
 
+/* ---- The tower linears on split operands (csrc/linear_split.hip; `tower_arithmetic: split` of train.clip_opt and of
+ *      calculate_clipscore; additive: the ABI version stays 3) ----
+ * ssr_linear_split: ssr_linear's product, Y[M, Nout] = act(X[M, K] W[Nout, K]^T + bias) (+ R), with the same views, epilogue order
+ *   (bias, activation, residual last, one fp32 rounding each), shape rules (any M >= 1, K % 4 == 0, Nout % 4 == 0, M and Nout up to
+ *   2^22, all three tails masked) and aliasing rules.  Only the contraction differs: every fp32 operand is two 16-bit pieces, hi =
+ *   round16(v) and lo = round16(v - hi), and per group of 16 consecutive k the fp32 accumulator receives x_hi w_hi, then x_hi w_lo, then
+ *   x_lo w_hi (v_mfma_f32_32x32x16_f16 / _bf16; x_lo w_lo is dropped), groups ascending: one fixed chain per output, no atomics, no
+ *   split-K, so two launches give the same bytes and a row's bytes depend neither on M nor on the row's place.
+ *   pieces = SSR_SPLIT_F16 (the forward): fp16 pieces, W multiplied by 2^SSR_F32H_WSHIFT before its split and the accumulator by
+ *     2^-SSR_F32H_WSHIFT before the bias (the convolutions' SSR_F32H convention).  Domain |x| < 65504, |w| < 64: beyond it a piece is
+ *     infinite and the output not finite.  Error against the exact product <= 2^-20 sum|x w| + 2^-25 sum|w| + 2^-35 sum|x|.
+ *   pieces = SSR_SPLIT_BF16 (the data gradient dX = dY W, whose values of 1e-8 .. 1e-4 lie below fp16's range): bf16 pieces, no scale.
+ *     Error <= 2^-16 sum|x w|.
+ *   wpk: the packed weight, ssr_linear_split_pack_bytes(Nout, K) = 32 Nout ceil(K / 8) bytes, 16-byte aligned, written once by
+ *   ssr_linear_split_pack from a contiguous row-major [Nout][K] fp32 device array with the SAME `pieces`:
+ *       entry [n][kg], kg < ceil(K / 8), row-major, 32 bytes = [ 8 hi pieces of W[n][8 kg .. 8 kg + 7] | their 8 lo pieces ]
+ *   (k >= K inside the last entry: zeros): each 16-byte half is one lane's MFMA operand, so the kernel stages entries into LDS as
+ *   they are; X is split while it is staged.  Two packs of one matrix give the same bytes.
+ *   SSR_EINVAL: a null x, y, w, wpk or out, a size <= 0, an unknown act or pieces, a view narrower than its channels or misaligned.
+ *   SSR_EUNSUP: K % 4, Nout % 4, M or Nout above 2^22.  A refused call launches nothing. */
+#define SSR_SPLIT_F16 1
+#define SSR_SPLIT_BF16 2
+int64_t ssr_linear_split_pack_bytes(int32_t Nout, int32_t K);
+int ssr_linear_split_pack(const float* w, int32_t Nout, int32_t K, int32_t pieces, void* out, void* stream);
+int ssr_linear_split(ssr_view x, const void* wpk, const float* bias, ssr_view r, ssr_view y, int32_t pieces, int32_t M, int32_t K,
+                     int32_t Nout, int32_t act, void* stream);
+
 /* library / device info: writes "gfx950 CUs=256 ..." style text */
 int ssr_device_info(char* buf, int32_t buflen);
 int ssr_abi_version(void);

@@ -18,6 +18,10 @@ refused by name.  Statements that rest on open_clip behaviour that cannot be exe
     clip_loss_grad_reference   the same loss and its image gradient in closed form, piece by piece as the kernels compute it
     check_clip_opt             the keys of a `train.clip_opt` block and its weights file (no device)
     ClipLossModel / ClipLossPlan     the weights (and their transposes) on the device / the static launch lists (csrc/vit_bwd.hip)
+
+`tower_arithmetic` ('exact', the default | 'split'; linear_split.py): under 'split' every matrix product of the tower runs as
+ssr_linear_split (csrc/linear_split.hip) - fp16 pieces in both forward passes, bf16 pieces in the backward's transposes - and
+clip_loss_grad_reference restates that on the CPU.
 """
 from __future__ import annotations
 
@@ -28,6 +32,7 @@ import torch
 import torch.nn.functional as F
 
 from .clipscore_metric import CLIP_MEAN, CLIP_STD, _GELUS, _attention, _flat_keys, nearest_index_table, vit_config_from_state, vit_features_from_input
+from .linear_split import check_split_domain, check_tower_arithmetic, linear_split_reference, pack_tower  # noqa: F401  (linear_split_reference: re-exported)
 
 CLIP_LOSS_MODELS = {"ViT-B-16-SigLIP-256": "siglip"}                                 # the reference's clip_loss_model -> family
 CLIP_LOSS_MEAN, CLIP_LOSS_STD = CLIP_MEAN["clip"], CLIP_STD["clip"]                    # OpenAI's, whatever the tower
@@ -110,24 +115,28 @@ def _attention_bwd(q, k, v, dy, heads: int):
 
 
 def clip_loss_grad_reference(fake: torch.Tensor, gt: torch.Tensor, state: Dict[str, torch.Tensor], loss_weight: float = 1.0,
-                             gelu: str = "tanh", dtype=torch.float64) -> Tuple[torch.Tensor, torch.Tensor]:
+                             gelu: str = "tanh", dtype=torch.float64, tower_arithmetic: str = "exact") -> Tuple[torch.Tensor, torch.Tensor]:
     """-> (l_clip_sim, d l_clip_sim / d fake [N, 3, H, W]) without autograd: LayerNorm backward, softmax-attention backward, the
     activation derivative, the linear transposes, the pooling head with Tq = 1, and the transposed resize as a gather over the
-    inverse index ranges - the pieces, and their order, of ClipLossPlan's backward."""
+    inverse index ranges - the pieces, and their order, of ClipLossPlan's backward.  tower_arithmetic 'split': every forward product
+    (of both images) is linear_split_reference with fp16 pieces, every transpose with bf16 pieces, as ClipLossPlan launches them."""
+    split = check_tower_arithmetic(tower_arithmetic, "tower_arithmetic") == "split"
+    mm = (lambda t, w, b=None: linear_split_reference(t, w, b, "f16").to(dtype)) if split else F.linear                 # noqa: E731
+    mt = (lambda dy, w: linear_split_reference(dy, w.t(), None, "bf16").to(dtype)) if split else (lambda dy, w: dy @ w)   # noqa: E731
     cfg = vit_config_from_state(state)
     if cfg["family"] != "siglip":
         raise NotImplementedError("train.clip_opt: the backward of a `clip` tower (class token) is not built: no clip_loss_model needs it")
     heads, eps, Cw, p, g, S = cfg["heads"], cfg["ln_eps"], cfg["width"], cfg["patch"], cfg["grid"], cfg["image_size"]
     Wt = lambda k: state[k].to(dtype)                                          # noqa: E731
-    lin = lambda t, name: F.linear(t, Wt(f"{name}.weight"), Wt(f"{name}.bias"))  # noqa: E731
+    lin = lambda t, name: mm(t, Wt(f"{name}.weight"), Wt(f"{name}.bias"))       # noqa: E731
     ln = lambda t, name: F.layer_norm(t, (Cw,), Wt(f"{name}.weight"), Wt(f"{name}.bias"), eps)       # noqa: E731
     act = lambda t: F.gelu(t, approximate="tanh" if gelu == "tanh" else "none")  # noqa: E731
     with torch.no_grad():
-        fg = vit_features_from_input(clip_loss_input(gt, S, dtype), state, gelu)
+        fg = vit_features_from_input(clip_loss_input(gt, S, dtype), state, gelu, tower_arithmetic)
         N, _, H, W = fake.shape
         xin = clip_loss_input(fake, S, dtype)[:, :, :g * p, :g * p]
         patches = xin.reshape(N, 3, g, p, g, p).permute(0, 2, 4, 1, 3, 5).reshape(N, g * g, 3 * p * p)
-        x = F.linear(patches, Wt("patch.weight").reshape(Cw, -1), Wt("patch.bias")) + Wt("pos")
+        x = mm(patches, Wt("patch.weight").reshape(Cw, -1), Wt("patch.bias")) + Wt("pos")
         saved = []
         for i in range(cfg["depth"]):
             b = f"blocks.{i}"
@@ -146,19 +155,19 @@ def clip_loss_grad_reference(fake: torch.Tensor, gt: torch.Tensor, state: Dict[s
         loss = loss_weight * diff.abs().mean()
         # backward
         df = (loss_weight / diff.numel() * torch.sign(diff))[:, None]                                   # [N, 1, C]
-        dpre = df @ Wt("pool.fc2.weight") * _act_grad(ppre, gelu)
-        dpy = _ln_bwd(py, Wt("pool.ln.weight"), dpre @ Wt("pool.fc1.weight"), eps) + df
-        _, dk, dv = _attention_bwd(pq, pk, pv, dpy @ Wt("pool.proj.weight"), heads)                    # the probe is a parameter: no dq
-        dx = _ln_bwd(x, Wt("ln_post.weight"), torch.cat([dk, dv], dim=-1) @ Wt("pool.kv.weight"), eps)
+        dpre = mt(df, Wt("pool.fc2.weight")) * _act_grad(ppre, gelu)
+        dpy = _ln_bwd(py, Wt("pool.ln.weight"), mt(dpre, Wt("pool.fc1.weight")), eps) + df
+        _, dk, dv = _attention_bwd(pq, pk, pv, mt(dpy, Wt("pool.proj.weight")), heads)                    # the probe is a parameter: no dq
+        dx = _ln_bwd(x, Wt("ln_post.weight"), mt(torch.cat([dk, dv], dim=-1), Wt("pool.kv.weight")), eps)
         for i in reversed(range(cfg["depth"])):
             b = f"blocks.{i}"
             x_in, qkv, x_mid, pre = saved[i]
-            dpre = dx @ Wt(f"{b}.fc2.weight") * _act_grad(pre, gelu)
-            dx_mid = _ln_bwd(x_mid, Wt(f"{b}.ln2.weight"), dpre @ Wt(f"{b}.fc1.weight"), eps) + dx
+            dpre = mt(dx, Wt(f"{b}.fc2.weight")) * _act_grad(pre, gelu)
+            dx_mid = _ln_bwd(x_mid, Wt(f"{b}.ln2.weight"), mt(dpre, Wt(f"{b}.fc1.weight")), eps) + dx
             q, k, v = qkv.chunk(3, dim=-1)
-            dqkv = torch.cat(_attention_bwd(q, k, v, dx_mid @ Wt(f"{b}.proj.weight"), heads), dim=-1)
-            dx = _ln_bwd(x_in, Wt(f"{b}.ln1.weight"), dqkv @ Wt(f"{b}.qkv.weight"), eps) + dx_mid
-        dpatch = dx @ Wt("patch.weight").reshape(Cw, -1)                                               # [N, G, 3 p p]
+            dqkv = torch.cat(_attention_bwd(q, k, v, mt(dx_mid, Wt(f"{b}.proj.weight")), heads), dim=-1)
+            dx = _ln_bwd(x_in, Wt(f"{b}.ln1.weight"), mt(dqkv, Wt(f"{b}.qkv.weight")), eps) + dx_mid
+        dpatch = mt(dx, Wt("patch.weight").reshape(Cw, -1))                                              # [N, G, 3 p p]
         dxin = dpatch.reshape(N, g, g, 3, p, p).permute(0, 3, 1, 4, 2, 5).reshape(N, 3, g * p, g * p)
         # the transposed resize: every source pixel gathers the destinations of its row range x column range (prefix sums)
         rr, cr = nearest_inverse_ranges(H, S, g * p), nearest_inverse_ranges(W, S, g * p)
@@ -174,13 +183,14 @@ CLIP_LOSS_REFUSED = {"EVA02-E-14-plus": "4.4 B parameters", "RN50": "a ResNet, n
 CLIP_LOSS_ENV = "SSR_CLIP_LOSS_SIGLIP_B16_WEIGHTS"
 CLIP_LOSS_PRETRAIN_PATH = "experiments/pretrained_models/clip_siglip_b16_256.pth"
 _SAVE_HINT = "torch.save(open_clip.create_model_and_transforms('ViT-B-16-SigLIP-256', pretrained='webli')[0].visual.state_dict(), <file>)"
-_CLIP_OPT_KEYS = ("type", "clip_loss_model", "loss_weight", "clip_weights", "gelu")
+_CLIP_OPT_KEYS = ("type", "clip_loss_model", "loss_weight", "clip_weights", "gelu", "tower_arithmetic")
 
 
 def check_clip_opt(block: Dict) -> Dict:
     """Validates a `train.clip_opt` block and finds the weights -> {"model", "family", "path", "gelu", "loss_weight"}.  Touches no
     device.  Keys: type (CLIPLoss), clip_loss_model (ViT-B-16-SigLIP-256), loss_weight (default 1.0, as CLIPLoss.__init__); ours:
-    clip_weights (a file), gelu ('tanh' | 'erf', default 'tanh' as the CLIPScore metric).  The weights file is the option
+    clip_weights (a file), gelu ('tanh' | 'erf', default 'tanh' as the CLIPScore metric), tower_arithmetic ('exact', the default and
+    what an absent key means: the result carries no such entry | 'split': "tower_arithmetic": "split").  The weights file is the option
     `clip_weights`, else the environment variable SSR_CLIP_LOSS_SIGLIP_B16_WEIGHTS, else the default path; anything else raises
     NotImplementedError beginning `train.clip_opt`."""
     import os
@@ -200,6 +210,8 @@ def check_clip_opt(block: Dict) -> Dict:
     if gelu not in _GELUS:
         raise NotImplementedError(f"train.clip_opt.gelu={gelu!r} (have {list(_GELUS)})")
     out = {"model": name, "family": CLIP_LOSS_MODELS[name], "gelu": gelu, "loss_weight": float(block.get("loss_weight", 1.0))}
+    if check_tower_arithmetic(block.get("tower_arithmetic"), "train.clip_opt.tower_arithmetic") == "split":
+        out["tower_arithmetic"] = "split"
     given = block.get("clip_weights")
     if given:
         if not os.path.exists(given):
@@ -218,13 +230,13 @@ def check_clip_opt(block: Dict) -> Dict:
 _LOSS_MODELS: Dict[Tuple, "ClipLossModel"] = {}
 
 
-def clip_loss_model(path: str, device, gelu: str = "tanh") -> "ClipLossModel":
-    """the tower of a weights file on the device, loaded once per (resolved path, device, gelu)"""
+def clip_loss_model(path: str, device, gelu: str = "tanh", tower_arithmetic: str = "exact") -> "ClipLossModel":
+    """the tower of a weights file on the device, loaded once per (resolved path, device, gelu, tower_arithmetic)"""
     from .clipscore_metric import load_clip_visual_state
     device = torch.device(device)
-    key = (path, device.type, device.index, gelu)
+    key = (path, device.type, device.index, gelu, tower_arithmetic)
     if key not in _LOSS_MODELS:
-        _LOSS_MODELS[key] = ClipLossModel(load_clip_visual_state(path, "siglip"), device, gelu)
+        _LOSS_MODELS[key] = ClipLossModel(load_clip_visual_state(path, "siglip"), device, gelu, tower_arithmetic)
     return _LOSS_MODELS[key]
 
 
@@ -233,12 +245,16 @@ _T_LEAVES = ("qkv", "proj", "fc1", "fc2")
 
 class ClipLossModel:
     """The tower's weights on the device, fp32, as CLIPVisualModel holds them, plus one transposed copy `<name>.weight.t` of every
-    matrix the backward passes through (dX = dY W is ssr_linear on W^T's rows): made once at load, + 0.34 GB for ViT-B."""
+    matrix the backward passes through (dX = dY W is ssr_linear on W^T's rows): made once at load, + 0.34 GB for ViT-B.
+    tower_arithmetic 'split': instead of both fp32 copies, every matrix is held as `<name>.weight.pk`, the packed fp16 pieces of W
+    (forward), and `<name>.weight.t.pk`, the packed bf16 pieces of W^T (backward), for ssr_linear_split; a matrix with max|w| >= 64
+    raises ValueError by name, on the host, before anything is loaded."""
 
-    def __init__(self, state: Dict[str, torch.Tensor], device="cuda", gelu: str = "tanh"):
+    def __init__(self, state: Dict[str, torch.Tensor], device="cuda", gelu: str = "tanh", tower_arithmetic: str = "exact"):
         from . import hip
         if gelu not in _GELUS:
             raise NotImplementedError(f"train.clip_opt: gelu={gelu!r} (have {list(_GELUS)})")
+        self.tower_arithmetic = check_tower_arithmetic(tower_arithmetic, "train.clip_opt.tower_arithmetic")
         self.cfg = vit_config_from_state(state)
         if self.cfg["family"] != "siglip":
             raise NotImplementedError("train.clip_opt: the backward of a `clip` tower (class token) is not built: no clip_loss_model needs it")
@@ -246,12 +262,19 @@ class ClipLossModel:
         for k in _flat_keys("siglip", self.cfg["depth"]):
             if k not in state:
                 raise KeyError(k)
-        self.w = {k: v.detach().to(torch.float32).contiguous().to(self.device) for k, v in state.items() if k not in ("heads", "image_size")}
-        self.w["patch.weight"] = self.w["patch.weight"].reshape(self.cfg["width"], -1)
         names = ["patch"] + [f"blocks.{i}.{leaf}" for i in range(self.cfg["depth"]) for leaf in _T_LEAVES] + \
                 [f"pool.{leaf}" for leaf in ("kv", "proj", "fc1", "fc2")]
-        for n in names:
-            self.w[f"{n}.weight.t"] = self.w[f"{n}.weight"].t().contiguous()
+        if self.tower_arithmetic == "split":
+            check_split_domain([(f"{n}.weight", state[f"{n}.weight"]) for n in names + ["pool.q"]], "train.clip_opt")
+        self.w = {k: v.detach().to(torch.float32).contiguous().to(self.device) for k, v in state.items() if k not in ("heads", "image_size")}
+        self.w["patch.weight"] = self.w["patch.weight"].reshape(self.cfg["width"], -1)
+        if self.tower_arithmetic == "split":
+            pack_tower(self.w, [f"{n}.weight" for n in names + ["pool.q"]], [f"{n}.weight" for n in names])
+            for n in names + ["pool.q"]:
+                del self.w[f"{n}.weight"]
+        else:
+            for n in names:
+                self.w[f"{n}.weight.t"] = self.w[f"{n}.weight"].t().contiguous()
         self.act = hip.VIT_ACTS[f"gelu_{gelu}"]
 
 
@@ -307,12 +330,22 @@ class ClipLossPlan:
         scale, eps, act = float(d) ** -0.5, cfg["ln_eps"], model.act
         F32 = hip.F32
 
+        use_split = model.tower_arithmetic == "split"  # ssr_linear_split: fp16 pieces forward (both passes), bf16 pieces backward
+
         def linear(L, xv, name, yv, rows, K, Nout, res=NULL_VIEW):
-            L.add(lib.ssr_linear, xv, ptr(f"{name}.weight"), ptr(f"{name}.bias"), res, yv, F32, rows, K, Nout, 0, what=f"linear {name}")
+            if use_split:
+                L.add(lib.ssr_linear_split, xv, ptr(f"{name}.weight.pk"), ptr(f"{name}.bias"), res, yv, hip.SPLIT_F16, rows, K, Nout, 0,
+                      what=f"linear {name}")
+            else:
+                L.add(lib.ssr_linear, xv, ptr(f"{name}.weight"), ptr(f"{name}.bias"), res, yv, F32, rows, K, Nout, 0, what=f"linear {name}")
 
         def linear_t(L, dyv, name, dxv, rows, K, Nout):
             """dX [rows, Nout] = dY [rows, K] W, W = `name`.weight [K, Nout]"""
-            L.add(lib.ssr_linear, dyv, ptr(f"{name}.weight.t"), None, NULL_VIEW, dxv, F32, rows, K, Nout, 0, what=f"linear^T {name}")
+            if use_split:
+                L.add(lib.ssr_linear_split, dyv, ptr(f"{name}.weight.t.pk"), None, NULL_VIEW, dxv, hip.SPLIT_BF16, rows, K, Nout, 0,
+                      what=f"linear^T {name}")
+            else:
+                L.add(lib.ssr_linear, dyv, ptr(f"{name}.weight.t"), None, NULL_VIEW, dxv, F32, rows, K, Nout, 0, what=f"linear^T {name}")
 
         def layernorm(L, xv, name, yv, rows):
             L.add(lib.ssr_layernorm_fwd, xv, ptr(f"{name}.weight"), ptr(f"{name}.bias"), yv, F32, rows, Cw, eps, what=f"layernorm {name}")

@@ -62,6 +62,8 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn.functional as F
 
+from .linear_split import check_split_domain, check_tower_arithmetic, linear_split_reference, pack_tower
+
 CLIP_MODELS = {"siglip-ViT-SO400M-14": "siglip", "clip-ViT-B/16": "clip"}          # the reference's names -> family
 CLIP_REFUSED = ("clipa-ViT-bigG-14",)                                                # the reference's third branch: 1.8 B parameters
 CLIP_IMG_SIZE = {"siglip": 384, "clip": 224}
@@ -73,7 +75,7 @@ CLIP_STD = {"siglip": (0.5, 0.5, 0.5), "clip": (0.26862954, 0.26130258, 0.275777
 LN_EPS = {"siglip": 1e-6, "clip": 1e-5}
 COS_EPS = 1e-8
 _IGNORED_KEYS = ("crop_border", "test_y_channel", "input_order", "better", "type")
-_OUR_KEYS = ("clip_weights", "rgb", "normalize", "gelu")
+_OUR_KEYS = ("clip_weights", "rgb", "normalize", "gelu", "tower_arithmetic")
 _GELUS = ("tanh", "erf")
 _BLOCK_LEAVES = ("ln1", "qkv", "proj", "ln2", "fc1", "fc2")
 _POOL_LEAVES = ("q", "kv", "proj", "ln", "fc1", "fc2")
@@ -365,14 +367,23 @@ def _attention(q, k, v, heads: int):
     return a.transpose(1, 2).reshape(n, tq, c)
 
 
-def vit_features_from_input(x: torch.Tensor, state: Dict[str, torch.Tensor], gelu: str = "tanh") -> torch.Tensor:
-    """the tower on an NCHW input in the input's dtype -> [N, out_dim]"""
+def vit_features_from_input(x: torch.Tensor, state: Dict[str, torch.Tensor], gelu: str = "tanh", tower_arithmetic: str = "exact") -> torch.Tensor:
+    """the tower on an NCHW input in the input's dtype -> [N, out_dim].  tower_arithmetic 'split': every matrix product is
+    linear_split.linear_split_reference with fp16 pieces (the patch embedding as a product over the patch matrix)."""
     cfg = vit_config_from_state(state)
     fam, heads, eps, dt = cfg["family"], cfg["heads"], cfg["ln_eps"], x.dtype
     W = lambda k: state[k].to(dt)                                              # noqa: E731
-    lin = lambda t, name: F.linear(t, W(f"{name}.weight"), W(f"{name}.bias"))  # noqa: E731
+    mm = F.linear
+    if check_tower_arithmetic(tower_arithmetic, "tower_arithmetic") == "split":
+        mm = lambda t, w, b=None: linear_split_reference(t, w, b, "f16").to(dt)  # noqa: E731
+    lin = lambda t, name: mm(t, W(f"{name}.weight"), W(f"{name}.bias"))        # noqa: E731
     ln = lambda t, name: F.layer_norm(t, (cfg["width"],), W(f"{name}.weight"), W(f"{name}.bias"), eps)       # noqa: E731
-    x = F.conv2d(x, W("patch.weight"), W("patch.bias") if fam == "siglip" else None, stride=cfg["patch"]).flatten(2).transpose(1, 2)
+    if mm is F.linear:
+        x = F.conv2d(x, W("patch.weight"), W("patch.bias") if fam == "siglip" else None, stride=cfg["patch"]).flatten(2).transpose(1, 2)
+    else:
+        n, p, g = x.shape[0], cfg["patch"], cfg["grid"]
+        patches = x[:, :, :g * p, :g * p].reshape(n, 3, g, p, g, p).permute(0, 2, 4, 1, 3, 5).reshape(n, g * g, 3 * p * p)
+        x = mm(patches, W("patch.weight").reshape(cfg["width"], -1), W("patch.bias") if fam == "siglip" else None)
     if fam == "clip":
         x = torch.cat([W("cls").expand(x.shape[0], 1, -1), x], dim=1)
     x = x + W("pos")
@@ -384,7 +395,7 @@ def vit_features_from_input(x: torch.Tensor, state: Dict[str, torch.Tensor], gel
         x = x + lin(_attention(q, k, v, heads), f"{b}.proj")
         x = x + lin(_act(lin(ln(x, f"{b}.ln2"), f"{b}.fc1"), fam, gelu), f"{b}.fc2")
     if fam == "clip":
-        return ln(x[:, 0], "ln_post") @ W("proj")
+        return ln(x[:, 0], "ln_post") @ W("proj") if mm is F.linear else mm(ln(x[:, 0], "ln_post"), W("proj").t())
     x = ln(x, "ln_post")
     q = lin(W("pool.probe").expand(x.shape[0], 1, -1), "pool.q")
     k, v = lin(x, "pool.kv").chunk(2, dim=-1)
@@ -394,11 +405,12 @@ def vit_features_from_input(x: torch.Tensor, state: Dict[str, torch.Tensor], gel
 
 
 def clip_image_features_reference(state: Dict[str, torch.Tensor], images_u8, bgr: bool = True, normalize: bool = False, gelu: str = "tanh",
-                                  dtype=torch.float64) -> torch.Tensor:
+                                  dtype=torch.float64, tower_arithmetic: str = "exact") -> torch.Tensor:
     """model.encode_image of uint8 [N, H, W, 3] RGB images as the reference feeds them (module docstring) -> [N, out_dim]"""
     cfg = vit_config_from_state(state)
     with torch.no_grad():
-        return vit_features_from_input(clip_resized_input(images_u8, cfg["image_size"], cfg["family"], bgr, normalize, dtype), state, gelu)
+        return vit_features_from_input(clip_resized_input(images_u8, cfg["image_size"], cfg["family"], bgr, normalize, dtype), state, gelu,
+                                       tower_arithmetic)
 
 
 def cosine_pairs_reference(fa: torch.Tensor, fb: torch.Tensor) -> torch.Tensor:
@@ -416,21 +428,33 @@ def clipscore_reference(a_u8, b_u8, state: Dict[str, torch.Tensor], bgr: bool = 
 # ---------------------------------------------------------------- the device path
 class CLIPVisualModel:
     """The weights of one tower on the device (fp32, the matrices as the state_dict holds them: ssr_linear reads [Nout][K] rows) and
-    the plans that use them, cached per (B, H, W, bgr, normalize)."""
+    the plans that use them, cached per (B, H, W, bgr, normalize).  tower_arithmetic 'split': every matrix is held as the packed fp16
+    pieces of ssr_linear_split instead (`<key>.pk`; a matrix with max|w| >= 64 raises ValueError by name before anything is loaded)."""
 
-    def __init__(self, state: Dict[str, torch.Tensor], device="cuda", gelu: str = "tanh"):
+    def __init__(self, state: Dict[str, torch.Tensor], device="cuda", gelu: str = "tanh", tower_arithmetic: str = "exact"):
         from . import hip
         if gelu not in _GELUS:
             raise NotImplementedError(f"gelu={gelu!r} (have {list(_GELUS)})")
+        self.tower_arithmetic = check_tower_arithmetic(tower_arithmetic, "metric type 'calculate_clipscore': tower_arithmetic")
         self.cfg = vit_config_from_state(state)
         self.device, self.gelu = torch.device(device), gelu
         for k in _flat_keys(self.cfg["family"], self.cfg["depth"]):
             if k not in state:
                 raise KeyError(k)
+        mats = [k for k in _flat_keys(self.cfg["family"], self.cfg["depth"])
+                if k.endswith(".weight") and k.split(".")[-2] not in ("ln1", "ln2", "ln", "ln_pre", "ln_post")]
+        if self.tower_arithmetic == "split":
+            check_split_domain([(k, state[k]) for k in mats] + ([("proj", state["proj"])] if self.cfg["family"] == "clip" else []),
+                               "metric type 'calculate_clipscore'")
         self.w = {k: v.detach().to(torch.float32).contiguous().to(self.device) for k, v in state.items() if k not in ("heads", "image_size")}
         self.w["patch.weight"] = self.w["patch.weight"].reshape(self.cfg["width"], -1)           # [C, 3 p p]: ssr_vit_patch_input's columns
         if self.cfg["family"] == "clip":
             self.w["proj.t"] = self.w["proj"].t().contiguous()                                    # [E, C]
+        if self.tower_arithmetic == "split":
+            mats += ["proj.t"] if self.cfg["family"] == "clip" else []
+            pack_tower(self.w, mats)
+            for k in mats:
+                del self.w[k]
         self.act = hip.VIT_ACTS["quick_gelu" if self.cfg["family"] == "clip" else f"gelu_{gelu}"]
         self.plans: Dict[Tuple, CLIPVisualPlan] = {}
 
@@ -474,8 +498,11 @@ class CLIPVisualPlan:
         L = engine.Launcher()
 
         def linear(xv, name, yv, rows, K, Nout, act=0, res=NULL_VIEW, wkey=None, bias=True, what=""):
-            L.add(lib.ssr_linear, xv, ptr(wkey or f"{name}.weight"), ptr(f"{name}.bias") if bias else None, res, yv, hip.F32, rows, K, Nout, act,
-                  what=what or f"linear {name}")
+            wkey, bp = wkey or f"{name}.weight", ptr(f"{name}.bias") if bias else None
+            if model.tower_arithmetic == "split":
+                L.add(lib.ssr_linear_split, xv, ptr(f"{wkey}.pk"), bp, res, yv, hip.SPLIT_F16, rows, K, Nout, act, what=what or f"linear {name}")
+            else:
+                L.add(lib.ssr_linear, xv, ptr(wkey), bp, res, yv, hip.F32, rows, K, Nout, act, what=what or f"linear {name}")
 
         def layernorm(xv, name, yv, rows):
             L.add(lib.ssr_layernorm_fwd, xv, ptr(f"{name}.weight"), ptr(f"{name}.bias"), yv, hip.F32, rows, Cw, eps, what=f"layernorm {name}")
@@ -582,6 +609,7 @@ def check_clipscore_opt(clip_model=None, **kw) -> Tuple[str, str, str]:
     gelu = kw.get("gelu", "tanh")
     if gelu not in _GELUS:
         raise NotImplementedError(f"metric type 'calculate_clipscore': gelu={gelu!r} (have {list(_GELUS)})")
+    check_tower_arithmetic(kw.get("tower_arithmetic"), "metric type 'calculate_clipscore': tower_arithmetic")
     given = kw.get("clip_weights")
     if given:
         if not os.path.exists(given):
@@ -601,14 +629,15 @@ def calculate_clipscore(img, img2, clip_model=None, **kw) -> float:
     """One image pair per call (uint8 [1, H, W, 3] or [H, W, 3] RGB on the device), as the other entries of metrics.METRICS; both
     images go through the tower in one pass.  Keys: clip_model ('siglip-ViT-SO400M-14' | 'clip-ViT-B/16'); ours: clip_weights, rgb
     (default false: the reference's BGR feed), normalize (default false: the reference's raw [0, 1] feed), gelu ('tanh' | 'erf',
-    siglip only).  The loaded tower and its plans are cached per (family, resolved path, device, gelu): the reference reloads the
-    model for every image."""
+    siglip only), tower_arithmetic ('exact', the default: ssr_linear | 'split': ssr_linear_split with fp16 pieces).  The loaded tower
+    and its plans are cached per (family, resolved path, device, gelu, tower_arithmetic): the reference reloads the model for every image."""
     family, path, gelu = check_clipscore_opt(clip_model, **kw)
+    arith = check_tower_arithmetic(kw.get("tower_arithmetic"), "metric type 'calculate_clipscore': tower_arithmetic")
     a, b = (t if t.dim() == 4 else t[None] for t in (img, img2))
     if a.shape[0] != 1:
         raise ValueError("one image per call (the reference validates with batch size 1)")
-    key = (family, path, a.device.index, gelu)
+    key = (family, path, a.device.index, gelu, arith)
     if key not in _MODELS:
-        _MODELS[key] = CLIPVisualModel(load_clip_visual_state(path, family), a.device, gelu=gelu)
+        _MODELS[key] = CLIPVisualModel(load_clip_visual_state(path, family), a.device, gelu=gelu, tower_arithmetic=arith)
     s = clipscore(a, b, _MODELS[key], bgr=not kw.get("rgb", False), normalize=bool(kw.get("normalize", False)))
     return float(s[0])

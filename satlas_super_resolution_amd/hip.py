@@ -182,9 +182,11 @@ ABI_SYMBOLS = [
     "ssr_linear", "ssr_layernorm_fwd", "ssr_mha_fwd", "ssr_vit_patch_input", "ssr_vit_tokens", "ssr_cosine_pairs",
     "ssr_vit_float_input", "ssr_vit_float_input_bwd", "ssr_layernorm_bwd", "ssr_vit_act_fwd", "ssr_vit_act_bwd", "ssr_mha_bwd_ws_floats",
     "ssr_mha_bwd", "ssr_feature_l1",
+    "ssr_linear_split_pack_bytes", "ssr_linear_split_pack", "ssr_linear_split",
     "ssr_device_info", "ssr_abi_version",
 ]
 VIT_ACTS = {"none": 0, "quick_gelu": 1, "gelu_tanh": 2, "gelu_erf": 3}      # SSR_VIT_ACT_*: `act` of ssr_linear (csrc/vit.hip)
+SPLIT_F16, SPLIT_BF16 = 1, 2  # SSR_SPLIT_*: `pieces` of ssr_linear_split (csrc/linear_split.hip)
 OBJ_CROP, OBJ_MAX_SIDE = 32, 128   # SSR_OBJ_CROP, SSR_OBJ_MAX_SIDE: side of a resized object crop, largest box side served (csrc/obj_crop.hip)
 SCAN_MAX_RANGES = 8           # SSR_SCAN_MAX_RANGES: ranges per ssr_nonfinite_scan call
 
@@ -311,11 +313,15 @@ def lib() -> C.CDLL:
     l.ssr_mha_bwd_ws_floats.argtypes = [i32, i32, i32]
     l.ssr_mha_bwd.argtypes = [View, View, View, View, View, View, View, vp, i32, i32, i32, i32, i32, i32, f32, vp]
     l.ssr_feature_l1.argtypes = [View, View, View, i32, i32, f32, vp, i32, vp]
+    l.ssr_linear_split_pack_bytes.argtypes = [i32, i32]
+    l.ssr_linear_split_pack.argtypes = [vp, i32, i32, i32, vp, vp]
+    l.ssr_linear_split.argtypes = [View, vp, vp, View, View, i32, i32, i32, i32, i32, vp]
     l.ssr_device_info.argtypes = [C.c_char_p, i32]
     l.ssr_abi_version.argtypes = []
     for s in ABI_SYMBOLS:
         getattr(l, s).restype = i64 if s in ("ssr_conv2d_chain_state_bytes", "ssr_sr_tail_scratch_bytes", "ssr_self_attention_save_floats",
-                                              "ssr_self_attention_scratch_floats", "ssr_mha_bwd_ws_floats") else i32
+                                              "ssr_self_attention_scratch_floats", "ssr_mha_bwd_ws_floats",
+                                              "ssr_linear_split_pack_bytes") else i32
     _lib = l
     return l
 

@@ -1,13 +1,14 @@
-"""Step time of ESRGANTrainStep with and without the CLIP loss (train.clip_opt; clip_loss.py, csrc/vit_bwd.hip), in one process on
-one GPU.
+"""Step time of ESRGANTrainStep without the CLIP loss and with it under both tower arithmetics (train.clip_opt; clip_loss.py,
+csrc/vit_bwd.hip, csrc/linear_split.hip), in one process on one GPU.
 
 The default step as bench.py runs it (B = 32, 8 Sentinel-2 frames = 24 input channels, fp32h, deterministic reductions, hipGraph
-replay), once without `clip` and once with a random tower of the ViT-B-16-SigLIP-256 sizes (clip_random_state: width 768, depth 12,
-12 heads of 64, MLP 3072, patch 16, 256 tokens at 256 x 256).  The two steps are timed in alternating blocks (per-step event
-pairs), and medians and minima are printed as one JSON line.  There is no CPU path: without a GPU the script fails.
+replay), once without `clip` and once per tower arithmetic with a random tower of the ViT-B-16-SigLIP-256 sizes (clip_random_state:
+width 768, depth 12, 12 heads of 64, MLP 3072, patch 16, 256 tokens at 256 x 256).  The legs - off, exact, split - are timed in
+alternating blocks of three steps (per-step event pairs); medians, minima and, per leg, the spread of its own blocks' medians are
+printed as one JSON line.  There is no CPU path: without a GPU the script fails.
 
-  python tools/clip_loss_bench.py [--steps 12] [--warmup 3]
-  python tools/clip_loss_bench.py --only-clip --steps 3 --no-graph      # under rocprofv3 --kernel-trace --stats: a serial kernel trace
+  python tools/clip_loss_bench.py [--steps 12] [--warmup 3] [--tower-arithmetic exact|split|both]
+  python tools/clip_loss_bench.py --only-clip --tower-arithmetic split --steps 3 --no-graph   # under rocprofv3 --kernel-trace --stats
 """
 import argparse
 import json
@@ -19,15 +20,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 TOWER = dict(width=768, depth=12, mlp=3072, patch=16, grid=16, heads=12)
+BLOCK = 3
 
 
-def build(clip, B, dtype, use_graph):
+def build(leg, B, dtype, use_graph):
+    """leg: 'off' | 'exact' | 'split'"""
     from satlas_super_resolution_amd import clipscore_metric as CM, flops
     from satlas_super_resolution_amd.train_step import ESRGANTrainStep, StepConfig
     g_kw = dict(num_in_ch=24, num_out_ch=3, scale=4, num_feat=64, num_block=23, num_grow_ch=32)
     d_kw = dict(num_in_ch=3, num_feat=64, skip_connection=True)
-    cfg = StepConfig(deterministic=True, clip={"model": "ViT-B-16-SigLIP-256", "family": "siglip", "path": None, "gelu": "tanh",
-                                               "loss_weight": 1.0} if clip else None)
+    clip = None
+    if leg != "off":
+        clip = {"model": "ViT-B-16-SigLIP-256", "family": "siglip", "path": None, "gelu": "tanh", "loss_weight": 1.0}
+        if leg == "split":
+            clip["tower_arithmetic"] = "split"
+    cfg = StepConfig(deterministic=True, clip=clip)
     ts = ESRGANTrainStep(g_kw, d_kw, B, 32, 32, dtype, cfg, use_graph=use_graph,
                          clip_state=CM.clip_random_state("siglip", seed=3, **TOWER) if clip else None)
     ts.load_state(flops.generator_random_state(seed=0, **g_kw), flops.discriminator_random_state(3, 64, seed=1))
@@ -35,7 +42,7 @@ def build(clip, B, dtype, use_graph):
 
 
 def tower_flops(B):
-    """multiply-adds x 2 of the ssr_linear launches of one step's term: two forwards (target, generated) and one data-gradient pass"""
+    """multiply-adds x 2 of the linear launches of one step's term: two forwards (target, generated) and one data-gradient pass"""
     w, d, m, T, kp = TOWER["width"], TOWER["depth"], TOWER["mlp"], TOWER["grid"] ** 2, 3 * TOWER["patch"] ** 2
     per_token = kp * w + d * (4 * w * w + 2 * w * m) + 2 * w * w          # embedding, blocks (qkv 3, proj 1, fc1, fc2), pooling kv
     return 2.0 * 3 * B * T * per_token
@@ -49,20 +56,20 @@ def run(args):
     B = args.batch
     lr = torch.rand(B, 24, 32, 32, device="cuda")
     gt = torch.rand(B, 3, 128, 128, device="cuda")
-    legs = [True] if args.only_clip else [False, True]
+    on = ["exact", "split"] if args.tower_arithmetic == "both" else [args.tower_arithmetic]
+    legs = on if args.only_clip else ["off"] + on
     steps = {}
-    for clip in legs:
-        ts = build(clip, B, args.dtype, not args.no_graph)
+    for leg in legs:
+        ts = build(leg, B, args.dtype, not args.no_graph)
         ts.feed_data(lr, gt)
         for _ in range(max(2, args.warmup)):
             ts.step()
-        steps[clip] = ts
+        steps[leg] = ts
     torch.cuda.synchronize()
     times = {k: [] for k in legs}
-    block = 3
     while min(len(v) for v in times.values()) < args.steps:
         for k, ts in steps.items():
-            for _ in range(block):
+            for _ in range(BLOCK):
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 a.record()
                 ts.step()
@@ -70,17 +77,25 @@ def run(args):
                 b.synchronize()
                 times[k].append(a.elapsed_time(b))
     logs = {k: ts.log() for k, ts in steps.items()}
-    name = lambda k: "clip on" if k else "clip off"                          # noqa: E731
-    plan = steps[True].c_plan
-    out = {"what": "ESRGANTrainStep, the default benchmark step, CLIP loss off / on (random ViT-B-16-SigLIP-256-sized tower)", "batch": B,
+    name = lambda k: f"clip {k}"                                             # noqa: E731
+    med = {k: statistics.median(v) for k, v in times.items()}
+    blocks = {k: [statistics.median(v[i:i + BLOCK]) for i in range(0, len(v), BLOCK)] for k, v in times.items()}
+    out = {"what": "ESRGANTrainStep, the default benchmark step, CLIP loss off / on with tower_arithmetic exact / split (random "
+                   "ViT-B-16-SigLIP-256-sized tower)", "batch": B,
            "dtype": args.dtype, "deterministic": True, "hip_graph": not args.no_graph, "timed_steps_each": {name(k): len(v) for k, v in times.items()},
-           "median_ms": {name(k): round(statistics.median(v), 3) for k, v in times.items()},
+           "median_ms": {name(k): round(med[k], 3) for k in times},
            "min_ms": {name(k): round(min(v), 3) for k, v in times.items()},
-           "l_clip_sim": logs[True].get("l_clip_sim"), "term_launches": len(plan.launcher), "saved_activation_bytes": plan.saved_bytes,
+           "block_medians_ms": {name(k): [round(x, 3) for x in v] for k, v in blocks.items()},
+           "block_spread_ms": {name(k): round(max(v) - min(v), 3) for k, v in blocks.items()},
+           "l_clip_sim": {name(k): logs[k].get("l_clip_sim") for k in on},
+           "term_launches": {name(k): len(steps[k].c_plan.launcher) for k in on},
+           "saved_activation_bytes": steps[on[0]].c_plan.saved_bytes,
            "term_linear_gflop": round(tower_flops(B) / 1e9, 1), "device_memory_allocated_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
     if not args.only_clip:
-        out["clip_term_ms"] = round(statistics.median(times[True]) - statistics.median(times[False]), 3)
-        out["term_linear_tflops"] = round(tower_flops(B) / 1e9 / out["clip_term_ms"], 1)
+        out["clip_term_ms"] = {name(k): round(med[k] - med["off"], 3) for k in on}
+        out["term_linear_tflops"] = {name(k): round(tower_flops(B) / 1e9 / (med[k] - med["off"]), 1) for k in on}
+        if len(on) == 2:
+            out["split_saves_ms"] = round(med["exact"] - med["split"], 3)
     print(json.dumps(out))
 
 
@@ -90,6 +105,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--dtype", default="fp32h")
+    ap.add_argument("--tower-arithmetic", default="both", choices=["exact", "split", "both"],
+                    help="the arithmetic of the tower's matrix products in the legs with the term (both: one leg each)")
     ap.add_argument("--only-clip", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
     run(ap.parse_args())
