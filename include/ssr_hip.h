@@ -974,6 +974,29 @@ int ssr_linear_split_pack(const float* w, int32_t Nout, int32_t K, int32_t piece
 int ssr_linear_split(ssr_view x, const void* wpk, const float* bias, ssr_view r, ssr_view y, int32_t pieces, int32_t M, int32_t K,
                      int32_t Nout, int32_t act, void* stream);
 
+/* ---- The tower's self-attention on the fp32-input matrix core (csrc/mha_mfma.hip; `tower_attention: mfma` of train.clip_opt and of
+ *      calculate_clipscore; additive: the ABI version stays 3) ----
+ * ssr_mha_mfma_fwd: ssr_mha_fwd's result, y = softmax_j(q_i . k_j * scale) v per (image, head), with the same views, row and head
+ *   layout, max-subtracted softmax in fp32 (expf) and key tiles of 64 with a running maximum and sum (any Tq, Tk >= 1, tails masked:
+ *   nothing outside the views is read or written).  Only the matrix products differ: q k^T and P v run on v_mfma_f32_32x32x2_f32, whose
+ *   result is a k-ordered fp32 fmaf chain, so against ssr_mha_fwd only the order of the additions changes.  Head dims 64 and 72
+ *   (SSR_EUNSUP otherwise; 72 is padded to 96 in registers on the output side, never in memory).  A block owns 128 queries.
+ *   SSR_EUNSUP: a dtype other than F32, d not 64 or 72, N or heads > 65535, Tq or Tk > 2^20.  SSR_EINVAL: a size <= 0, a NaN scale, a
+ *   bad view.  y must not alias q, k or v.
+ * ssr_mha_mfma_bwd: ssr_mha_bwd's result, dS = P (dP - delta), dv = P^T dy, dk = scale dS^T q, dq = scale dS k, the statistics
+ *   recomputed (nothing is taken from the forward), dq optionally a null view; q k^T, dy v^T, P^T dy, dS^T q and dS k on the same
+ *   instruction, the softmax, its rescaling and delta on the vector unit in fp32.  Two launches as ssr_mha_bwd: blocks that own 128
+ *   queries walk the keys (statistics, delta, dq), blocks that own 128 keys walk the queries (dk, dv).  ws:
+ *   ssr_mha_mfma_bwd_ws_floats(N, Tq, heads) = 3 N heads Tq floats of scratch (maximum, 1 / sum, delta per query row), written by the
+ *   first launch and read by the second.  dq, dk, dv must not alias an input.  Error codes as ssr_mha_bwd (a null ws: SSR_EINVAL).
+ * Both: no atomics, one fixed order of additions per output (two launches give the same bytes), and an image's bytes depend neither
+ *   on N nor on its place in the batch.  A refused call launches nothing. */
+int ssr_mha_mfma_fwd(ssr_view q, ssr_view k, ssr_view v, ssr_view y, int32_t dtype, int32_t N, int32_t Tq, int32_t Tk, int32_t heads,
+                     int32_t d, float scale, void* stream);
+int64_t ssr_mha_mfma_bwd_ws_floats(int32_t N, int32_t Tq, int32_t heads);
+int ssr_mha_mfma_bwd(ssr_view q, ssr_view k, ssr_view v, ssr_view dy, ssr_view dq, ssr_view dk, ssr_view dv, float* ws, int32_t dtype,
+                     int32_t N, int32_t Tq, int32_t Tk, int32_t heads, int32_t d, float scale, void* stream);
+
 /* library / device info: writes "gfx950 CUs=256 ..." style text */
 int ssr_device_info(char* buf, int32_t buflen);
 int ssr_abi_version(void);

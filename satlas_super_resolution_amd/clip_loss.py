@@ -22,6 +22,11 @@ refused by name.  Statements that rest on open_clip behaviour that cannot be exe
 `tower_arithmetic` ('exact', the default | 'split'; linear_split.py): under 'split' every matrix product of the tower runs as
 ssr_linear_split (csrc/linear_split.hip) - fp16 pieces in both forward passes, bf16 pieces in the backward's transposes - and
 clip_loss_grad_reference restates that on the CPU.
+
+`tower_attention` ('fma', the default | 'mfma'; csrc/mha_mfma.hip): under 'mfma' the blocks' self-attention of both forward passes and of
+the backward runs as ssr_mha_mfma_fwd / ssr_mha_mfma_bwd on the fp32-input matrix core - exact fp32 products, another order of
+additions, so the CPU statements above hold for it unchanged.  The pooling head (one query row) keeps ssr_mha_fwd / ssr_mha_bwd.
+Orthogonal to tower_arithmetic.
 """
 from __future__ import annotations
 
@@ -32,7 +37,8 @@ import torch
 import torch.nn.functional as F
 
 from .clipscore_metric import CLIP_MEAN, CLIP_STD, _GELUS, _attention, _flat_keys, nearest_index_table, vit_config_from_state, vit_features_from_input
-from .linear_split import check_split_domain, check_tower_arithmetic, linear_split_reference, pack_tower  # noqa: F401  (linear_split_reference: re-exported)
+from .linear_split import (check_mfma_head_dim, check_split_domain, check_tower_arithmetic, check_tower_attention,  # noqa: F401
+                           linear_split_reference, pack_tower)                        # (linear_split_reference: re-exported)
 
 CLIP_LOSS_MODELS = {"ViT-B-16-SigLIP-256": "siglip"}                                 # the reference's clip_loss_model -> family
 CLIP_LOSS_MEAN, CLIP_LOSS_STD = CLIP_MEAN["clip"], CLIP_STD["clip"]                    # OpenAI's, whatever the tower
@@ -183,14 +189,15 @@ CLIP_LOSS_REFUSED = {"EVA02-E-14-plus": "4.4 B parameters", "RN50": "a ResNet, n
 CLIP_LOSS_ENV = "SSR_CLIP_LOSS_SIGLIP_B16_WEIGHTS"
 CLIP_LOSS_PRETRAIN_PATH = "experiments/pretrained_models/clip_siglip_b16_256.pth"
 _SAVE_HINT = "torch.save(open_clip.create_model_and_transforms('ViT-B-16-SigLIP-256', pretrained='webli')[0].visual.state_dict(), <file>)"
-_CLIP_OPT_KEYS = ("type", "clip_loss_model", "loss_weight", "clip_weights", "gelu", "tower_arithmetic")
+_CLIP_OPT_KEYS = ("type", "clip_loss_model", "loss_weight", "clip_weights", "gelu", "tower_arithmetic", "tower_attention")
 
 
 def check_clip_opt(block: Dict) -> Dict:
     """Validates a `train.clip_opt` block and finds the weights -> {"model", "family", "path", "gelu", "loss_weight"}.  Touches no
     device.  Keys: type (CLIPLoss), clip_loss_model (ViT-B-16-SigLIP-256), loss_weight (default 1.0, as CLIPLoss.__init__); ours:
     clip_weights (a file), gelu ('tanh' | 'erf', default 'tanh' as the CLIPScore metric), tower_arithmetic ('exact', the default and
-    what an absent key means: the result carries no such entry | 'split': "tower_arithmetic": "split").  The weights file is the option
+    what an absent key means: the result carries no such entry | 'split': "tower_arithmetic": "split"), tower_attention ('fma', the
+    default, likewise absent from the result | 'mfma': "tower_attention": "mfma").  The weights file is the option
     `clip_weights`, else the environment variable SSR_CLIP_LOSS_SIGLIP_B16_WEIGHTS, else the default path; anything else raises
     NotImplementedError beginning `train.clip_opt`."""
     import os
@@ -212,6 +219,8 @@ def check_clip_opt(block: Dict) -> Dict:
     out = {"model": name, "family": CLIP_LOSS_MODELS[name], "gelu": gelu, "loss_weight": float(block.get("loss_weight", 1.0))}
     if check_tower_arithmetic(block.get("tower_arithmetic"), "train.clip_opt.tower_arithmetic") == "split":
         out["tower_arithmetic"] = "split"
+    if check_tower_attention(block.get("tower_attention"), "train.clip_opt.tower_attention") == "mfma":
+        out["tower_attention"] = "mfma"
     given = block.get("clip_weights")
     if given:
         if not os.path.exists(given):
@@ -230,13 +239,17 @@ def check_clip_opt(block: Dict) -> Dict:
 _LOSS_MODELS: Dict[Tuple, "ClipLossModel"] = {}
 
 
-def clip_loss_model(path: str, device, gelu: str = "tanh", tower_arithmetic: str = "exact") -> "ClipLossModel":
-    """the tower of a weights file on the device, loaded once per (resolved path, device, gelu, tower_arithmetic)"""
-    from .clipscore_metric import load_clip_visual_state
+def _loss_model_key(path: str, device, gelu: str, tower_arithmetic: str, tower_attention: str) -> Tuple:
     device = torch.device(device)
-    key = (path, device.type, device.index, gelu, tower_arithmetic)
+    return (path, device.type, device.index, gelu, tower_arithmetic, tower_attention)
+
+
+def clip_loss_model(path: str, device, gelu: str = "tanh", tower_arithmetic: str = "exact", tower_attention: str = "fma") -> "ClipLossModel":
+    """the tower of a weights file on the device, loaded once per (resolved path, device, gelu, tower_arithmetic, tower_attention)"""
+    from .clipscore_metric import load_clip_visual_state
+    key = _loss_model_key(path, device, gelu, tower_arithmetic, tower_attention)
     if key not in _LOSS_MODELS:
-        _LOSS_MODELS[key] = ClipLossModel(load_clip_visual_state(path, "siglip"), device, gelu, tower_arithmetic)
+        _LOSS_MODELS[key] = ClipLossModel(load_clip_visual_state(path, "siglip"), torch.device(device), gelu, tower_arithmetic, tower_attention)
     return _LOSS_MODELS[key]
 
 
@@ -248,13 +261,16 @@ class ClipLossModel:
     matrix the backward passes through (dX = dY W is ssr_linear on W^T's rows): made once at load, + 0.34 GB for ViT-B.
     tower_arithmetic 'split': instead of both fp32 copies, every matrix is held as `<name>.weight.pk`, the packed fp16 pieces of W
     (forward), and `<name>.weight.t.pk`, the packed bf16 pieces of W^T (backward), for ssr_linear_split; a matrix with max|w| >= 64
-    raises ValueError by name, on the host, before anything is loaded."""
+    raises ValueError by name, on the host, before anything is loaded.  tower_attention changes no weight: it is what the plans of
+    this model launch for the blocks' self-attention."""
 
-    def __init__(self, state: Dict[str, torch.Tensor], device="cuda", gelu: str = "tanh", tower_arithmetic: str = "exact"):
+    def __init__(self, state: Dict[str, torch.Tensor], device="cuda", gelu: str = "tanh", tower_arithmetic: str = "exact",
+                 tower_attention: str = "fma"):
         from . import hip
         if gelu not in _GELUS:
             raise NotImplementedError(f"train.clip_opt: gelu={gelu!r} (have {list(_GELUS)})")
         self.tower_arithmetic = check_tower_arithmetic(tower_arithmetic, "train.clip_opt.tower_arithmetic")
+        self.tower_attention = check_tower_attention(tower_attention, "train.clip_opt.tower_attention")
         self.cfg = vit_config_from_state(state)
         if self.cfg["family"] != "siglip":
             raise NotImplementedError("train.clip_opt: the backward of a `clip` tower (class token) is not built: no clip_loss_model needs it")
@@ -288,7 +304,8 @@ class ClipLossPlan:
       bwd          ssr_feature_l1, the pooling head, ln_post, the blocks in reverse, the patch embedding, ssr_vit_float_input_bwd,
                    which ADDS the image gradient into grad_view
     `launcher` is the three in that order.  fc1 runs without its activation into the saved buffer and ssr_vit_act_fwd applies it (same
-    device function: same bytes), on both passes, so the two feature sets come from identical arithmetic."""
+    device function: same bytes), on both passes, so the two feature sets come from identical arithmetic.  A model with tower_attention
+    'mfma' launches ssr_mha_mfma_fwd / ssr_mha_mfma_bwd for the blocks (all three lists); the pooling head keeps ssr_mha_fwd / _bwd."""
 
     def __init__(self, model: ClipLossModel, B: int, H: int, W: int, fake_view, target_view, grad_view, loss_ptr: int, weight: float = 1.0,
                  flags: int = 0):
@@ -302,6 +319,10 @@ class ClipLossPlan:
             raise ValueError(f"patch size {p}: ssr_linear contracts 3 p^2 channels, a multiple of 4")
         if d not in (64, 72):
             raise NotImplementedError(f"train.clip_opt: head dim {d} has no attention backward (ssr_mha_bwd: 64, 72)")
+        use_mfma = model.tower_attention == "mfma"
+        if use_mfma:
+            check_mfma_head_dim(d, "train.clip_opt")
+        ws_floats = hip.lib().ssr_mha_mfma_bwd_ws_floats if use_mfma else hip.lib().ssr_mha_bwd_ws_floats
         self.model, self.B, self.H, self.W = model, B, H, W
         lib, S, KP, M, depth = hip.lib(), cfg["image_size"], 3 * p * p, B * T, cfg["depth"]
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)      # noqa: E731
@@ -320,7 +341,8 @@ class ClipLossPlan:
                          # gradients
                          "df": z(B, Cw), "dpm": z(B, mlp), "dpz": z(B, Cw), "dpy": z(B, Cw), "dpa": z(B, Cw), "dkv": z(M, 2 * Cw), "dh": z(M, Cw),
                          "dx": z(M, Cw), "dx2": z(M, Cw), "dmlp": z(M, mlp), "datt": z(M, Cw), "dqkv": z(M, 3 * Cw), "dpatch": z(M, KP),
-                         "ws": z(max(int(lib.ssr_mha_bwd_ws_floats(B, T, heads)), 1))}
+                         # the blocks' attention backward sizes it; the pooling head's (Tq = 1, always ssr_mha_bwd) needs less
+                         "ws": z(max(int(ws_floats(B, T, heads)), int(lib.ssr_mha_bwd_ws_floats(B, 1, heads)), 1))}
         for i in range(depth + 1):
             b[f"x.{i}"] = z(M, Cw)                                             # x.i: the input of block i; x.depth: the tower's last rows
         for i in range(depth):
@@ -331,6 +353,7 @@ class ClipLossPlan:
         F32 = hip.F32
 
         use_split = model.tower_arithmetic == "split"  # ssr_linear_split: fp16 pieces forward (both passes), bf16 pieces backward
+        mha_fwd, mha_bwd = (lib.ssr_mha_mfma_fwd, lib.ssr_mha_mfma_bwd) if use_mfma else (lib.ssr_mha_fwd, lib.ssr_mha_bwd)   # the blocks'
 
         def linear(L, xv, name, yv, rows, K, Nout, res=NULL_VIEW):
             if use_split:
@@ -368,7 +391,7 @@ class ClipLossPlan:
                 qs = split(qkvs[i], 3)
                 layernorm(L, view(xs[i]), f"{n}.ln1", hv, M)
                 linear(L, hv, f"{n}.qkv", view(qkvs[i]), M, Cw, 3 * Cw)
-                L.add(lib.ssr_mha_fwd, qs[0], qs[1], qs[2], view(b["att"]), F32, B, T, T, heads, d, scale, what=f"attention {n}")
+                L.add(mha_fwd, qs[0], qs[1], qs[2], view(b["att"]), F32, B, T, T, heads, d, scale, what=f"attention {n}")
                 linear(L, view(b["att"]), f"{n}.proj", view(xmids[i]), M, Cw, Cw, res=view(xs[i]))
                 layernorm(L, view(xmids[i]), f"{n}.ln2", hv, M)
                 linear(L, hv, f"{n}.fc1", view(pres[i]), M, Cw, mlp)
@@ -413,7 +436,7 @@ class ClipLossPlan:
             layernorm_bwd(L, view(b[f"xmid.{i}"]), f"{n}.ln2", view(b["dh"]), view(b["dx"]), view(b["dx2"]), M)
             linear_t(L, view(b["dx2"]), f"{n}.proj", view(b["datt"]), M, Cw, Cw)
             qs, dqs = split(b[f"qkv.{i}"], 3), split(b["dqkv"], 3)
-            L.add(lib.ssr_mha_bwd, qs[0], qs[1], qs[2], view(b["datt"]), dqs[0], dqs[1], dqs[2], ws, F32, B, T, T, heads, d, scale,
+            L.add(mha_bwd, qs[0], qs[1], qs[2], view(b["datt"]), dqs[0], dqs[1], dqs[2], ws, F32, B, T, T, heads, d, scale,
                   what=f"attention bwd {n}")
             linear_t(L, view(b["dqkv"]), f"{n}.qkv", view(b["dh"]), M, 3 * Cw, Cw)
             layernorm_bwd(L, view(b[f"x.{i}"]), f"{n}.ln1", view(b["dh"]), view(b["dx2"]), view(b["dx"]), M)

@@ -62,7 +62,7 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn.functional as F
 
-from .linear_split import check_split_domain, check_tower_arithmetic, linear_split_reference, pack_tower
+from .linear_split import check_mfma_head_dim, check_split_domain, check_tower_arithmetic, check_tower_attention, linear_split_reference, pack_tower
 
 CLIP_MODELS = {"siglip-ViT-SO400M-14": "siglip", "clip-ViT-B/16": "clip"}          # the reference's names -> family
 CLIP_REFUSED = ("clipa-ViT-bigG-14",)                                                # the reference's third branch: 1.8 B parameters
@@ -75,7 +75,7 @@ CLIP_STD = {"siglip": (0.5, 0.5, 0.5), "clip": (0.26862954, 0.26130258, 0.275777
 LN_EPS = {"siglip": 1e-6, "clip": 1e-5}
 COS_EPS = 1e-8
 _IGNORED_KEYS = ("crop_border", "test_y_channel", "input_order", "better", "type")
-_OUR_KEYS = ("clip_weights", "rgb", "normalize", "gelu", "tower_arithmetic")
+_OUR_KEYS = ("clip_weights", "rgb", "normalize", "gelu", "tower_arithmetic", "tower_attention")
 _GELUS = ("tanh", "erf")
 _BLOCK_LEAVES = ("ln1", "qkv", "proj", "ln2", "fc1", "fc2")
 _POOL_LEAVES = ("q", "kv", "proj", "ln", "fc1", "fc2")
@@ -428,14 +428,17 @@ def clipscore_reference(a_u8, b_u8, state: Dict[str, torch.Tensor], bgr: bool = 
 # ---------------------------------------------------------------- the device path
 class CLIPVisualModel:
     """The weights of one tower on the device (fp32, the matrices as the state_dict holds them: ssr_linear reads [Nout][K] rows) and
-    the plans that use them, cached per (B, H, W, bgr, normalize).  tower_arithmetic 'split': every matrix is held as the packed fp16
-    pieces of ssr_linear_split instead (`<key>.pk`; a matrix with max|w| >= 64 raises ValueError by name before anything is loaded)."""
+    the plans that use them, cached per (B, H, W, bgr, normalize, tower_attention).  tower_arithmetic 'split': every matrix is held as the packed fp16
+    pieces of ssr_linear_split instead (`<key>.pk`; a matrix with max|w| >= 64 raises ValueError by name before anything is loaded).
+    tower_attention 'mfma' changes no weight: the plans launch ssr_mha_mfma_fwd (csrc/mha_mfma.hip) for the blocks' self-attention."""
 
-    def __init__(self, state: Dict[str, torch.Tensor], device="cuda", gelu: str = "tanh", tower_arithmetic: str = "exact"):
+    def __init__(self, state: Dict[str, torch.Tensor], device="cuda", gelu: str = "tanh", tower_arithmetic: str = "exact",
+                 tower_attention: str = "fma"):
         from . import hip
         if gelu not in _GELUS:
             raise NotImplementedError(f"gelu={gelu!r} (have {list(_GELUS)})")
         self.tower_arithmetic = check_tower_arithmetic(tower_arithmetic, "metric type 'calculate_clipscore': tower_arithmetic")
+        self.tower_attention = check_tower_attention(tower_attention, "metric type 'calculate_clipscore': tower_attention")
         self.cfg = vit_config_from_state(state)
         self.device, self.gelu = torch.device(device), gelu
         for k in _flat_keys(self.cfg["family"], self.cfg["depth"]):
@@ -459,7 +462,7 @@ class CLIPVisualModel:
         self.plans: Dict[Tuple, CLIPVisualPlan] = {}
 
     def plan(self, B: int, H: int, W: int, bgr: bool = True, normalize: bool = False) -> "CLIPVisualPlan":
-        key = (B, H, W, bool(bgr), bool(normalize))
+        key = (B, H, W, bool(bgr), bool(normalize), self.tower_attention)
         if key not in self.plans:
             self.plans[key] = CLIPVisualPlan(self, B, H, W, bgr, normalize)
         return self.plans[key]
@@ -480,8 +483,11 @@ class CLIPVisualPlan:
         fam, Cw, p, g, T, mlp, heads, d, E = (cfg[k] for k in ("family", "width", "patch", "grid", "tokens", "mlp", "heads", "head_dim", "out_dim"))
         if p % 2:
             raise ValueError(f"patch size {p}: ssr_linear contracts 3 p^2 channels, a multiple of 4")
+        if model.tower_attention == "mfma":
+            check_mfma_head_dim(d, "metric type 'calculate_clipscore'")
         self.model, self.B, self.H, self.W = model, B, H, W
         lib, G, S, KP = hip.lib(), g * g, cfg["image_size"], 3 * p * p
+        mha_blocks = lib.ssr_mha_mfma_fwd if model.tower_attention == "mfma" else lib.ssr_mha_fwd      # the pooling head keeps ssr_mha_fwd
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)      # noqa: E731
         # the resize to S x S, of which the patch convolution reads the first g * p rows and columns
         self.rowidx = nearest_index_table(H, S)[:g * p].to(torch.int32).to(dev)
@@ -519,7 +525,7 @@ class CLIPVisualPlan:
             n = f"blocks.{i}"
             layernorm(xv, f"{n}.ln1", hv, M)
             linear(hv, f"{n}.qkv", view(b["qkv"]), M, Cw, 3 * Cw)
-            L.add(lib.ssr_mha_fwd, qkv[0], qkv[1], qkv[2], view(b["att"]), hip.F32, B, T, T, heads, d, scale, what=f"attention {n}")
+            L.add(mha_blocks, qkv[0], qkv[1], qkv[2], view(b["att"]), hip.F32, B, T, T, heads, d, scale, what=f"attention {n}")
             linear(view(b["att"]), f"{n}.proj", xv, M, Cw, Cw, res=xv)
             layernorm(xv, f"{n}.ln2", hv, M)
             linear(hv, f"{n}.fc1", view(b["mlp"]), M, Cw, mlp, act=act)
@@ -587,6 +593,11 @@ def clipscore(a_u8: torch.Tensor, b_u8: torch.Tensor, model: CLIPVisualModel, bg
 
 # ---------------------------------------------------------------- the metric entry
 _MODELS: Dict[Tuple, CLIPVisualModel] = {}
+
+
+def _model_key(family: str, path: str, device_index, gelu: str, tower_arithmetic: str, tower_attention: str) -> Tuple:
+    """what one cached tower (and so its plans) is loaded per"""
+    return (family, path, device_index, gelu, tower_arithmetic, tower_attention)
 _SAVE_HINT = {
     "siglip": "torch.save(open_clip.create_model_and_transforms('ViT-SO400M-14-SigLIP-384', pretrained='webli')[0].visual.state_dict(), <file>)",
     "clip": "torch.save(clip.load('ViT-B/16', device='cpu')[0].state_dict(), <file>), or the downloaded ViT-B-16.pt itself",
@@ -610,6 +621,7 @@ def check_clipscore_opt(clip_model=None, **kw) -> Tuple[str, str, str]:
     if gelu not in _GELUS:
         raise NotImplementedError(f"metric type 'calculate_clipscore': gelu={gelu!r} (have {list(_GELUS)})")
     check_tower_arithmetic(kw.get("tower_arithmetic"), "metric type 'calculate_clipscore': tower_arithmetic")
+    check_tower_attention(kw.get("tower_attention"), "metric type 'calculate_clipscore': tower_attention")
     given = kw.get("clip_weights")
     if given:
         if not os.path.exists(given):
@@ -629,15 +641,17 @@ def calculate_clipscore(img, img2, clip_model=None, **kw) -> float:
     """One image pair per call (uint8 [1, H, W, 3] or [H, W, 3] RGB on the device), as the other entries of metrics.METRICS; both
     images go through the tower in one pass.  Keys: clip_model ('siglip-ViT-SO400M-14' | 'clip-ViT-B/16'); ours: clip_weights, rgb
     (default false: the reference's BGR feed), normalize (default false: the reference's raw [0, 1] feed), gelu ('tanh' | 'erf',
-    siglip only), tower_arithmetic ('exact', the default: ssr_linear | 'split': ssr_linear_split with fp16 pieces).  The loaded tower
-    and its plans are cached per (family, resolved path, device, gelu, tower_arithmetic): the reference reloads the model for every image."""
+    siglip only), tower_arithmetic ('exact', the default: ssr_linear | 'split': ssr_linear_split with fp16 pieces), tower_attention
+    ('fma', the default: ssr_mha_fwd | 'mfma': ssr_mha_mfma_fwd for the blocks' self-attention).  The loaded tower and its plans are
+    cached per (family, resolved path, device, gelu, tower_arithmetic, tower_attention): the reference reloads the model for every image."""
     family, path, gelu = check_clipscore_opt(clip_model, **kw)
     arith = check_tower_arithmetic(kw.get("tower_arithmetic"), "metric type 'calculate_clipscore': tower_arithmetic")
+    attn = check_tower_attention(kw.get("tower_attention"), "metric type 'calculate_clipscore': tower_attention")
     a, b = (t if t.dim() == 4 else t[None] for t in (img, img2))
     if a.shape[0] != 1:
         raise ValueError("one image per call (the reference validates with batch size 1)")
-    key = (family, path, a.device.index, gelu, arith)
+    key = _model_key(family, path, a.device.index, gelu, arith, attn)
     if key not in _MODELS:
-        _MODELS[key] = CLIPVisualModel(load_clip_visual_state(path, family), a.device, gelu=gelu, tower_arithmetic=arith)
+        _MODELS[key] = CLIPVisualModel(load_clip_visual_state(path, family), a.device, gelu=gelu, tower_arithmetic=arith, tower_attention=attn)
     s = clipscore(a, b, _MODELS[key], bgr=not kw.get("rgb", False), normalize=bool(kw.get("normalize", False)))
     return float(s[0])

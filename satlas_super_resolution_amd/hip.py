@@ -183,6 +183,7 @@ ABI_SYMBOLS = [
     "ssr_vit_float_input", "ssr_vit_float_input_bwd", "ssr_layernorm_bwd", "ssr_vit_act_fwd", "ssr_vit_act_bwd", "ssr_mha_bwd_ws_floats",
     "ssr_mha_bwd", "ssr_feature_l1",
     "ssr_linear_split_pack_bytes", "ssr_linear_split_pack", "ssr_linear_split",
+    "ssr_mha_mfma_fwd", "ssr_mha_mfma_bwd_ws_floats", "ssr_mha_mfma_bwd",
     "ssr_device_info", "ssr_abi_version",
 ]
 VIT_ACTS = {"none": 0, "quick_gelu": 1, "gelu_tanh": 2, "gelu_erf": 3}      # SSR_VIT_ACT_*: `act` of ssr_linear (csrc/vit.hip)
@@ -316,12 +317,15 @@ def lib() -> C.CDLL:
     l.ssr_linear_split_pack_bytes.argtypes = [i32, i32]
     l.ssr_linear_split_pack.argtypes = [vp, i32, i32, i32, vp, vp]
     l.ssr_linear_split.argtypes = [View, vp, vp, View, View, i32, i32, i32, i32, i32, vp]
+    l.ssr_mha_mfma_fwd.argtypes = l.ssr_mha_fwd.argtypes
+    l.ssr_mha_mfma_bwd_ws_floats.argtypes = [i32, i32, i32]
+    l.ssr_mha_mfma_bwd.argtypes = l.ssr_mha_bwd.argtypes
     l.ssr_device_info.argtypes = [C.c_char_p, i32]
     l.ssr_abi_version.argtypes = []
     for s in ABI_SYMBOLS:
         getattr(l, s).restype = i64 if s in ("ssr_conv2d_chain_state_bytes", "ssr_sr_tail_scratch_bytes", "ssr_self_attention_save_floats",
                                               "ssr_self_attention_scratch_floats", "ssr_mha_bwd_ws_floats",
-                                              "ssr_linear_split_pack_bytes") else i32
+                                              "ssr_linear_split_pack_bytes", "ssr_mha_mfma_bwd_ws_floats") else i32
     _lib = l
     return l
 

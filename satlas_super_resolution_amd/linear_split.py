@@ -9,6 +9,7 @@ Every fp32 operand v is two 16-bit pieces, hi = round16(v) and lo = round16(v - 
     linear_split_reference     the arithmetic model the kernel is held to: the three piece products in float64
     split_representation_bound what the model may differ from the exact product by, per output
     check_tower_arithmetic     the option's values
+    check_tower_attention      the values of the sibling option `tower_attention: fma | mfma` (csrc/mha_mfma.hip), check_mfma_head_dim
     check_split_domain         |w| < 64 for every matrix, by name, on the host
     pack_split_weight          ssr_linear_split_pack into a fresh device buffer
 """
@@ -30,6 +31,27 @@ def check_tower_arithmetic(value, where: str) -> str:
     if value not in TOWER_ARITHMETICS:
         raise NotImplementedError(f"{where}={value!r} (have {list(TOWER_ARITHMETICS)})")
     return value
+
+
+TOWER_ATTENTIONS = ("fma", "mfma")      # ssr_mha_fwd / ssr_mha_bwd | ssr_mha_mfma_fwd / ssr_mha_mfma_bwd (csrc/mha_mfma.hip)
+MFMA_HEAD_DIMS = (64, 72)               # the head dims ssr_mha_mfma_* take
+
+
+def check_tower_attention(value, where: str) -> str:
+    """`tower_attention` of train.clip_opt and of calculate_clipscore: which kernels run the blocks' self-attention, 'fma' (the
+    default, and what None, an absent key, means) or 'mfma' (the fp32-input matrix core; same mathematics, another order of
+    additions).  Orthogonal to tower_arithmetic.  `where` names the option in the refusal."""
+    value = "fma" if value is None else value
+    if value not in TOWER_ATTENTIONS:
+        raise NotImplementedError(f"{where}={value!r} (have {list(TOWER_ATTENTIONS)})")
+    return value
+
+
+def check_mfma_head_dim(head_dim: int, where: str) -> None:
+    """a tower whose head dim ssr_mha_mfma_* do not take is refused by name, on the host, when the plan is built"""
+    if head_dim not in MFMA_HEAD_DIMS:
+        raise NotImplementedError(f"{where}: tower_attention 'mfma' takes head dims {list(MFMA_HEAD_DIMS)}, this tower has {head_dim}; use "
+                                  "tower_attention 'fma'")
 
 
 def split_pieces(t: torch.Tensor, pieces: str):

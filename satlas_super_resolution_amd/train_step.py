@@ -49,7 +49,8 @@ class StepConfig:
     optim_d: Optional[Dict] = None
     deterministic: bool = False    # fixed-order reductions only: two runs give bit-identical parameters (engine.deterministic; SSR_DETERMINISTIC=1)
     # train.clip_opt (CLIPLoss, ssr_esrgan_model.py:187-190; cliploss_esrgan_s2naip_urban.yml), as clip_loss.check_clip_opt returns it:
-    # {"model", "family", "path", "gelu", "loss_weight"} and, only when it is not the default 'exact', "tower_arithmetic": "split"
+    # {"model", "family", "path", "gelu", "loss_weight"} and, only when it is not the default 'exact', "tower_arithmetic": "split";
+    # likewise "tower_attention": "mfma" only when it is not the default 'fma'
     clip: Optional[Dict] = None
 
 
@@ -207,8 +208,9 @@ class ESRGANTrainStep:
                     raise NotImplementedError(f"train.clip_opt with world size {self.dp.world}: l_clip_sim is not part of the cross-rank "
                                               "reduction of the logged scalars; run it on one GPU")
                 arith = cfg.clip.get("tower_arithmetic", "exact")      # 'split': the tower's linears as ssr_linear_split (clip_loss.py)
-                cmodel = CL.ClipLossModel(clip_state, dev, cfg.clip.get("gelu", "tanh"), arith) if clip_state is not None else \
-                    CL.clip_loss_model(cfg.clip["path"], dev, cfg.clip.get("gelu", "tanh"), arith)
+                attn = cfg.clip.get("tower_attention", "fma")          # 'mfma': the blocks' attention as ssr_mha_mfma_fwd / _bwd
+                cmodel = CL.ClipLossModel(clip_state, dev, cfg.clip.get("gelu", "tanh"), arith, attn) if clip_state is not None else \
+                    CL.clip_loss_model(cfg.clip["path"], dev, cfg.clip.get("gelu", "tanh"), arith, attn)
                 self.clip_loss = torch.zeros(self.loss_stride, dtype=torch.float32, device=dev)      # the rule of the other loss scalars
                 self.c_plan = CL.ClipLossPlan(cmodel, B, H, W, view(self.fake_in), view(self.l1_tgt), view(self.grad_l1),
                                               self.clip_loss.data_ptr(), float(cfg.clip.get("loss_weight", 1.0)),

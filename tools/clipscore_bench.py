@@ -1,9 +1,9 @@
 """Time of one CLIPScore pair (two 128 x 128 images, one pass of batch 2) for both real-size towers with random weights
 (clipscore_metric.clip_random_state), HIP events, one process.
 
-    python tools/clipscore_bench.py [--towers siglip clip] [--tower-arithmetic exact split] [--iters 10] [--warmup 3] [--out FILE.json]
+    python tools/clipscore_bench.py [--towers siglip clip] [--tower-arithmetic exact split] [--tower-attention fma mfma] [--iters 10] [--warmup 3] [--out FILE.json]
 
-Prints one JSON line per tower and tower arithmetic: ms per pair (median, min, max), the FLOPs of the ssr_linear / ssr_linear_split
+Prints one JSON line per tower, tower arithmetic and tower attention (fma: ssr_mha_fwd | mfma: ssr_mha_mfma_fwd for the blocks): ms per pair (median, min, max), the FLOPs of the ssr_linear / ssr_linear_split
 launches of the plan (2 M K Nout each) and what share of the matrix-core ceiling (155 TFLOP/s fp32 MFMA for `exact`; 833 TFLOP/s =
 a third of the 16-bit rate for `split`, which spends three MFMAs per product) the WHOLE pair time would be if it were all linear
 launches (a lower bound of the kernel's own fraction: the kernel trace under profiles/clipscore/ splits the time by kernel)."""
@@ -24,6 +24,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--towers", nargs="+", default=["siglip", "clip"])
     ap.add_argument("--tower-arithmetic", nargs="+", default=["exact"], choices=["exact", "split"])
+    ap.add_argument("--tower-attention", nargs="+", default=["fma"], choices=["fma", "mfma"])
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--size", type=int, default=128)
@@ -35,10 +36,10 @@ def main():
     img = torch.randint(0, 256, (1, a.size, a.size, 3), generator=g, dtype=torch.uint8).cuda()
     img2 = torch.randint(0, 256, (1, a.size, a.size, 3), generator=g, dtype=torch.uint8).cuda()
     results = []
-    for family, arith in ((f, t) for f in a.towers for t in a.tower_arithmetic):
+    for family, arith, attn in ((f, t, m) for f in a.towers for t in a.tower_arithmetic for m in a.tower_attention):
         state = CM.clip_random_state(family, seed=1)
         cfg = CM.vit_config_from_state(state)
-        model = CM.CLIPVisualModel(state, "cuda", tower_arithmetic=arith)
+        model = CM.CLIPVisualModel(state, "cuda", tower_arithmetic=arith, tower_attention=attn)
         del state
         plan = model.plan(2, a.size, a.size)
         calls = list(plan.launcher.flat_calls())
@@ -56,7 +57,7 @@ def main():
             times.append(e0.elapsed_time(e1))
         times.sort()
         med = times[len(times) // 2]
-        r = {"tower": family, "tower_arithmetic": arith, "width": cfg["width"], "depth": cfg["depth"], "tokens": cfg["tokens"], "image_size": cfg["image_size"],
+        r = {"tower": family, "tower_arithmetic": arith, "tower_attention": attn, "width": cfg["width"], "depth": cfg["depth"], "tokens": cfg["tokens"], "image_size": cfg["image_size"],
              "pair_ms_median": round(med, 3), "pair_ms_min": round(times[0], 3), "pair_ms_max": round(times[-1], 3), "iters": a.iters,
              "launches": len(calls) + 1, "linear_launches": len(lin), "linear_gflop_per_pair": round(flops / 1e9, 2),
              "linear_tflops_if_all_time_were_linear": round(flops / (med * 1e-3) / 1e12, 2),
