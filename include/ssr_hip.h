@@ -165,6 +165,8 @@ int64_t ssr_conv2d_chain_state_bytes(int32_t N, int32_t Gh, int32_t Gw);
  * the argument list), e.g. "conv_x3r_kernel<1, 1, 0, 8, 2>" (NTW, NU, EP, TH, AM): the key under which bench.py, tools/pmc_traffic.py, tools/pmc_sq.py and
  * tools/roofline_check.py file a launch, so that roofline.kernel can be found in profiles/ by name.  buflen >= 48. */
 int ssr_conv2d_symbol(const ssr_conv_desc* d, char* buf, int32_t buflen);
+/* the same for the launch of ssr_conv2d_impl(d, stream, impl): the symbol of a forced family (SSR_EUNSUP where the launch would be) */
+int ssr_conv2d_symbol_impl(const ssr_conv_desc* d, int32_t impl, char* buf, int32_t buflen);
 /* input channels per packed weight chunk for a KHxKH kernel in `dtype` */
 int ssr_conv2d_ck(int32_t dtype, int32_t KH);
 /* 1 if a 4x4 stride-2 layer of this shape can run through the space-to-depth path (ssr_conv_desc.s2d), else 0 */

@@ -960,15 +960,18 @@ extern "C" int ssr_conv2d_variant(const ssr_conv_desc* dp) {
 
 // The kernel symbol ssr_conv2d launches for this descriptor, as rocprofv3 prints it: the key of profiles/*_kernel_stats*.csv,
 // *_pmc_sq.json and traffic_*.json.  Exact for the kernels that carry the step, name + variant code for the older families.
-extern "C" int ssr_conv2d_symbol(const ssr_conv_desc* dp, char* buf, int32_t buflen) {
+// ssr_conv2d_symbol_impl: the same for a launch of ssr_conv2d_impl (tests/test_gpu_conv_exact.py ties every forced launch to its kernel).
+extern "C" int ssr_conv2d_symbol_impl(const ssr_conv_desc* dp, int32_t impl, char* buf, int32_t buflen) {
     if (!dp || !buf || buflen < 48) return SSR_EINVAL;
     const ssr_conv_family* fam;
     ssr_conv_desc d;
-    const int rc = select(*dp, 0, fam, d);
+    const int rc = select(*dp, impl, fam, d);
     if (rc != SSR_OK) return rc;
     fam->symbol(d, dp->KH * 1000 + dp->stride * 100 + fam->code(d), buf, buflen);
     return SSR_OK;
 }
+
+extern "C" int ssr_conv2d_symbol(const ssr_conv_desc* dp, char* buf, int32_t buflen) { return ssr_conv2d_symbol_impl(dp, 0, buf, buflen); }
 
 extern "C" int ssr_conv2d_ck(int32_t dtype, int32_t KH) {
     const int vec = dtype == SSR_BF16 ? 8 : 4;      // SSR_F32X3 packs like SSR_F32
