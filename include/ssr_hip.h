@@ -999,6 +999,48 @@ int64_t ssr_mha_mfma_bwd_ws_floats(int32_t N, int32_t Tq, int32_t heads);
 int ssr_mha_mfma_bwd(ssr_view q, ssr_view k, ssr_view v, ssr_view dy, ssr_view dq, ssr_view dk, ssr_view dv, float* ws, int32_t dtype,
                      int32_t N, int32_t Tq, int32_t Tk, int32_t heads, int32_t d, float scale, void* stream);
 
+/* ---- PNG decode on the device (csrc/png_decode.hip, csrc/png_inflate.h; `png_decode: device` of infer_grid; additive: the ABI
+ *      version stays 3) ----
+ * ssr_png_decode: n PNG images per launch, 8-bit grayscale (channels 1) or RGB (channels 3), not interlaced.  `streams` is one device
+ *   buffer of streams_len bytes holding the images' zlib streams (the concatenated IDAT payloads; the host parses the container),
+ *   `items` a device array: item i's stream is streams[src_off .. src_off + src_len), its pixels go to dst[dst_off .. dst_off + height
+ *   width channels) as tight [H][W][C] bytes, and its raw scanlines (height (width channels + 1) bytes, ssr_png_scratch_bytes rounded
+ *   to 16) may use scratch[raw_off ..).  Items' dst and scratch ranges must not overlap each other.  status[i] receives
+ *       0 ok, 1 truncated input, 2 bad zlib header (CM, window, FDICT, FCHECK), 3 bad block type, 4 bad stored LEN/NLEN, 5 bad code
+ *       lengths, 6 invalid symbol, 7 distance too far back, 8 output overrun (more than the raw image), 9 output short, 10 bad filter
+ *       byte, 11 Adler-32 mismatch, 12 bad descriptor (the item does not fit streams_len / dst_len / scratch_len, a size outside 1 ..
+ *       32768, channels not 1 or 3, more than 2^24 raw bytes: nothing of the item is read or written)
+ *   and 0 is the only success.  Whatever the stream holds, an item reads only its stream and writes only inside its own dst and
+ *   scratch ranges, and its decode ends: every step of the decoder consumes input or produces output.  A failed item's dst range
+ *   holds unspecified bytes.  Stored, fixed and dynamic blocks, distances up to 32768 (the window is the raw image itself),
+ *   incomplete code sets as zlib takes them (a single code of length 1; no distance code at all), over-subscribed sets refused.
+ *   One wave per item; lds_pool (0 .. ssr_png_lds_pool_max()) is the LDS a block gets beyond its code tables: an item's stream is
+ *   staged there when it fits and its raw scanlines live in the rest when they fit, otherwise global memory serves (same bytes
+ *   either way).  Two launches on the same input give the same bytes.
+ *   SSR_EINVAL: a null pointer, n <= 0, a negative length or lds_pool.  SSR_EUNSUP: n > 2^20, lds_pool above the maximum.  A refused
+ *   call launches nothing.
+ * ssr_png_decode_host: the same decoder (the same source text) on the CPU, every pointer a host pointer; the twin of the CPU tests.
+ * ssr_stack_zero_scan: over B decoded stacks uint8 [T_b][32][32][3] at buf[offs[b] ..) (offs, T: device arrays), has_zero[b][t] = 1
+ *   where frame t holds a zero sample, 0 where it does not and for t >= T_b (has_zero: uint8 [B][Tmax]; the rule of select_frames /
+ *   format_s2naip_data).  A stack that does not lie inside buf_len, or with T_b > Tmax, reads nothing and gives zeros.
+ * ssr_stack_gather: out uint8 [B][n][32][32][3] = frames frame_ids[b][k] of stack b, first uint8 [B][32][32][3] = frame 0 of every
+ *   stack.  A frame id outside 0 .. T_b - 1 or a stack outside buf_len makes its copy a no-op.
+ *   Both: SSR_EINVAL for a null pointer or a size <= 0, SSR_EUNSUP above 2^30 (stack, frame) pairs. */
+typedef struct ssr_png_item {
+    int64_t src_off, dst_off, raw_off;
+    int32_t src_len, width, height, channels;
+} ssr_png_item;
+int64_t ssr_png_scratch_bytes(int32_t width, int32_t height, int32_t channels);
+int32_t ssr_png_lds_pool_max(void);
+int ssr_png_decode(const uint8_t* streams, int64_t streams_len, const ssr_png_item* items, int32_t n, uint8_t* dst, int64_t dst_len,
+                   uint8_t* scratch, int64_t scratch_len, int32_t* status, int32_t lds_pool, void* stream);
+int ssr_png_decode_host(const uint8_t* streams, int64_t streams_len, const ssr_png_item* items, int32_t n, uint8_t* dst, int64_t dst_len,
+                        uint8_t* scratch, int64_t scratch_len, int32_t* status);
+int ssr_stack_zero_scan(const uint8_t* buf, int64_t buf_len, const int64_t* offs, const int32_t* T, int32_t B, int32_t Tmax,
+                        uint8_t* has_zero, void* stream);
+int ssr_stack_gather(const uint8_t* buf, int64_t buf_len, const int64_t* offs, const int32_t* T, const int32_t* frame_ids, int32_t B,
+                     int32_t n, uint8_t* out, uint8_t* first, void* stream);
+
 /* library / device info: writes "gfx950 CUs=256 ..." style text */
 int ssr_device_info(char* buf, int32_t buflen);
 int ssr_abi_version(void);

@@ -158,6 +158,11 @@ class AttnDesc(C.Structure):
                 ("dgamma", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class PngItem(C.Structure):
+    _fields_ = [("src_off", C.c_int64), ("dst_off", C.c_int64), ("raw_off", C.c_int64),
+                ("src_len", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32)]
+
+
 # every symbol include/ssr_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "ssr_conv2d", "ssr_conv2d_fixup", "ssr_conv2d_batch", "ssr_conv2d_impl", "ssr_conv2d_variant", "ssr_conv2d_symbol", "ssr_conv2d_symbol_impl", "ssr_conv2d_chain", "ssr_conv2d_chain_ok", "ssr_conv2d_chain_state_bytes", "ssr_conv2d_ck", "ssr_conv2d_s2d_ok", "ssr_rdb_forward", "ssr_rdb_backward", "ssr_rdb_tile_of", "ssr_conv2d_wgrad", "ssr_wgrad_reduce", "ssr_wgrad_tiles", "ssr_wgrad_ci_tile", "ssr_wgrad_co_tile", "ssr_pack_weights", "ssr_pack_dgrad_gather", "ssr_add_views", "ssr_nchw_to_nhwc", "ssr_nhwc_to_nchw",
@@ -184,6 +189,7 @@ ABI_SYMBOLS = [
     "ssr_mha_bwd", "ssr_feature_l1",
     "ssr_linear_split_pack_bytes", "ssr_linear_split_pack", "ssr_linear_split",
     "ssr_mha_mfma_fwd", "ssr_mha_mfma_bwd_ws_floats", "ssr_mha_mfma_bwd",
+    "ssr_png_scratch_bytes", "ssr_png_lds_pool_max", "ssr_png_decode", "ssr_png_decode_host", "ssr_stack_zero_scan", "ssr_stack_gather",
     "ssr_device_info", "ssr_abi_version",
 ]
 VIT_ACTS = {"none": 0, "quick_gelu": 1, "gelu_tanh": 2, "gelu_erf": 3}      # SSR_VIT_ACT_*: `act` of ssr_linear (csrc/vit.hip)
@@ -321,12 +327,18 @@ def lib() -> C.CDLL:
     l.ssr_mha_mfma_fwd.argtypes = l.ssr_mha_fwd.argtypes
     l.ssr_mha_mfma_bwd_ws_floats.argtypes = [i32, i32, i32]
     l.ssr_mha_mfma_bwd.argtypes = l.ssr_mha_bwd.argtypes
+    l.ssr_png_scratch_bytes.argtypes = [i32, i32, i32]
+    l.ssr_png_lds_pool_max.argtypes = []
+    l.ssr_png_decode.argtypes = [vp, i64, vp, i32, vp, i64, vp, i64, vp, i32, vp]
+    l.ssr_png_decode_host.argtypes = [vp, i64, vp, i32, vp, i64, vp, i64, vp]
+    l.ssr_stack_zero_scan.argtypes = [vp, i64, vp, vp, i32, i32, vp, vp]
+    l.ssr_stack_gather.argtypes = [vp, i64, vp, vp, vp, i32, i32, vp, vp, vp]
     l.ssr_device_info.argtypes = [C.c_char_p, i32]
     l.ssr_abi_version.argtypes = []
     for s in ABI_SYMBOLS:
         getattr(l, s).restype = i64 if s in ("ssr_conv2d_chain_state_bytes", "ssr_sr_tail_scratch_bytes", "ssr_self_attention_save_floats",
                                               "ssr_self_attention_scratch_floats", "ssr_mha_bwd_ws_floats",
-                                              "ssr_linear_split_pack_bytes", "ssr_mha_mfma_bwd_ws_floats") else i32
+                                              "ssr_linear_split_pack_bytes", "ssr_mha_mfma_bwd_ws_floats", "ssr_png_scratch_bytes") else i32
     _lib = l
     return l
 

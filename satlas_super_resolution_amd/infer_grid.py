@@ -9,7 +9,11 @@ stitched_sr.png 2048x2048 and stitched_s2.png 512x512 per complete tile).  What 
 chunk at a time through the network; here the chunk list is sharded over the ranks (rank r takes chunks r, r + world, ...: no
 collective on the data path), every rank runs its share in batches through the HIP generator, quantises on the
 device (truncating uint8, infer_grid.py:60-64) and writes its own PNGs; rank 0 stitches after a barrier.
-`compute_dtype` in the option file (our extension; default fp32h = the all-gates mode; its forward runs at fp32x3 speed) selects the arithmetic; `batch` the chunk batch."""
+`compute_dtype` in the option file (our extension; default fp32h = the all-gates mode; its forward runs at fp32x3 speed) selects the arithmetic; `batch` the chunk batch.
+`png_decode` (our extension; `host`, the default, or `device`): where the input PNGs are decoded.  `device`: this process reads the
+file bytes and parses the PNG container on a few threads, the streams of a batch are inflated and unfiltered on the device one batch
+ahead on a side stream (png_device.py, csrc/png_decode.hip), the zero test and the frame gather run on the decoded stacks there;
+frames are still drawn here from `random` in listing order, so a seeded run picks the same frames and writes the same bytes."""
 from __future__ import annotations
 
 import argparse
@@ -52,8 +56,13 @@ def run_infer_grid(opt: Dict, model: Optional[Callable[[torch.Tensor], torch.Ten
                    device=None, barrier: Callable[[], None] = lambda: None) -> Dict[str, int]:
     from .utils.infer_utils import frames_to_input, quantize_output, select_frames
     data_dir, n_lr_images, save_path = opt["data_dir"], opt["n_lr_images"], opt["save_path"]
+    png_decode = opt.get("png_decode", "host")
+    if png_decode not in ("host", "device"):
+        raise ValueError(f"png_decode: {png_decode!r} (host or device)")
     if device is None:
         device = torch.device("cuda")
+    if png_decode == "device" and torch.device(device).type != "cuda":
+        raise ValueError("png_decode: device needs the GPU")
     if model is None:
         model = load_generator(opt, device)
     pngs = sorted(glob.glob(data_dir + "/**/*.png", recursive=True))      # sorted: every rank must see the same order
@@ -122,7 +131,7 @@ def run_infer_grid(opt: Dict, model: Optional[Callable[[torch.Tensor], torch.Ten
     with contextlib.ExitStack() as _stack:
         _stack.callback(lambda: [b.close() for b in blocks])          # registered first: runs after the pool has shut down
         pool = _stack.enter_context(png_io.shared_pool(workers))      # the workers stay up for the next call of this process
-        in_blocks = [new_block(batch * SLOT, f"in{k}") for k in range(NIN)]
+        in_blocks = [new_block(batch * SLOT, f"in{k}") for k in range(NIN)] if png_decode == "host" else []
         out_blocks = [new_block(out_bytes, f"out{k}") for k in range(NOUT)]
         out_busy = [[] for _ in range(NOUT)]      # save tasks that still read the block
 
@@ -164,6 +173,63 @@ def run_infer_grid(opt: Dict, model: Optional[Callable[[torch.Tensor], torch.Ten
                     dst_np[k], first = select_frames(a, n_lr_images)
                     firsts.append(np.array(first))
             return firsts, dst
+
+        if png_decode == "device":
+            # the decode moves to the device: threads of this process read and parse (file reads and zlib.crc32 release the GIL), the
+            # worker processes keep encoding.  read_group: the reads of a batch; prep: its decode enqueued on the side stream, then - the
+            # statuses and has_zero [B, T] down - the same `random` calls in the same order as above, the ids up, the gather
+            from concurrent.futures import ThreadPoolExecutor
+            from . import png_device
+            readers = _stack.enter_context(ThreadPoolExecutor(max_workers=max(2, min(8, png_io.host_cores() // max(1, world)))))
+            side = torch.cuda.Stream(device=device)
+
+            def load(path):
+                with open(path, "rb") as f:
+                    info = png_device.parse_png(f.read())
+                if info.reason is None and info.channels == 3:
+                    return info, None
+                # every kind the device decoder does not take (palette, alpha, 16-bit, interlaced; grayscale, which the host reader
+                # expands to RGB): the host reader's pixels go up into the file's slot
+                return info._replace(stream=b"", reason=info.reason or "grayscale"), _read_png(path)
+
+            def read_group(g):
+                return [readers.submit(load, pngs[i]) for i in groups[g]]
+
+            class _Firsts:
+                """frame 0 of every stack of a batch, on its way down with the batch (read after the batch's event)"""
+
+                def __init__(self, pinned_firsts):
+                    self.t = pinned_firsts
+
+                def __getitem__(self, k):
+                    return np.array(self.t[k].numpy())
+
+            def prep(rd):
+                g = prep_n[0]
+                prep_n[0] += 1
+                res = [f.result() for f in rd]
+                with torch.cuda.stream(side):
+                    b = png_device.launch_decode([pngs[i] for i in groups[g]], [r[0] for r in res], [r[1] for r in res], device,
+                                                 scan_frames=True)
+                b.wait()                              # PngDecodeError before anything of the batch is used
+                has_zero = b.has_zero_host.numpy().astype(bool)
+                ids = torch.empty(len(res), n_lr_images, dtype=torch.int32, pin_memory=True)
+                ids_np = ids.numpy()
+                for k, T in enumerate(b.T):
+                    clean = np.flatnonzero(~has_zero[k, :T]).tolist()
+                    if len(clean) >= n_lr_images:
+                        chosen = random.sample(clean, n_lr_images)
+                    else:
+                        chosen = clean + random.sample(np.flatnonzero(has_zero[k, :T]).tolist(), n_lr_images - len(clean))
+                    ids_np[k] = chosen
+                main = torch.cuda.current_stream()
+                main.wait_stream(side)
+                for t in (b.buf, b.offs_dev, b.T_dev):
+                    t.record_stream(main)
+                sel, first = png_device.stack_gather(b.buf, b.offs_dev, b.T_dev, ids.to(device, non_blocking=True))
+                fh = torch.empty(first.shape, dtype=torch.uint8, pin_memory=True)
+                fh.copy_(first, non_blocking=True)
+                return _Firsts(fh), sel
 
         compute_dtype = getattr(model, "compute_dtype", None)
 
