@@ -617,6 +617,32 @@ int ssr_scene_blend_add_tf(ssr_view src, int32_t dtype, const int32_t* origins, 
 int ssr_scene_blend_finish_scaled(const uint32_t* acc, const int32_t* Sy, const int32_t* Sx, int32_t C, int32_t scale, uint8_t* mosaic,
                                   int32_t Ho, int32_t Wo, void* stream);
 
+/* ---- scene inference from raw Sentinel-2 L1C: reprojection onto the grid (csrc/reproject.hip; additive: the ABI version stays 3) ----
+ * The model's grid is Web-Mercator at 2 pi R / 2^22 m per pixel (R = 6378137), global pixel (px, py) from x = -pi R, y = +pi R, py
+ * southwards; ESA's rasters are UTM.  satlas_super_resolution_amd/s2_reproject.py states every formula (`source_coords`,
+ * `warp_bilinear`); these two entries compute them on the device.
+ * ssr_merc_to_utm_coords: coords is a DEVICE array int32 [h][w][2], 8-byte aligned.  For the CENTRE of pixel (px0 + j, py0 + i) of
+ *   the window: longitude and latitude (lat = atan(sinh(y / R))), then easting E and northing N in the WGS84 UTM zone of `epsg` by
+ *   the Krueger series through n^6 (k0 = 0.9996, false easting 500 000, false northing 10 000 000 for 327zz, central meridian
+ *   6 zone - 183), all in fp64; u = (E - ulx) / xdim - 0.5, v = (N - uly) / ydim - 0.5;
+ *     coords[i][j] = (floor(u 65536 + 0.5), floor(v 65536 + 0.5))   where -0.5 <= u < cols - 0.5 and -0.5 <= v < rows - 0.5,
+ *     coords[i][j] = (INT32_MIN, INT32_MIN)                         elsewhere (the sentinel).
+ *   SSR_EINVAL: a null or misaligned coords, w, h, rows or cols <= 0, a negative px0 / py0 or a window that leaves the 2^22 grid,
+ *   xdim <= 0, ydim >= 0, a non-finite ulx / uly / xdim / ydim.  SSR_EUNSUP: an epsg outside 32601 .. 32660 and 32701 .. 32760, w or
+ *   h above 4096, rows or cols above 32767 (the coordinates would not fit the 16.16 words).
+ * ssr_scene_warp_bilinear: src uint8 [T][Hs][Ws][C], C = 1 or 3, ANY address (no alignment is assumed); coords as above, shared
+ *   by the T frames; dst uint8 [T][h][w][C].  x0 = U >> 16 (arithmetic), fx = U & 0xffff, likewise y; the four neighbours are
+ *   clamped into the raster, so no coordinate makes the kernel read outside src;
+ *     dst = ((65536 - fx)(65536 - fy) p00 + fx (65536 - fy) p10 + (65536 - fx) fy p01 + fx fy p11 + 2^31) >> 32   in 64-bit integers,
+ *   0 in every channel at the sentinel.  mode 0 (blend): that; mode 1 (propagate): a pixel one of whose neighbours with NON-ZERO
+ *   weight has a zero among its C samples is 0 in every channel.  Every pixel is written whole by one thread, nothing is
+ *   accumulated: a second launch writes the same bytes.  SSR_EINVAL: a null pointer, a misaligned coords, a size <= 0, another
+ *   mode.  SSR_EUNSUP: C not 1 or 3, w or h above 4096, Hs or Ws above 32767, T above 65535. */
+int ssr_merc_to_utm_coords(int32_t px0, int32_t py0, int32_t w, int32_t h, int32_t epsg, double ulx, double uly, double xdim,
+                           double ydim, int32_t rows, int32_t cols, int32_t* coords, void* stream);
+int ssr_scene_warp_bilinear(const uint8_t* src, int32_t T, int32_t Hs, int32_t Ws, int32_t C, const int32_t* coords, int32_t h,
+                            int32_t w, int32_t mode, uint8_t* dst, void* stream);
+
 /* ---- VGG19 perceptual loss glue (csrc/vgg.hip; the convolutions run through ssr_conv2d with SSR_ACT_RELU / m_relu) ----
  * ssr_channel_affine: y[p, c] (+)= x[p, c] * scale[c] + shift[c] for c < C <= 8 (host float arrays, copied into the launch):
  *   the input normalisation (x - mean) / std of the feature extractor and, with accumulate = 1, its adjoint.

@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["conv.hip", "conv_res.hip", "conv_ws.hip", "conv_big.hip", "conv_big_x3.hip", "conv_x3q.hip", "conv_x3r.hip", "conv_x3c.hip", "conv_thin.hip", "rdb_fwd.hip", "rdb_tile.hip", "wgrad.hip", "wgrad_bf16.hip", "wgrad_x3.hip", "misc.hip", "losses.hip", "ssim.hip", "metrics.hip", "vgg.hip", "gram.hip", "finite.hip", "optim.hip", "scene.hip", "lpips.hip", "conv_direct.hip", "l2net.hip", "attention.hip", "obj_crop.hip", "vit.hip", "vit_bwd.hip", "linear_split.hip", "mha_mfma.hip", "png_decode.hip"]
+SOURCES = ["conv.hip", "conv_res.hip", "conv_ws.hip", "conv_big.hip", "conv_big_x3.hip", "conv_x3q.hip", "conv_x3r.hip", "conv_x3c.hip", "conv_thin.hip", "rdb_fwd.hip", "rdb_tile.hip", "wgrad.hip", "wgrad_bf16.hip", "wgrad_x3.hip", "misc.hip", "losses.hip", "ssim.hip", "metrics.hip", "vgg.hip", "gram.hip", "finite.hip", "optim.hip", "scene.hip", "lpips.hip", "conv_direct.hip", "l2net.hip", "attention.hip", "obj_crop.hip", "vit.hip", "vit_bwd.hip", "linear_split.hip", "mha_mfma.hip", "png_decode.hip", "reproject.hip"]
 OUT = os.path.join(HERE, "libssr_hip.so")
 
 

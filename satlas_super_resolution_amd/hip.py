@@ -178,6 +178,7 @@ ABI_SYMBOLS = [
     "ssr_scene_frame_keys", "ssr_scene_rank_frames",
     "ssr_scene_support_add", "ssr_scene_apply_nodata",
     "ssr_scene_gather_tf", "ssr_scene_blend_add_tf", "ssr_scene_blend_finish_scaled",
+    "ssr_merc_to_utm_coords", "ssr_scene_warp_bilinear",
     "ssr_lpips_input", "ssr_lpips_layer_blocks", "ssr_lpips_layer",
     "ssr_conv_direct", "ssr_maxpool3s2_fwd",
     "ssr_prelu_reflect_fwd", "ssr_prelu_reflect_bwd", "ssr_sr_tail_fwd", "ssr_sr_tail_bwd", "ssr_sr_tail_scratch_bytes",
@@ -286,6 +287,8 @@ def lib() -> C.CDLL:
     l.ssr_scene_gather_tf.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, View, i32, vp]
     l.ssr_scene_blend_add_tf.argtypes = [View, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp]
     l.ssr_scene_blend_finish_scaled.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp]
+    l.ssr_merc_to_utm_coords.argtypes = [i32, i32, i32, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp]
+    l.ssr_scene_warp_bilinear.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp]
     l.ssr_lpips_input.argtypes = [vp, View, i32, i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(i32), i32, vp]
     l.ssr_lpips_layer_blocks.argtypes = [i32, i32, i32]
     l.ssr_lpips_layer.argtypes = [View, View, vp, i32, i32, i32, i32, i32, vp, vp]

@@ -18,7 +18,7 @@ straight from the plan's output into the mosaic, and the count of non-finite out
 
 Option keys: `data_dir`, `save_path`, `n_lr_images`, `network_g`, `path.*`, `compute_dtype` (default fp32h), `batch` (chunks per
 generator launch, default 64), `io_workers` as `infer_grid`; `scene_hw: [H, W]` for PNG scenes that are not square; `overlap`;
-`s2_bands`; `frame_select`; `nodata`, `nodata_min_support`; `self_ensemble`.
+`s2_bands`; `frame_select`; `nodata`, `nodata_min_support`; `self_ensemble`; `source`, `window`, `reproject_nodata`.
 
 `overlap: K` (0 .. 16; absent: the path above, unchanged) takes scenes of ANY height and width >= 32 instead: chunks overlap their
 neighbours by K pixels, the last chunk of a row or column ends at the scene's edge, and the super-resolved chunks are cross-faded
@@ -68,7 +68,21 @@ slices that list, so a scene takes eight times the generator time; the frames of
 `ssr_scene_gather_tf` writes a transformed chunk into the plan's input, `ssr_scene_blend_add_tf` turns the output back while it
 accumulates, `ssr_scene_blend_finish_scaled` divides.  Integer sums: the bytes do not depend on `batch`, and with `frame_select:
 clearest` and chunk origins symmetric about the centre the mosaic of a flipped or transposed scene is the flipped or transposed mosaic,
-byte for byte."""
+byte for byte.
+
+`source: sentinel2_l1c` (absent: every path above, launch for launch; nothing new runs) starts from what ESA ships instead of stacks
+that already lie on the grid: a scene is the DIRECTORY `{data_dir}/NAME/` of T products sorted by name - `.SAFE` directories (their
+`*_TCI.jp2` under GRANULE/*/IMG_DATA/, georeferenced by GRANULE/*/MTD_TL.xml) or raster files (.jp2 / .tif / .png / .npy) with a
+sidecar NAME.json - in UTM.  `window: {tile: "COL_ROW", zoom: 13 | 17} | {pixels: [px0, py0, w, h]} | {bbox: [lon_min, lat_min,
+lon_max, lat_max]}` names the pixels of the model's Web-Mercator grid to produce (multiples of 32, at most 4096 per side);
+`reproject_nodata: blend | propagate` (default `blend`) is what a zero sample does in the bilinear warp.  `s2_reproject.py` states the
+grid, the projection and the warp for the CPU and is their definition - the bytes are NOT GDAL's, which the reference's pseudo-code
+would call.  Per scene the `png_io` workers decode the rasters (Pillow: JPEG 2000, TIFF) and keep only the rectangle the window
+needs; on the device `ssr_merc_to_utm_coords` computes one coordinate array per distinct georeference and `ssr_scene_warp_bilinear`
+warps the frames into one tensor uint8 [T, h, w, 3], which goes to the paths above as it is (`reproject_scene` in Python).  It works
+with `overlap`, `frame_select`, `nodata` and `self_ensemble`; `s2_bands` beside it is refused by name (the 16-bit band files are out
+of scope).  `stitched_s2.png` is the reprojected frame 0; `stitched_sr.json` / `stitched_s2.json` hold EPSG 3857, the upper-left
+corner in metres, the pixel size and the window in global pixels."""
 from __future__ import annotations
 
 import argparse
@@ -366,6 +380,36 @@ def band_scene_shape(tci_path: str, band_paths: Sequence[Optional[str]]) -> Tupl
     return rows, W
 
 
+SOURCES = ("sentinel2_l1c",)
+
+
+def check_source(source, s2_bands=None) -> Optional[str]:
+    """the refusals of the `source` option, on the host: a value other than `sentinel2_l1c`; `s2_bands` beside it (the 16-bit band
+    files and their / 8160 scaling are out of scope)"""
+    if source is None:
+        return None
+    if source not in SOURCES:
+        raise ValueError(f"source = {source!r}: one of {', '.join(SOURCES)} (absent: scenes that already lie on the grid)")
+    if s2_bands is not None:
+        raise ValueError(f"s2_bands = {list(s2_bands)} with source: {source}: the 16-bit band files of an L1C product are not read; "
+                         "this source takes the TCI alone")
+    return source
+
+
+def list_product_scenes(data_dir: str) -> List[Tuple[str, List[str]]]:
+    """[(NAME, its products sorted by name)] of the scene directories `data_dir/NAME/` that hold at least one product (a `.SAFE`
+    directory or a raster file with its sidecar), sorted by NAME"""
+    from .s2_reproject import list_products
+    out = []
+    for name in sorted(os.listdir(data_dir)):
+        d = os.path.join(data_dir, name)
+        if os.path.isdir(d) and not name.upper().endswith(".SAFE"):
+            products = list(list_products(d))
+            if products:
+                out.append((name, products))
+    return out
+
+
 def scenes_of_rank(scenes: Sequence, rank: int, world: int) -> List:
     """rank r takes scenes r, r + world, ... of the sorted list (no collective, no barrier: every scene is one rank's own)"""
     return list(scenes[rank::world])
@@ -647,6 +691,91 @@ def scene_blend_finish_scaled(acc: torch.Tensor, Sy: torch.Tensor, Sx: torch.Ten
     _blend_finish(acc, Sy, Sx, mosaic, int(scale))
 
 
+def merc_to_utm_coords(window, georef, device=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`s2_reproject.source_coords` on the device (`ssr_merc_to_utm_coords`): window (a Window or a window mapping) and georef (a
+    Georef or its mapping) -> int32 [h, w, 2] on the device, (U, V) of every pixel centre in 16.16 fixed point, INT32_MIN in both
+    words outside the raster.  The same refusals as the statement, on the host, before the launch."""
+    from . import hip, s2_reproject as S
+    win, g = S.parse_window(window), S.check_georef(georef)
+    if out is None:
+        out = torch.empty(win.h, win.w, 2, dtype=torch.int32, device=torch.device("cuda") if device is None else device)
+    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (win.h, win.w, 2), (out.dtype, out.shape)
+    hip.check(hip.lib().ssr_merc_to_utm_coords(win.px0, win.py0, win.w, win.h, g.epsg, g.ulx, g.uly, g.xdim, g.ydim, g.rows, g.cols,
+                                               _ptr(out), hip.stream_ptr()), "ssr_merc_to_utm_coords")
+    return out
+
+
+def scene_warp(src: torch.Tensor, coords: torch.Tensor, nodata: str = "blend", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`s2_reproject.warp_bilinear` on the device (`ssr_scene_warp_bilinear`): src uint8 [T, Hs, Ws, C] (C = 1 or 3, any address) and
+    coords int32 [h, w, 2] (`merc_to_utm_coords`), both on the device -> uint8 [T, h, w, C] on the device; every frame reads the one
+    coordinate array.  nodata: "blend" or "propagate", as the statement."""
+    from . import hip, s2_reproject as S
+    if nodata not in S.NODATA_MODES:
+        raise ValueError(f"reproject_nodata = {nodata!r}: one of {', '.join(S.NODATA_MODES)}")
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 4 and src.shape[3] in (1, 3) \
+        and src.numel() > 0, (src.dtype, src.shape)
+    assert coords.is_cuda and coords.dtype == torch.int32 and coords.is_contiguous() and coords.dim() == 3 and coords.shape[2] == 2 \
+        and coords.numel() > 0, (coords.dtype, coords.shape)
+    T, Hs, Ws, C = src.shape
+    h, w = coords.shape[:2]
+    if max(h, w) > S.MAX_WINDOW or max(Hs, Ws) > S.MAX_RASTER:
+        raise ValueError(f"a warp of a {Hs} x {Ws} source into {h} x {w} pixels: at most {S.MAX_RASTER} and {S.MAX_WINDOW} per side")
+    if out is None:
+        out = torch.empty(T, h, w, C, dtype=torch.uint8, device=src.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (T, h, w, C), (out.dtype, out.shape)
+    hip.check(hip.lib().ssr_scene_warp_bilinear(_ptr(src), T, Hs, Ws, C, _ptr(coords), h, w, S.NODATA_MODES.index(nodata), _ptr(out),
+                                                hip.stream_ptr()), "ssr_scene_warp_bilinear")
+    return out
+
+
+def reproject_scene(rasters, georefs, window, nodata: str = "blend", device=None) -> torch.Tensor:
+    """Raw Sentinel-2 frames onto the model's grid, on the device: rasters, T uint8 arrays [Hs, Ws, 3] (numpy; each frame its own
+    size), georefs, their T georeferences (`s2_reproject.Georef` or its mapping: UTM, `ulx` / `uly` the outer corner of the array's
+    first pixel), window (a window mapping, `s2_reproject.parse_window`) -> uint8 [T, h, w, 3] on the device, what
+    `super_resolve_scene(_blended)` take as `frames`.  `s2_reproject.py` states the result (`source_coords`, `warp_bilinear`); it is
+    not GDAL's.
+    Of every raster only the rectangle the window needs (`source_crop`, padded by 2 pixels) is uploaded, with its own georeference;
+    frames whose crops share a georeference and a size are stacked and warped by ONE launch from ONE coordinate array; a frame the
+    window misses altogether stays 0.  nodata: "blend" (plain bilinear) or "propagate" (a zero sample with non-zero weight makes the
+    pixel NODATA)."""
+    from . import s2_reproject as S
+    win = S.parse_window(window)
+    if nodata not in S.NODATA_MODES:
+        raise ValueError(f"reproject_nodata = {nodata!r}: one of {', '.join(S.NODATA_MODES)}")
+    rasters, georefs = list(rasters), [S.check_georef(g) for g in georefs]
+    if not rasters or len(rasters) != len(georefs):
+        raise ValueError(f"{len(rasters)} rasters with {len(georefs)} georeferences")
+    crops: List[Optional[np.ndarray]] = []
+    crop_georefs: List[Optional[S.Georef]] = []
+    for t, (a, g) in enumerate(zip(rasters, georefs)):
+        a = np.asarray(a)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[:2] != (g.rows, g.cols):
+            raise ValueError(f"raster {t}: a uint8 array [{g.rows}, {g.cols}, 3] by its georeference, not {a.dtype} {tuple(a.shape)}")
+        box = S.source_crop(win, g)
+        crops.append(None if box is None else a[box[1]:box[3], box[0]:box[2]])
+        crop_georefs.append(None if box is None else S.crop_georef(g, box))
+    return _warp_crops(crops, crop_georefs, win, nodata, torch.device("cuda") if device is None else device)
+
+
+def _warp_crops(crops, crop_georefs, win, nodata: str, dev) -> torch.Tensor:
+    """the device half of `reproject_scene`: the frames' crops (uint8 [Hc, Wc, 3] on the host, or None for a frame the window
+    misses) with their own georeferences -> uint8 [T, h, w, 3] on the device.  Frames that share a georeference are stacked,
+    uploaded once and warped by one launch from one coordinate array."""
+    groups: Dict = {}
+    for t, g in enumerate(crop_georefs):
+        if g is not None:
+            groups.setdefault(g, []).append(t)
+    out = torch.zeros(len(crops), win.h, win.w, 3, dtype=torch.uint8, device=dev)
+    for g, ts in groups.items():
+        src = torch.from_numpy(np.stack([crops[t] for t in ts])).to(dev)
+        coords = merc_to_utm_coords(win, g, dev)
+        if ts == list(range(ts[0], ts[0] + len(ts))):
+            scene_warp(src, coords, nodata, out[ts[0]:ts[0] + len(ts)])          # a run of frames: straight into its place
+        else:
+            out[torch.tensor(ts, device=dev)] = scene_warp(src, coords, nodata)
+    return out
+
+
 class _Pending:
     """a scene whose launches are queued: the pinned host buffer its mosaic and counter (under `nodata: keep` the support map
     behind them) are being copied to, and the event behind that copy"""
@@ -921,13 +1050,24 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
     nodata, min_support = check_nodata(opt.get("nodata", "fill"), opt.get("nodata_min_support", 1))      # absent: fill, as ever
     keep = nodata == "keep"
     self_ensemble = check_self_ensemble(opt.get("self_ensemble", False))      # absent: false, the launches of the paths above
+    source = check_source(opt.get("source"), opt.get("s2_bands"))             # absent: scenes on the grid, nothing new runs
+    if source is not None:
+        from . import s2_reproject as S2
+        s2_window = S2.parse_window(opt.get("window"))
+        reproject_nodata = opt.get("reproject_nodata", "blend")
+        if reproject_nodata not in S2.NODATA_MODES:
+            raise ValueError(f"reproject_nodata = {reproject_nodata!r}: one of {', '.join(S2.NODATA_MODES)}")
     if device is None:
         device = torch.device("cuda")
     if model is None:
         model = load_generator(opt, device)
     s2_bands = opt.get("s2_bands")                  # absent: scene files NAME.png / NAME.npy; given: scene directories NAME/<band>.png
     K = 0 if s2_bands is None else len(order_s2_bands(s2_bands)) - 1
-    scenes = list_scenes(data_dir) if s2_bands is None else list_band_scenes(data_dir, s2_bands)
+    if source is not None:
+        scenes = list_product_scenes(data_dir)
+        png_io.check_raster_decoders([p for _, products in scenes for p in products])      # at start-up: names what Pillow lacks
+    else:
+        scenes = list_scenes(data_dir) if s2_bands is None else list_band_scenes(data_dir, s2_bands)
     if rank == 0:
         print("Running inference on ", len(scenes), " scenes.")
     mine = scenes_of_rank(scenes, rank, world)
@@ -957,6 +1097,8 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
 
         def start_read(k):
             """scene k's pixels on their way to host memory: a PNG is decoded by a worker into a one-shot block, a .npy is mapped"""
+            if source is not None:
+                return start_read_products(*mine[k])
             if s2_bands is not None:
                 return start_read_bands(*mine[k])
             name, path = mine[k]
@@ -977,7 +1119,35 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
                      for kb, p in enumerate(band_paths) if p is not None]
             return name, blk, futs, (rows, W, 3)
 
+        def start_read_products(name, products):
+            """a scene of raw products: per product the georeference (MTD_TL.xml or the sidecar), the source rectangle the window
+            needs, and a worker that decodes the raster and writes that rectangle into the scene's block"""
+            found = [S2.find_product(p) for p in products]
+            plan, off = [], 0
+            for f, g in found:
+                if png_io.raster_size(f) != (g.rows, g.cols):
+                    raise ValueError(f"{f}: {png_io.raster_size(f)} pixels, its georeference says {(g.rows, g.cols)}")
+                box = S2.source_crop(s2_window, g)
+                plan.append(None if box is None else (f, box, S2.crop_georef(g, box), off))
+                off += 0 if box is None else 3 * (box[2] - box[0]) * (box[3] - box[1])
+            blk = block(off, "scene") if off else None
+            futs = [pool.submit("read_crop_into", f, box, blk.path, blk.nbytes, o, True) for f, box, _, o in filter(None, plan)]
+            return name, blk, futs, plan
+
+        def finish_read_products(rd):
+            """the crops are in the block: upload, coordinates, warp - the scene as a device tensor [T, h, w, 3]"""
+            name, blk, futs, plan = rd
+            shapes = iter([f.result() for f in futs])
+            crops = []
+            for p in plan:
+                sh = None if p is None else next(shapes)
+                crops.append(None if p is None else blk.buf[p[3]:p[3] + int(np.prod(sh))].reshape(sh))
+            frames = _warp_crops(crops, [None if p is None else p[2] for p in plan], s2_window, reproject_nodata, device)
+            return name, blk, frames, None
+
         def finish_read(rd) -> Tuple[str, object, np.ndarray, Optional[np.ndarray]]:
+            if source is not None:
+                return finish_read_products(rd)
             name, blk, futs, what = rd
             if blk is None:
                 return name, None, parse_scene(np.asarray(what), scene_hw, blended), None
@@ -1007,13 +1177,16 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
             if k < len(mine):
                 name, blk, frames, bands = finish_read(reading)
                 reading = start_read(k + 1) if k + 1 < len(mine) else None
+                # the reprojected frame 0 comes back BEFORE the scene's launches are queued: the copy waits for the warp alone
+                first = frames[0].cpu().numpy() if source is not None else None
                 pending = _enqueue_scene(model, frames, n_lr_images, batch, hosts[k & 1], bands=bands, frame_select=frame_select,
                                          nodata=nodata, min_support=min_support, self_ensemble=self_ensemble, blended=blended,
                                          overlap=overlap)
                 hosts[k & 1] = pending.host
-                first = np.array(frames[0])
+                if first is None:
+                    first = np.array(frames[0])
                 del frames, bands
-                if frame_select == "random":
+                if frame_select == "random" or source is not None:      # (source: the crops were uploaded before frame 0 came back)
                     if blk is not None:
                         release(blk)                                # (the upload has been waited for: the flags came back)
                     blk = None
@@ -1027,6 +1200,12 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
                 saves.append(submit_save(first, os.path.join(save_path, pname, "stitched_s2.png")))
                 if keep:
                     saves.append(submit_save(ppend.support(), os.path.join(save_path, pname, "stitched_support.png")))
+                if source is not None:                              # what places the two mosaics in a GIS
+                    import json
+                    for stem, scale in (("stitched_sr", SCALE), ("stitched_s2", 1)):
+                        os.makedirs(os.path.join(save_path, pname), exist_ok=True)
+                        with open(os.path.join(save_path, pname, stem + ".json"), "w") as f:
+                            json.dump(S2.window_georef(s2_window, scale), f, indent=1)
                 chunks += ppend.chunks
             prev = cur
         for f in saves:
@@ -1037,6 +1216,8 @@ def run_infer_scene(opt: Dict, model=None, rank: int = 0, world: int = 1, device
         res.update(nodata=nodata, nodata_min_support=min_support)
     if self_ensemble:
         res.update(self_ensemble=True)
+    if source is not None:
+        res.update(source=source, window_pixels=list(s2_window), reproject_nodata=reproject_nodata)
     return res
 
 

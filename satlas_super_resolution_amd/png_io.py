@@ -223,6 +223,84 @@ def read_gray_into(path: str, shm_path: str, nbytes: int, offset: int, shape: Se
     return tuple(shape)
 
 
+def raster_decoders() -> dict:
+    """which of the decoders the Sentinel-2 source needs this Pillow build has: {"jpg_2000": bool, "libtiff": bool}"""
+    from PIL import features
+    return {c: bool(features.check_codec(c)) for c in ("jpg_2000", "libtiff")}
+
+
+def check_raster_decoders(paths: Sequence[str]) -> None:
+    """RuntimeError naming the decoder this Pillow build lacks for one of the products (JPEG 2000 for .jp2 and the TCI of a .SAFE
+    directory, libtiff for .tif)"""
+    have = raster_decoders()
+    need = {".jp2": "jpg_2000", ".safe": "jpg_2000", ".tif": "libtiff", ".tiff": "libtiff"}
+    for p in paths:
+        codec = need.get(os.path.splitext(p)[1].lower())
+        if codec is not None and not have[codec]:
+            raise RuntimeError(f"{p}: this Pillow build has no {codec} decoder (PIL.features.check_codec({codec!r}) is False)")
+
+
+class _pixel_limit:
+    """Pillow's decompression-bomb limit raised for the `with` block only (a 10980 x 10980 TCI has 120 M pixels, the default limit
+    warns at 89 M), and put back: nothing outside the block sees another limit"""
+
+    def __init__(self, pixels: int = 32767 * 32767):
+        self.pixels = pixels
+
+    def __enter__(self):
+        from PIL import Image
+        self.old = Image.MAX_IMAGE_PIXELS
+        if self.old is not None and self.old < self.pixels:
+            Image.MAX_IMAGE_PIXELS = self.pixels
+
+    def __exit__(self, *exc):
+        from PIL import Image
+        Image.MAX_IMAGE_PIXELS = self.old
+
+
+def raster_size(path: str) -> Tuple[int, int]:
+    """(rows, cols) of a raster file (.jp2 / .tif / .png: the header only; .npy: the mapped array's shape)"""
+    if path.lower().endswith(".npy"):
+        return tuple(np.load(path, mmap_mode="r").shape[:2])
+    from PIL import Image
+    with _pixel_limit(), Image.open(path) as im:
+        return im.size[1], im.size[0]
+
+
+def read_raster_crop(path: str, box: Sequence[int]) -> np.ndarray:
+    """the rectangle box = (x0, y0, x1, y1) of an 8-bit raster file as uint8 [y1 - y0, x1 - x0, 3] (gray becomes three equal
+    samples).  Pillow decodes the file whole; only the crop is kept."""
+    x0, y0, x1, y1 = (int(v) for v in box)
+    if path.lower().endswith(".npy"):
+        a = np.load(path, mmap_mode="r")
+        a = np.array(a[y0:y1, x0:x1])
+    else:
+        from PIL import Image
+        with _pixel_limit(), Image.open(path) as im:
+            if im.mode not in ("RGB", "L"):
+                raise ValueError(f"{path}: mode {im.mode!r}; an 8-bit RGB (or gray) raster is expected - the 16-bit band files are out "
+                                 "of scope")
+            a = np.asarray(im.crop((x0, y0, x1, y1)))
+    if a.ndim == 2:
+        a = np.repeat(a[:, :, None], 3, axis=2)
+    if a.dtype != np.uint8 or a.shape != (y1 - y0, x1 - x0, 3):
+        raise ValueError(f"{path}: crop {list(box)} came out as {a.dtype} {tuple(a.shape)}")
+    return a
+
+
+def read_crop_into(path: str, box: Sequence[int], shm_path: str, nbytes: int, offset: int, transient: bool = False):
+    """`read_raster_crop` into the block at `offset`; returns the crop's shape"""
+    a = read_raster_crop(path, box)
+    assert 0 <= offset and offset + a.nbytes <= nbytes, (offset, a.nbytes, nbytes)
+    e = _open_map(shm_path, nbytes) if transient else None
+    m = e[0] if transient else _map(shm_path, nbytes)
+    m[offset:offset + a.nbytes] = a.reshape(-1)
+    if transient:
+        del m
+        _close_map(e)
+    return tuple(a.shape)
+
+
 def save_from(shm_path: str, nbytes: int, items: Sequence[Tuple[int, Tuple[int, ...], str]], transient: bool = False) -> int:
     """encode and write the images that lie at (offset, shape) in the block.  transient: a one-shot block (a tile's mosaic) -
     mapped, encoded and unmapped here, so that the driver's unlink really frees it"""
@@ -246,7 +324,8 @@ def timed(name: str, *args):
 
 
 _TASKS = {"read_many": read_many, "save_many": save_many, "stitch_and_save": stitch_and_save, "stitch_from_dir": stitch_from_dir,
-          "read_into": read_into, "read_gray_into": read_gray_into, "save_from": save_from, "timed": timed}
+          "read_into": read_into, "read_gray_into": read_gray_into, "read_crop_into": read_crop_into, "save_from": save_from,
+          "timed": timed}
 
 
 class PngWorkerPool:
