@@ -21,8 +21,8 @@ launches has 4 x 16 tiles only where Gh > 4 (xr_tile_height), so "exactly one ti
 
 Not covered here:
   - the fused dense-block kernels rdb_fwd.hip and rdb_tile.hip: their intermediate activations pass through fl(0.2f v) and a bf16 store, so
-    later sums leave every lattice.  They stay held to the per-conv path by tests/test_gpu_rdb_tile.py and tests/test_gpu_parity.py, which
-    this file makes exact underneath;
+    a chain of five stages leaves every lattice.  tests/test_gpu_rdb_exact.py (over tests/rdb_lattice.py) holds them to exact sums one
+    stage at a time - the stages before the one under test hand over lattice values - and to float64 stage by stage on normal data;
   - conv_x3c (opt-in, held bit-identical to four launches by tests/test_gpu_conv_x3.py);
   - ssr_conv2d_fixup."""
 import pytest
