@@ -17,16 +17,11 @@ refused by name.  Statements that rest on open_clip behaviour that cannot be exe
     clip_loss_reference        the definition, differentiable (autograd), on clipscore_metric.vit_features_from_input
     clip_loss_grad_reference   the same loss and its image gradient in closed form, piece by piece as the kernels compute it
     check_clip_opt             the keys of a `train.clip_opt` block and its weights file (no device)
-    ClipLossModel / ClipLossPlan     the weights (and their transposes) on the device / the static launch lists (csrc/vit_bwd.hip)
+    ClipLossModel / ClipLossPlan     the weights (and their transposes) on the device / the static launch lists (vit_tower.py, csrc/vit_bwd.hip)
 
-`tower_arithmetic` ('exact', the default | 'split'; linear_split.py): under 'split' every matrix product of the tower runs as
-ssr_linear_split (csrc/linear_split.hip) - fp16 pieces in both forward passes, bf16 pieces in the backward's transposes - and
-clip_loss_grad_reference restates that on the CPU.
-
-`tower_attention` ('fma', the default | 'mfma'; csrc/mha_mfma.hip): under 'mfma' the blocks' self-attention of both forward passes and of
-the backward runs as ssr_mha_mfma_fwd / ssr_mha_mfma_bwd on the fp32-input matrix core - exact fp32 products, another order of
-additions, so the CPU statements above hold for it unchanged.  The pooling head (one query row) keeps ssr_mha_fwd / ssr_mha_bwd.
-Orthogonal to tower_arithmetic.
+`tower_arithmetic` ('exact' | 'split') and `tower_attention` ('fma' | 'mfma') are the tower's own, orthogonal options (vit_tower.py).  Under
+'split' the backward's transposes run as ssr_linear_split on bf16 pieces, which clip_loss_grad_reference restates on the CPU; under 'mfma'
+the blocks' attention backward is ssr_mha_mfma_bwd: exact fp32 products in another order of additions, so the CPU statements hold unchanged.
 """
 from __future__ import annotations
 
@@ -36,9 +31,9 @@ from typing import Dict, Tuple
 import torch
 import torch.nn.functional as F
 
-from .clipscore_metric import CLIP_MEAN, CLIP_STD, _GELUS, _attention, _flat_keys, nearest_index_table, vit_config_from_state, vit_features_from_input
-from .linear_split import (check_mfma_head_dim, check_split_domain, check_tower_arithmetic, check_tower_attention,  # noqa: F401
-                           linear_split_reference, pack_tower)                        # (linear_split_reference: re-exported)
+from .clipscore_metric import CLIP_MEAN, CLIP_STD, _GELUS, _attention, nearest_index_table, vit_config_from_state, vit_features_from_input
+from .linear_split import check_tower_arithmetic, check_tower_attention, linear_split_reference
+from .vit_tower import TowerPlan, TowerWeights
 
 CLIP_LOSS_MODELS = {"ViT-B-16-SigLIP-256": "siglip"}                                 # the reference's clip_loss_model -> family
 CLIP_LOSS_MEAN, CLIP_LOSS_STD = CLIP_MEAN["clip"], CLIP_STD["clip"]                    # OpenAI's, whatever the tower
@@ -253,48 +248,21 @@ def clip_loss_model(path: str, device, gelu: str = "tanh", tower_arithmetic: str
     return _LOSS_MODELS[key]
 
 
-_T_LEAVES = ("qkv", "proj", "fc1", "fc2")
-
-
-class ClipLossModel:
-    """The tower's weights on the device, fp32, as CLIPVisualModel holds them, plus one transposed copy `<name>.weight.t` of every
-    matrix the backward passes through (dX = dY W is ssr_linear on W^T's rows): made once at load, + 0.34 GB for ViT-B.
-    tower_arithmetic 'split': instead of both fp32 copies, every matrix is held as `<name>.weight.pk`, the packed fp16 pieces of W
-    (forward), and `<name>.weight.t.pk`, the packed bf16 pieces of W^T (backward), for ssr_linear_split; a matrix with max|w| >= 64
-    raises ValueError by name, on the host, before anything is loaded.  tower_attention changes no weight: it is what the plans of
-    this model launch for the blocks' self-attention."""
+class ClipLossModel(TowerWeights):
+    """A siglip tower's weights with what its backward reads (vit_tower.TowerWeights, backward=True); a `clip` tower is refused."""
 
     def __init__(self, state: Dict[str, torch.Tensor], device="cuda", gelu: str = "tanh", tower_arithmetic: str = "exact",
                  tower_attention: str = "fma"):
-        from . import hip
         if gelu not in _GELUS:
             raise NotImplementedError(f"train.clip_opt: gelu={gelu!r} (have {list(_GELUS)})")
-        self.tower_arithmetic = check_tower_arithmetic(tower_arithmetic, "train.clip_opt.tower_arithmetic")
-        self.tower_attention = check_tower_attention(tower_attention, "train.clip_opt.tower_attention")
-        self.cfg = vit_config_from_state(state)
-        if self.cfg["family"] != "siglip":
+        tower_arithmetic = check_tower_arithmetic(tower_arithmetic, "train.clip_opt.tower_arithmetic")
+        tower_attention = check_tower_attention(tower_attention, "train.clip_opt.tower_attention")
+        if vit_config_from_state(state)["family"] != "siglip":
             raise NotImplementedError("train.clip_opt: the backward of a `clip` tower (class token) is not built: no clip_loss_model needs it")
-        self.device, self.gelu = torch.device(device), gelu
-        for k in _flat_keys("siglip", self.cfg["depth"]):
-            if k not in state:
-                raise KeyError(k)
-        names = ["patch"] + [f"blocks.{i}.{leaf}" for i in range(self.cfg["depth"]) for leaf in _T_LEAVES] + \
-                [f"pool.{leaf}" for leaf in ("kv", "proj", "fc1", "fc2")]
-        if self.tower_arithmetic == "split":
-            check_split_domain([(f"{n}.weight", state[f"{n}.weight"]) for n in names + ["pool.q"]], "train.clip_opt")
-        self.w = {k: v.detach().to(torch.float32).contiguous().to(self.device) for k, v in state.items() if k not in ("heads", "image_size")}
-        self.w["patch.weight"] = self.w["patch.weight"].reshape(self.cfg["width"], -1)
-        if self.tower_arithmetic == "split":
-            pack_tower(self.w, [f"{n}.weight" for n in names + ["pool.q"]], [f"{n}.weight" for n in names])
-            for n in names + ["pool.q"]:
-                del self.w[f"{n}.weight"]
-        else:
-            for n in names:
-                self.w[f"{n}.weight.t"] = self.w[f"{n}.weight"].t().contiguous()
-        self.act = hip.VIT_ACTS[f"gelu_{gelu}"]
+        super().__init__(state, device, gelu, tower_arithmetic, tower_attention, "train.clip_opt", backward=True)
 
 
-class ClipLossPlan:
+class ClipLossPlan(TowerPlan):
     """Static launch lists for B image pairs of H x W.  `fake_view` / `target_view` / `grad_view` are fp32 NHWC views (hip.View) of the
     generated images, the targets and the gradient image (B * H * W pixels, channels coff .. coff + 2 = RGB); `loss_ptr` a float
     scalar (slot 0 of a slotted buffer in deterministic mode) that l_clip_sim is ADDED to, as the other loss kernels do.
@@ -303,36 +271,24 @@ class ClipLossPlan:
       fwd_fake     the tower on the generated rows: per block x_in, the packed qkv, x_mid and the fc1 pre-activation stay
       bwd          ssr_feature_l1, the pooling head, ln_post, the blocks in reverse, the patch embedding, ssr_vit_float_input_bwd,
                    which ADDS the image gradient into grad_view
-    `launcher` is the three in that order.  fc1 runs without its activation into the saved buffer and ssr_vit_act_fwd applies it (same
-    device function: same bytes), on both passes, so the two feature sets come from identical arithmetic.  A model with tower_attention
-    'mfma' launches ssr_mha_mfma_fwd / ssr_mha_mfma_bwd for the blocks (all three lists); the pooling head keeps ssr_mha_fwd / _bwd."""
+    `launcher` is the three in that order.  Both forwards are vit_tower.TowerPlan.forward behind ssr_vit_float_input with fc1's
+    pre-activation kept, so the two feature sets come from identical arithmetic."""
 
     def __init__(self, model: ClipLossModel, B: int, H: int, W: int, fake_view, target_view, grad_view, loss_ptr: int, weight: float = 1.0,
                  flags: int = 0):
         from . import engine, hip
-        from .hip import NULL_VIEW, View, view
-        cfg, w, dev = model.cfg, model.w, model.device
-        if B <= 0 or H <= 0 or W <= 0:
-            raise ValueError(f"the CLIP loss needs at least one image, got {B} x {H} x {W}")
-        Cw, p, g, T, mlp, heads, d = (cfg[k] for k in ("width", "patch", "grid", "tokens", "mlp", "heads", "head_dim"))
-        if p % 2:
-            raise ValueError(f"patch size {p}: ssr_linear contracts 3 p^2 channels, a multiple of 4")
-        if d not in (64, 72):
-            raise NotImplementedError(f"train.clip_opt: head dim {d} has no attention backward (ssr_mha_bwd: 64, 72)")
-        use_mfma = model.tower_attention == "mfma"
-        if use_mfma:
-            check_mfma_head_dim(d, "train.clip_opt")
-        ws_floats = hip.lib().ssr_mha_mfma_bwd_ws_floats if use_mfma else hip.lib().ssr_mha_bwd_ws_floats
-        self.model, self.B, self.H, self.W = model, B, H, W
-        lib, S, KP, M, depth = hip.lib(), cfg["image_size"], 3 * p * p, B * T, cfg["depth"]
+        from .hip import NULL_VIEW, view
+        super().__init__(model, B, H, W, "the CLIP loss")
+        cfg, dev, lib = model.cfg, model.device, self.lib
+        Cw, p, g, T, mlp, heads, d, depth = (cfg[k] for k in ("width", "patch", "grid", "tokens", "mlp", "heads", "head_dim", "depth"))
+        mfma = model.tower_attention == "mfma"                               # the blocks'; the pooling head keeps ssr_mha_bwd
+        ws_floats, mha_bwd = (lib.ssr_mha_mfma_bwd_ws_floats, lib.ssr_mha_mfma_bwd) if mfma else (lib.ssr_mha_bwd_ws_floats, lib.ssr_mha_bwd)
+        KP, M, scale, act, F32 = 3 * p * p, B * T, float(d) ** -0.5, model.act, hip.F32
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)      # noqa: E731
-        i32 = lambda t: t.to(torch.int32).contiguous().to(dev)               # noqa: E731
-        self.rowidx, self.colidx = i32(nearest_index_table(H, S)[:g * p]), i32(nearest_index_table(W, S)[:g * p])
-        self.rowrange, self.colrange = i32(nearest_inverse_ranges(H, S, g * p)), i32(nearest_inverse_ranges(W, S, g * p))
         self._perm = (C.c_int32 * 3)(0, 1, 2)
         self._mean, self._std = (C.c_float * 3)(*CLIP_LOSS_MEAN), (C.c_float * 3)(*CLIP_LOSS_STD)
         b = self.bufs = {"patches": z(M, KP), "embed": z(M, Cw), "h": z(M, Cw), "att": z(M, Cw), "post": z(M, mlp),
-                         "probe": w["pool.probe"].reshape(1, Cw).repeat(B, 1).contiguous(), "pz": z(B, Cw), "pa": z(B, Cw), "pm": z(B, mlp),
+                         "probe": model.w["pool.probe"].reshape(1, Cw).repeat(B, 1).contiguous(), "pz": z(B, Cw), "pa": z(B, Cw), "pm": z(B, mlp),
                          # the target pass's scratch
                          "t.x": z(M, Cw), "t.qkv": z(M, 3 * Cw), "t.pre": z(M, mlp), "t.q": z(B, Cw), "t.kv": z(M, 2 * Cw), "t.py": z(B, Cw),
                          "t.ppre": z(B, mlp), "fg": z(B, Cw),
@@ -348,71 +304,17 @@ class ClipLossPlan:
         for i in range(depth):
             b[f"qkv.{i}"], b[f"xmid.{i}"], b[f"pre.{i}"] = z(M, 3 * Cw), z(M, Cw), z(M, mlp)
         self.saved_bytes = 4 * sum(b[k].numel() for k in b if k.split(".")[0] in ("x", "qkv", "xmid", "pre"))
-        ptr = lambda k: w[k].data_ptr()                                        # noqa: E731
-        scale, eps, act = float(d) ** -0.5, cfg["ln_eps"], model.act
-        F32 = hip.F32
+        linear_t, layernorm_bwd, split = self.linear_t, self.layernorm_bwd, self.split
 
-        use_split = model.tower_arithmetic == "split"  # ssr_linear_split: fp16 pieces forward (both passes), bf16 pieces backward
-        mha_fwd, mha_bwd = (lib.ssr_mha_mfma_fwd, lib.ssr_mha_mfma_bwd) if use_mfma else (lib.ssr_mha_fwd, lib.ssr_mha_bwd)   # the blocks'
-
-        def linear(L, xv, name, yv, rows, K, Nout, res=NULL_VIEW):
-            if use_split:
-                L.add(lib.ssr_linear_split, xv, ptr(f"{name}.weight.pk"), ptr(f"{name}.bias"), res, yv, hip.SPLIT_F16, rows, K, Nout, 0,
-                      what=f"linear {name}")
-            else:
-                L.add(lib.ssr_linear, xv, ptr(f"{name}.weight"), ptr(f"{name}.bias"), res, yv, F32, rows, K, Nout, 0, what=f"linear {name}")
-
-        def linear_t(L, dyv, name, dxv, rows, K, Nout):
-            """dX [rows, Nout] = dY [rows, K] W, W = `name`.weight [K, Nout]"""
-            if use_split:
-                L.add(lib.ssr_linear_split, dyv, ptr(f"{name}.weight.t.pk"), None, NULL_VIEW, dxv, hip.SPLIT_BF16, rows, K, Nout, 0,
-                      what=f"linear^T {name}")
-            else:
-                L.add(lib.ssr_linear, dyv, ptr(f"{name}.weight.t"), None, NULL_VIEW, dxv, F32, rows, K, Nout, 0, what=f"linear^T {name}")
-
-        def layernorm(L, xv, name, yv, rows):
-            L.add(lib.ssr_layernorm_fwd, xv, ptr(f"{name}.weight"), ptr(f"{name}.bias"), yv, F32, rows, Cw, eps, what=f"layernorm {name}")
-
-        def layernorm_bwd(L, xv, name, dyv, rv, outv, rows):
-            L.add(lib.ssr_layernorm_bwd, xv, ptr(f"{name}.weight"), dyv, rv, outv, F32, rows, Cw, eps, what=f"layernorm bwd {name}")
-
-        def split(t, n):
-            return [View(t.data_ptr(), n * Cw, i * Cw) for i in range(n)]
-
-        def forward(L, img, xs, qkvs, xmids, pres, q, kv, py, ppre, feat):
-            """xs: depth + 1 row buffers (block inputs, then the last rows); all the same buffer when nothing is saved"""
-            L.add(lib.ssr_vit_float_input, img, B, H, W, self.rowidx.data_ptr(), self.colidx.data_ptr(), g, p, view(b["patches"]), F32,
-                  self._perm, self._mean, self._std, what="float input")
-            linear(L, view(b["patches"]), "patch", view(b["embed"]), M, KP, Cw)
-            L.add(lib.ssr_vit_tokens, view(b["embed"]), None, ptr("pos"), view(xs[0]), F32, B, T, Cw, what="tokens")
-            hv = view(b["h"])
-            for i in range(depth):
-                n = f"blocks.{i}"
-                qs = split(qkvs[i], 3)
-                layernorm(L, view(xs[i]), f"{n}.ln1", hv, M)
-                linear(L, hv, f"{n}.qkv", view(qkvs[i]), M, Cw, 3 * Cw)
-                L.add(mha_fwd, qs[0], qs[1], qs[2], view(b["att"]), F32, B, T, T, heads, d, scale, what=f"attention {n}")
-                linear(L, view(b["att"]), f"{n}.proj", view(xmids[i]), M, Cw, Cw, res=view(xs[i]))
-                layernorm(L, view(xmids[i]), f"{n}.ln2", hv, M)
-                linear(L, hv, f"{n}.fc1", view(pres[i]), M, Cw, mlp)
-                L.add(lib.ssr_vit_act_fwd, view(pres[i]), view(b["post"]), F32, M, mlp, act, what=f"activation {n}")
-                linear(L, view(b["post"]), f"{n}.fc2", view(xs[i + 1]), M, mlp, Cw, res=view(xmids[i]))
-            ks = split(kv, 2)
-            layernorm(L, view(xs[depth]), "ln_post", hv, M)
-            linear(L, view(b["probe"]), "pool.q", view(q), B, Cw, Cw)
-            linear(L, hv, "pool.kv", view(kv), M, Cw, 2 * Cw)
-            L.add(lib.ssr_mha_fwd, view(q), ks[0], ks[1], view(b["pa"]), F32, B, 1, T, heads, d, scale, what="attention pool")
-            linear(L, view(b["pa"]), "pool.proj", view(py), B, Cw, Cw)
-            layernorm(L, view(py), "pool.ln", view(b["pz"]), B)
-            linear(L, view(b["pz"]), "pool.fc1", view(ppre), B, Cw, mlp)
-            L.add(lib.ssr_vit_act_fwd, view(ppre), view(b["pm"]), F32, B, mlp, act, what="activation pool")
-            linear(L, view(b["pm"]), "pool.fc2", view(feat), B, mlp, Cw, res=view(py))
+        def float_input(img):
+            return lambda L, patches: L.add(lib.ssr_vit_float_input, img, B, H, W, self.rowidx.data_ptr(), self.colidx.data_ptr(), g, p, patches,
+                                            F32, self._perm, self._mean, self._std, what="float input")
 
         self.fwd_target, self.fwd_fake, self.bwd = engine.Launcher(), engine.Launcher(), engine.Launcher()
-        forward(self.fwd_target, target_view, [b["t.x"]] * (depth + 1), [b["t.qkv"]] * depth, [b["t.x"]] * depth, [b["t.pre"]] * depth,
-                b["t.q"], b["t.kv"], b["t.py"], b["t.ppre"], b["fg"])
-        forward(self.fwd_fake, fake_view, [b[f"x.{i}"] for i in range(depth + 1)], [b[f"qkv.{i}"] for i in range(depth)],
-                [b[f"xmid.{i}"] for i in range(depth)], [b[f"pre.{i}"] for i in range(depth)], b["q"], b["kv"], b["py"], b["ppre"], b["fx"])
+        self.forward(self.fwd_target, float_input(target_view), b, [b["t.x"]] * (depth + 1), [b["t.qkv"]] * depth, [b["t.x"]] * depth,
+                     [b["t.pre"]] * depth, (b["t.q"], b["t.kv"], b["t.py"], b["t.ppre"]), b["fg"])
+        self.forward(self.fwd_fake, float_input(fake_view), b, [b[f"x.{i}"] for i in range(depth + 1)], [b[f"qkv.{i}"] for i in range(depth)],
+                     [b[f"xmid.{i}"] for i in range(depth)], [b[f"pre.{i}"] for i in range(depth)], (b["q"], b["kv"], b["py"], b["ppre"]), b["fx"])
 
         L = self.bwd
         ws = b["ws"].data_ptr()

@@ -44,7 +44,7 @@ widened to fp32 on load.
     clip_random_state                random weights of any size (tests, throughput runs)
     nearest_index_table              F.interpolate(mode='nearest')'s source index per destination index, from F.interpolate itself
     clip_image_features_reference    the definition in torch on the CPU;   clipscore_reference   the same, for the score
-    CLIPVisualModel / CLIPVisualPlan the weights on the device / the static launch list of one (B, H, W) (csrc/vit.hip)
+    CLIPVisualModel / CLIPVisualPlan the weights on the device / the static launch list of one (B, H, W) (vit_tower.py, csrc/vit.hip)
     clipscore                        uint8 NHWC device images -> float64 [N] on the host
     check_clipscore_opt / calculate_clipscore        the entries of metrics.METRIC_CHECKS / metrics.METRICS
 
@@ -62,7 +62,8 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn.functional as F
 
-from .linear_split import check_mfma_head_dim, check_split_domain, check_tower_arithmetic, check_tower_attention, linear_split_reference, pack_tower
+from .linear_split import check_tower_arithmetic, check_tower_attention, linear_split_reference
+from .vit_tower import TowerPlan, TowerWeights
 
 CLIP_MODELS = {"siglip-ViT-SO400M-14": "siglip", "clip-ViT-B/16": "clip"}          # the reference's names -> family
 CLIP_REFUSED = ("clipa-ViT-bigG-14",)                                                # the reference's third branch: 1.8 B parameters
@@ -426,39 +427,17 @@ def clipscore_reference(a_u8, b_u8, state: Dict[str, torch.Tensor], bgr: bool = 
 
 
 # ---------------------------------------------------------------- the device path
-class CLIPVisualModel:
-    """The weights of one tower on the device (fp32, the matrices as the state_dict holds them: ssr_linear reads [Nout][K] rows) and
-    the plans that use them, cached per (B, H, W, bgr, normalize, tower_attention).  tower_arithmetic 'split': every matrix is held as the packed fp16
-    pieces of ssr_linear_split instead (`<key>.pk`; a matrix with max|w| >= 64 raises ValueError by name before anything is loaded).
-    tower_attention 'mfma' changes no weight: the plans launch ssr_mha_mfma_fwd (csrc/mha_mfma.hip) for the blocks' self-attention."""
+class CLIPVisualModel(TowerWeights):
+    """The weights of one tower of either family (vit_tower.TowerWeights, no backward) and the plans that use them, cached per
+    (B, H, W, bgr, normalize, tower_attention)."""
 
     def __init__(self, state: Dict[str, torch.Tensor], device="cuda", gelu: str = "tanh", tower_arithmetic: str = "exact",
                  tower_attention: str = "fma"):
-        from . import hip
         if gelu not in _GELUS:
             raise NotImplementedError(f"gelu={gelu!r} (have {list(_GELUS)})")
-        self.tower_arithmetic = check_tower_arithmetic(tower_arithmetic, "metric type 'calculate_clipscore': tower_arithmetic")
-        self.tower_attention = check_tower_attention(tower_attention, "metric type 'calculate_clipscore': tower_attention")
-        self.cfg = vit_config_from_state(state)
-        self.device, self.gelu = torch.device(device), gelu
-        for k in _flat_keys(self.cfg["family"], self.cfg["depth"]):
-            if k not in state:
-                raise KeyError(k)
-        mats = [k for k in _flat_keys(self.cfg["family"], self.cfg["depth"])
-                if k.endswith(".weight") and k.split(".")[-2] not in ("ln1", "ln2", "ln", "ln_pre", "ln_post")]
-        if self.tower_arithmetic == "split":
-            check_split_domain([(k, state[k]) for k in mats] + ([("proj", state["proj"])] if self.cfg["family"] == "clip" else []),
-                               "metric type 'calculate_clipscore'")
-        self.w = {k: v.detach().to(torch.float32).contiguous().to(self.device) for k, v in state.items() if k not in ("heads", "image_size")}
-        self.w["patch.weight"] = self.w["patch.weight"].reshape(self.cfg["width"], -1)           # [C, 3 p p]: ssr_vit_patch_input's columns
-        if self.cfg["family"] == "clip":
-            self.w["proj.t"] = self.w["proj"].t().contiguous()                                    # [E, C]
-        if self.tower_arithmetic == "split":
-            mats += ["proj.t"] if self.cfg["family"] == "clip" else []
-            pack_tower(self.w, mats)
-            for k in mats:
-                del self.w[k]
-        self.act = hip.VIT_ACTS["quick_gelu" if self.cfg["family"] == "clip" else f"gelu_{gelu}"]
+        super().__init__(state, device, gelu, check_tower_arithmetic(tower_arithmetic, "metric type 'calculate_clipscore': tower_arithmetic"),
+                         check_tower_attention(tower_attention, "metric type 'calculate_clipscore': tower_attention"),
+                         "metric type 'calculate_clipscore'")
         self.plans: Dict[Tuple, CLIPVisualPlan] = {}
 
     def plan(self, B: int, H: int, W: int, bgr: bool = True, normalize: bool = False) -> "CLIPVisualPlan":
@@ -468,87 +447,36 @@ class CLIPVisualModel:
         return self.plans[key]
 
 
-class CLIPVisualPlan:
-    """One static launch list for B images of H x W: ssr_vit_patch_input (the nearest resize by two index tables built on the host
-    with F.interpolate itself), the patch embedding as ssr_linear, ssr_vit_tokens, per block ln1 / qkv / ssr_mha_fwd over the three
-    slices of the packed buffer / proj (+ residual) / ln2 / fc1 (+ activation) / fc2 (+ residual), then the family's pooling.
-    `features` [B, out_dim] stays on the device; `pairs()` appends ssr_cosine_pairs for B = 2 N."""
+class CLIPVisualPlan(TowerPlan):
+    """One static launch list for B uint8 images of H x W: ssr_vit_patch_input (resize, channel order, / 255, mean / std), then one
+    pass of vit_tower.TowerPlan.forward with the rows updated in place and the activation fused into fc1.  `features` [B, out_dim]
+    stays on the device; `run_pairs()` appends ssr_cosine_pairs for B = 2 N."""
 
     def __init__(self, model: CLIPVisualModel, B: int, H: int, W: int, bgr: bool = True, normalize: bool = False):
         from . import engine, hip
-        from .hip import NULL_VIEW, View, view
-        cfg, w, dev = model.cfg, model.w, model.device
-        if B <= 0 or H <= 0 or W <= 0:
-            raise ValueError(f"CLIPScore needs at least one image, got {B} x {H} x {W}")
-        fam, Cw, p, g, T, mlp, heads, d, E = (cfg[k] for k in ("family", "width", "patch", "grid", "tokens", "mlp", "heads", "head_dim", "out_dim"))
-        if p % 2:
-            raise ValueError(f"patch size {p}: ssr_linear contracts 3 p^2 channels, a multiple of 4")
-        if model.tower_attention == "mfma":
-            check_mfma_head_dim(d, "metric type 'calculate_clipscore'")
-        self.model, self.B, self.H, self.W = model, B, H, W
-        lib, G, S, KP = hip.lib(), g * g, cfg["image_size"], 3 * p * p
-        mha_blocks = lib.ssr_mha_mfma_fwd if model.tower_attention == "mfma" else lib.ssr_mha_fwd      # the pooling head keeps ssr_mha_fwd
-        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)      # noqa: E731
-        # the resize to S x S, of which the patch convolution reads the first g * p rows and columns
-        self.rowidx = nearest_index_table(H, S)[:g * p].to(torch.int32).to(dev)
-        self.colidx = nearest_index_table(W, S)[:g * p].to(torch.int32).to(dev)
-        self.u8 = torch.zeros(B, H, W, 3, dtype=torch.uint8, device=dev)
+        super().__init__(model, B, H, W, "CLIPScore")
+        fam, Cw, p, g, T, mlp, E, depth = (model.cfg[k] for k in ("family", "width", "patch", "grid", "tokens", "mlp", "out_dim", "depth"))
+        G, M = g * g, B * T
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=model.device)      # noqa: E731
+        self.u8 = torch.zeros(B, H, W, 3, dtype=torch.uint8, device=model.device)
         self._perm = (C.c_int32 * 3)(*((2, 1, 0) if bgr else (0, 1, 2)))
-        self._mean = (C.c_float * 3)(*CLIP_MEAN[fam]) if normalize else None
-        self._std = (C.c_float * 3)(*CLIP_STD[fam]) if normalize else None
-        M = B * T
-        b = self.bufs = {"patches": z(B * G, KP), "embed": z(B * G, Cw), "x": z(M, Cw), "h": z(M, Cw), "qkv": z(M, 3 * Cw), "att": z(M, Cw),
-                         "mlp": z(M, mlp), "features": z(B, E)}
-        ptr = lambda k: w[k].data_ptr()                                        # noqa: E731
-        scale, eps, act = float(d) ** -0.5, cfg["ln_eps"], model.act
-        L = engine.Launcher()
-
-        def linear(xv, name, yv, rows, K, Nout, act=0, res=NULL_VIEW, wkey=None, bias=True, what=""):
-            wkey, bp = wkey or f"{name}.weight", ptr(f"{name}.bias") if bias else None
-            if model.tower_arithmetic == "split":
-                L.add(lib.ssr_linear_split, xv, ptr(f"{wkey}.pk"), bp, res, yv, hip.SPLIT_F16, rows, K, Nout, act, what=what or f"linear {name}")
-            else:
-                L.add(lib.ssr_linear, xv, ptr(wkey), bp, res, yv, hip.F32, rows, K, Nout, act, what=what or f"linear {name}")
-
-        def layernorm(xv, name, yv, rows):
-            L.add(lib.ssr_layernorm_fwd, xv, ptr(f"{name}.weight"), ptr(f"{name}.bias"), yv, hip.F32, rows, Cw, eps, what=f"layernorm {name}")
-
-        L.add(lib.ssr_vit_patch_input, self.u8.data_ptr(), B, H, W, self.rowidx.data_ptr(), self.colidx.data_ptr(), g, p, view(b["patches"]),
-              hip.F32, self._perm, self._mean, self._std, what="patch input")
-        linear(view(b["patches"]), "patch", view(b["embed"]), B * G, KP, Cw, bias=fam == "siglip")
-        L.add(lib.ssr_vit_tokens, view(b["embed"]), ptr("cls") if fam == "clip" else None, ptr("pos"), view(b["x"]), hip.F32, B, G, Cw, what="tokens")
-        xv, hv = view(b["x"]), view(b["h"])
-        if fam == "clip":
-            layernorm(xv, "ln_pre", xv, M)
-        qkv = [View(b["qkv"].data_ptr(), 3 * Cw, i * Cw) for i in range(3)]
-        for i in range(cfg["depth"]):
-            n = f"blocks.{i}"
-            layernorm(xv, f"{n}.ln1", hv, M)
-            linear(hv, f"{n}.qkv", view(b["qkv"]), M, Cw, 3 * Cw)
-            L.add(mha_blocks, qkv[0], qkv[1], qkv[2], view(b["att"]), hip.F32, B, T, T, heads, d, scale, what=f"attention {n}")
-            linear(view(b["att"]), f"{n}.proj", xv, M, Cw, Cw, res=xv)
-            layernorm(xv, f"{n}.ln2", hv, M)
-            linear(hv, f"{n}.fc1", view(b["mlp"]), M, Cw, mlp, act=act)
-            linear(view(b["mlp"]), f"{n}.fc2", xv, M, mlp, Cw, res=xv)
-        fv = view(b["features"])
+        self._mean, self._std = ((C.c_float * 3)(*t[fam]) if normalize else None for t in (CLIP_MEAN, CLIP_STD))
+        b = self.bufs = {"patches": z(B * G, 3 * p * p), "embed": z(B * G, Cw), "x": z(M, Cw), "h": z(M, Cw), "qkv": z(M, 3 * Cw), "att": z(M, Cw),
+                         "post": z(M, mlp), "features": z(B, E)}
         if fam == "clip":
             b["pooled"] = z(B, Cw)
-            layernorm(View(b["x"].data_ptr(), T * Cw, 0), "ln_post", view(b["pooled"]), B)        # the class-token row of every image
-            linear(view(b["pooled"]), "proj", fv, B, Cw, E, wkey="proj.t", bias=False)
         else:
-            b.update(probe=w["pool.probe"].reshape(1, Cw).repeat(B, 1).contiguous(), q=z(B, Cw), kv=z(M, 2 * Cw), pa=z(B, Cw), py=z(B, Cw),
+            b.update(probe=model.w["pool.probe"].reshape(1, Cw).repeat(B, 1).contiguous(), q=z(B, Cw), kv=z(M, 2 * Cw), pa=z(B, Cw), py=z(B, Cw),
                      pz=z(B, Cw), pm=z(B, mlp))
-            layernorm(xv, "ln_post", hv, M)
-            linear(view(b["probe"]), "pool.q", view(b["q"]), B, Cw, Cw)
-            linear(hv, "pool.kv", view(b["kv"]), M, Cw, 2 * Cw)
-            L.add(lib.ssr_mha_fwd, view(b["q"]), View(b["kv"].data_ptr(), 2 * Cw, 0), View(b["kv"].data_ptr(), 2 * Cw, Cw), view(b["pa"]), hip.F32,
-                  B, 1, T, heads, d, scale, what="attention pool")
-            linear(view(b["pa"]), "pool.proj", view(b["py"]), B, Cw, Cw)
-            layernorm(view(b["py"]), "pool.ln", view(b["pz"]), B)
-            linear(view(b["pz"]), "pool.fc1", view(b["pm"]), B, Cw, mlp, act=act)
-            linear(view(b["pm"]), "pool.fc2", fv, B, mlp, Cw, res=view(b["py"]))
+
+        def patch_input(L, patches):
+            L.add(self.lib.ssr_vit_patch_input, self.u8.data_ptr(), B, H, W, self.rowidx.data_ptr(), self.colidx.data_ptr(), g, p, patches,
+                  hip.F32, self._perm, self._mean, self._std, what="patch input")
+
+        self.launcher = engine.Launcher()
+        self.forward(self.launcher, patch_input, b, [b["x"]] * (depth + 1), [b["qkv"]] * depth, [b["x"]] * depth, None,
+                     None if fam == "clip" else (b["q"], b["kv"], b["py"], None), b["features"])
         self.features = b["features"]
-        self.launcher = L
         self.scores = None
 
     def run(self, images_u8: torch.Tensor) -> torch.Tensor:

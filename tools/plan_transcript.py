@@ -18,6 +18,18 @@ to (256, 8).
 
 tests/test_launch_plans_host.py regenerates every text and compares it with the committed file (call count + sha256 per
 configuration, the full text of FULL_TEXT); tests/test_gpu_launch_plans.py builds three of them on the device.
+
+The ViT towers have a table of their own, TOWER_CONFIGS: the CLIPScore metric plan (family x tower_arithmetic x tower_attention, fed
+bgr + normalize, and once the reference's raw feed) and the CLIP loss plan (siglip x tower_arithmetic x tower_attention; fwd_target,
+fwd_fake, bwd and their concatenation as separate launchers) on two two-block towers (head dims 64 and 72) at B, H, W = 2, 10, 13.
+Per configuration the text also lists the model's weights (key, shape, dtype; under exact arithmetic a sha256 over their bytes), the
+element count of the plan's buffers and the loss plan's saved_bytes.  On the CPU the split weights are zeroed buffers of the packed
+size (packing is a kernel); their addresses are canonical either way.
+
+  python tools/plan_transcript.py --tower-golden tests/golden/tower_plans.json
+  python tools/plan_transcript.py --show loss/split/mfma/d72
+
+tests/test_tower_plans_host.py and tests/test_gpu_tower_plans.py hold vit_tower.py, clipscore_metric.py and clip_loss.py to that file.
 """
 import argparse
 import bisect
@@ -144,7 +156,11 @@ def fmt_launcher(canon, L, out, indent=""):
         parts = []
         for i, (t, a) in enumerate(zip(types_, args)):
             if isinstance(t, type) and issubclass(t, C._Pointer):
-                if isinstance(a, C.Array):             # (records, count)
+                if a is None:
+                    parts.append("null")
+                elif isinstance(a, C.Array) and not issubclass(a._type_, C.Structure):      # scalars by value (perm, mean, std)
+                    parts.append(_fmt_value(canon, type(a), a))
+                elif isinstance(a, C.Array):           # (records, count)
                     parts.append("[" + " ".join(fmt_struct(canon, a[j]) for j in range(int(args[i + 1]))) + "]")
                 else:
                     parts.append(fmt_struct(canon, a._obj))
@@ -152,6 +168,8 @@ def fmt_launcher(canon, L, out, indent=""):
                 parts.append(canon(a))
             elif t is C.c_float:
                 parts.append(_fbits(a))
+            elif t is C.c_double:
+                parts.append("d:%016x" % struct.unpack("<Q", struct.pack("<d", a))[0])
             elif isinstance(a, C.Structure):
                 parts.append(_fmt_value(canon, t, a))
             else:
@@ -433,9 +451,114 @@ def golden(runs):
     return doc
 
 
+# ---------------------------------------------------------------------------------------------------- the ViT towers
+# The CLIPScore metric plan and the CLIP loss plan (vit_tower.py, clipscore_metric.py, clip_loss.py): a table of their own, recorded in
+# tests/golden/tower_plans.json.  No switch is read at import, so one process builds them all.
+TOWERS = {"d64": dict(width=128, depth=2, mlp=192, patch=4, grid=3, heads=2),           # head dim 64
+          "d72": dict(width=144, depth=2, mlp=192, patch=4, grid=3, heads=2)}           # head dim 72, the other one both attention kernels take
+TOWER_SHAPE = (2, 10, 13)            # B, H, W: not square, no multiple of the patch: both index tables and both inverse ranges are non-trivial
+TOWER_FULL_TEXT = ("metric/siglip/split/mfma/d64", "loss/split/mfma/d72")
+TOWER_CONFIGS = {}                   # name -> (builder, keyword arguments)
+
+
+def _on_cpu(dev):
+    import torch
+    return torch.device(dev).type == "cpu"
+
+
+class _cpu_pack:
+    """on the CPU, linear_split.pack_split_weight (which launches ssr_linear_split_pack) gives a zeroed buffer of the packed size"""
+
+    def __init__(self, dev):
+        self.cpu = _on_cpu(dev)
+
+    def __enter__(self):
+        import torch
+        from satlas_super_resolution_amd import hip, linear_split
+        self.real = linear_split.pack_split_weight
+        if self.cpu:
+            linear_split.pack_split_weight = lambda w, pieces: torch.zeros(int(hip.lib().ssr_linear_split_pack_bytes(*w.shape)), dtype=torch.uint8)
+
+    def __exit__(self, *exc):
+        from satlas_super_resolution_amd import linear_split
+        linear_split.pack_split_weight = self.real
+
+
+def _metric_tower(dev, family, arithmetic, attention, tower, bgr=True, normalize=True):
+    from satlas_super_resolution_amd import clipscore_metric as CM
+    with _cpu_pack(dev):
+        model = CM.CLIPVisualModel(CM.clip_random_state(family, **TOWERS[tower]), dev, tower_arithmetic=arithmetic, tower_attention=attention)
+    plan = model.plan(*TOWER_SHAPE, bgr=bgr, normalize=normalize)
+    return model, plan, [("launcher", plan.launcher)], []
+
+
+def _loss_tower(dev, arithmetic, attention, tower):
+    """fake, target and gradient views of channel stride 8, the target at channel offset 4 of the buffer it shares with the generated
+    image; weight 0.5 into slot 0 of a slotted loss buffer"""
+    import torch
+    from satlas_super_resolution_amd import clip_loss as CL, clipscore_metric as CM, hip
+    B, H, W = TOWER_SHAPE
+    with _cpu_pack(dev):
+        model = CL.ClipLossModel(CM.clip_random_state("siglip", **TOWERS[tower]), dev, tower_arithmetic=arithmetic, tower_attention=attention)
+    images, grad = (torch.zeros(B, H, W, 8, device=dev) for _ in range(2))
+    loss = torch.zeros(hip.LOSS_SLOTS, device=dev)
+    plan = CL.ClipLossPlan(model, B, H, W, hip.View(images.data_ptr(), 8, 0), hip.View(images.data_ptr(), 8, 4), hip.View(grad.data_ptr(), 8, 0),
+                           loss.data_ptr(), 0.5, hip.DETERMINISTIC)
+    return model, plan, [(n, getattr(plan, n)) for n in ("fwd_target", "fwd_fake", "bwd", "launcher")], [images, grad, loss]
+
+
+for _t in TOWERS:
+    for _ar in ("exact", "split"):
+        for _at in ("fma", "mfma"):
+            for _f in ("siglip", "clip"):
+                TOWER_CONFIGS["metric/%s/%s/%s/%s" % (_f, _ar, _at, _t)] = (_metric_tower, dict(family=_f, arithmetic=_ar, attention=_at, tower=_t))
+            TOWER_CONFIGS["loss/%s/%s/%s" % (_ar, _at, _t)] = (_loss_tower, dict(arithmetic=_ar, attention=_at, tower=_t))
+# the reference's feed: no mean / std (null pointers), the identity permutation
+TOWER_CONFIGS["metric/siglip/exact/fma/d64/raw"] = (_metric_tower, dict(family="siglip", arithmetic="exact", attention="fma", tower="d64", bgr=False,
+                                                                          normalize=False))
+
+
+def tower_transcript(model, plan, launchers, extra):
+    """-> (text, number of C-ABI calls): every launcher, then the (key, shape, dtype) of every weight the model holds - under exact
+    arithmetic with a sha256 over the keys and bytes - the element count of the plan's buffers and the loss plan's saved_bytes"""
+    canon = Canon([plan, model] + list(extra))
+    out, calls = [], 0
+    for name, L in launchers:
+        out.append("launcher %s" % name)
+        calls += fmt_launcher(canon, L, out, "  ")
+    h = hashlib.sha256()
+    for k in sorted(model.w):
+        t = model.w[k]
+        out.append("weight %s %s %s" % (k, list(t.shape), str(t.dtype).replace("torch.", "")))
+        h.update(k.encode())
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    if model.tower_arithmetic == "exact":
+        out.append("weights sha256 %s" % h.hexdigest())
+    out.append("bufs numel %d" % sum(t.numel() for t in plan.bufs.values()))
+    if hasattr(plan, "saved_bytes"):
+        out.append("saved_bytes %d" % plan.saved_bytes)
+    return "\n".join(out) + "\n", calls
+
+
+def build_tower(name, dev="cpu"):
+    """(text, calls) of one tower configuration"""
+    fn, kw = TOWER_CONFIGS[name]
+    return tower_transcript(*fn(dev, **kw))
+
+
+def tower_sweep(dev="cpu"):
+    return {name: build_tower(name, dev) for name in TOWER_CONFIGS}
+
+
+def tower_golden(runs):
+    return {"configs": {k: {"calls": c, "sha256": digest(t)} for k, (t, c) in runs.items()},
+            "full_text": {k: runs[k][0].splitlines() for k in TOWER_FULL_TEXT}}
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--golden")
+    ap.add_argument("--tower-golden")
     ap.add_argument("--one", action="store_true")
     ap.add_argument("--setting", default="")
     ap.add_argument("--show")
@@ -443,6 +566,14 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.one:
         json.dump(sweep(a.setting, a.device), sys.stdout)
+    elif a.tower_golden:
+        doc = tower_golden(tower_sweep(a.device))
+        with open(a.tower_golden, "w") as f:
+            json.dump(doc, f, indent=0)
+            f.write("\n")
+        print("%d tower transcripts -> %s (%d bytes)" % (len(doc["configs"]), a.tower_golden, os.path.getsize(a.tower_golden)))
+    elif a.show in TOWER_CONFIGS:
+        sys.stdout.write(build_tower(a.show, a.device)[0])
     elif a.show:
         name, mode = a.show.split("/")
         sys.stdout.write(build(name, mode, a.device)[0])
