@@ -29,7 +29,10 @@ layer, the `lin{k}` layers and the formula; only F_k differs:
 Its first two convolutions and its pooling are csrc/conv_direct.hip (ssr_conv_direct, ssr_maxpool3s2_fwd); the three 3x3 layers run
 through ssr_conv2d in exact fp32 like VGG's.  Every function below takes the backbone as `net` ('vgg' by default, 'alex').
 
-    vgg16_layers / vgg16_specs     the layer table
+The two backbones themselves - layer records, geometry, specs, random weights, the forward's launches - are cnn_backbone.py, shared
+with the perceptual loss's VGG19.
+
+    vgg16_layers / vgg16_specs     the layer table (cnn_backbone's records as plain tuples)
     alexnet_layers / alexnet_specs / alexnet_tap_sizes      the second backbone's
     load_lpips_state               torchvision + lpips files, one lpips state_dict, or the flat layout -> flat layout
     lpips_random_state             random weights of the same architecture (tests, throughput runs)
@@ -41,25 +44,23 @@ through ssr_conv2d in exact fp32 like VGG's.  Every function below takes the bac
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
 
+from . import cnn_backbone as CB, engine, hip
+from .cnn_backbone import ALEXNET_LAYERS, VGG16_BLOCKS          # the backbones are written there
+from .hip import view
+
 LPIPS_PRETRAIN_PATH = "experiments/pretrained_models/lpips_vgg.pth"
 LPIPS_SHIFT = (-0.030, -0.088, -0.188)
 LPIPS_SCALE = (0.458, 0.448, 0.450)
 LPIPS_EPS = 1e-10
-# (block, convs in the block, width)
-VGG16_BLOCKS = ((1, 2, 64), (2, 2, 128), (3, 3, 256), (4, 3, 512), (5, 3, 512))
 LPIPS_TAPS = ("conv1_2", "conv2_2", "conv3_3", "conv4_3", "conv5_3")
 LPIPS_ALEX_PRETRAIN_PATH = "experiments/pretrained_models/lpips_alex.pth"
-# (name, torchvision features index, cin, cout, kernel, stride, pad, pooled_before); every layer is a tap       [recalled]
-ALEXNET_LAYERS = (("conv1", 0, 3, 64, 11, 4, 2, False), ("conv2", 3, 64, 192, 5, 1, 2, True), ("conv3", 6, 192, 384, 3, 1, 1, True),
-                  ("conv4", 8, 384, 256, 3, 1, 1, False), ("conv5", 10, 256, 256, 3, 1, 1, False))
-LPIPS_ALEX_TAPS = tuple(l[0] for l in ALEXNET_LAYERS)
+LPIPS_ALEX_TAPS = tuple(l.name for l in ALEXNET_LAYERS)          # every layer is a tap       [recalled]
 ALEXNET_MIN_SIDE = 31              # the smallest side that leaves a pixel behind both poolings: taps of 7, 3, 1, 1, 1
 # keys of a `calculate_lpips` metric entry: the reference's **kwargs swallows the first four
 _IGNORED_KEYS = ("crop_border", "test_y_channel", "input_order", "better", "type")
@@ -76,32 +77,22 @@ def _net(net: str) -> str:
 
 def vgg16_layers():
     """[(name 'convB_J', torchvision features index, cin, cout, pooled_before)]"""
-    out, idx, cin = [], 0, 3
-    for b, n, width in VGG16_BLOCKS:
-        for j in range(1, n + 1):
-            out.append((f"conv{b}_{j}", idx, cin, width, j == 1 and b > 1))
-            idx += 2                    # conv, relu
-            cin = width
-        idx += 1                        # pool
-    return out
+    return [(l.name, l.idx, l.cin, l.cout, bool(l.pool)) for l in CB.vgg_layers(VGG16_BLOCKS)]
 
 
 def vgg16_specs():
-    from . import engine
     # no backward here: the transposed packing of the weights is left out
-    return [engine.ConvSpec(f"features.{idx}", cout, cin, 3, 1, True, False, dgrad_packed=False) for _, idx, cin, cout, _ in vgg16_layers()]
+    return CB.conv_specs(CB.vgg_layers(VGG16_BLOCKS), dgrad_packed=False)
 
 
 def alexnet_layers():
     """[(name 'convJ', torchvision features index, cin, cout, kernel, stride, pad, pooled_before)]"""
-    return list(ALEXNET_LAYERS)
+    return [tuple(l[:7]) + (bool(l.pool),) for l in ALEXNET_LAYERS]
 
 
 def alexnet_specs():
     """the 3x3 layers, which ssr_conv2d runs (conv1 and conv2 go through ssr_conv_direct and are not in a ParamStore)"""
-    from . import engine
-    return [engine.ConvSpec(f"features.{idx}", cout, cin, 3, 1, True, False, dgrad_packed=False)
-            for _, idx, cin, cout, k, _, _, _ in ALEXNET_LAYERS if k == 3]
+    return CB.conv_specs(ALEXNET_LAYERS, dgrad_packed=False)
 
 
 def alexnet_tap_sizes(H: int, W: int) -> List[Tuple[int, int]]:
@@ -109,20 +100,11 @@ def alexnet_tap_sizes(H: int, W: int) -> List[Tuple[int, int]]:
     if H < ALEXNET_MIN_SIDE or W < ALEXNET_MIN_SIDE:
         raise ValueError(f"LPIPS (AlexNet: 11x11 stride-4 convolution, two 3x3 stride-2 poolings) needs H and W >= {ALEXNET_MIN_SIDE}, "
                          f"got {H} x {W}")
-    out, h, w = [], H, W
-    for _, _, _, _, k, s, p, pooled_before in ALEXNET_LAYERS:
-        if pooled_before:
-            h, w = (h - 3) // 2 + 1, (w - 3) // 2 + 1
-        h, w = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
-        out.append((h, w))
-    return out
+    return CB.tap_sizes(ALEXNET_LAYERS, H, W)
 
 
-def _conv_table(net: str = "vgg") -> List[Tuple[int, Tuple[int, int, int, int]]]:
-    """[(torchvision features index, weight shape)] of the backbone's convolutions"""
-    if _net(net) == "alex":
-        return [(idx, (cout, cin, k, k)) for _, idx, cin, cout, k, _, _, _ in ALEXNET_LAYERS]
-    return [(idx, (cout, cin, 3, 3)) for _, idx, cin, cout, _ in vgg16_layers()]
+def _layers(net: str = "vgg") -> List[CB.Layer]:
+    return list(ALEXNET_LAYERS) if _net(net) == "alex" else CB.vgg_layers(VGG16_BLOCKS)
 
 
 def _tap_names(net: str = "vgg") -> Tuple[str, ...]:
@@ -130,10 +112,7 @@ def _tap_names(net: str = "vgg") -> Tuple[str, ...]:
 
 
 def _tap_widths(net: str = "vgg") -> List[int]:
-    if _net(net) == "alex":
-        return [l[3] for l in ALEXNET_LAYERS]
-    width = {n: cout for n, _, _, cout, _ in vgg16_layers()}
-    return [width[t] for t in LPIPS_TAPS]
+    return [l.cout for l in _layers(net) if l.name in _tap_names(net)]
 
 
 def lpips_random_state(seed: int = 0, net: str = "vgg") -> Dict[str, torch.Tensor]:
@@ -141,26 +120,9 @@ def lpips_random_state(seed: int = 0, net: str = "vgg") -> Dict[str, torch.Tenso
     AlexNet: torchvision's AlexNet keeps nn.Conv2d's default, weights and biases from U(-b, b), b = 1 / sqrt(fan_in) [recalled], so
     its biases are not zero.  `lin` weights from U[0, 1) (the package's are non-negative: the metric is a weighted sum of squares)."""
     g = torch.Generator().manual_seed(seed)
-    sd = {}
-    if _net(net) == "alex":
-        for idx, shape in _conv_table("alex"):
-            b = 1.0 / math.sqrt(shape[1] * shape[2] * shape[3])
-            sd[f"features.{idx}.weight"] = (2 * torch.rand(*shape, generator=g) - 1) * b
-            sd[f"features.{idx}.bias"] = (2 * torch.rand(shape[0], generator=g) - 1) * b
-    else:
-        for _, idx, cin, cout, _ in vgg16_layers():
-            sd[f"features.{idx}.weight"] = torch.randn(cout, cin, 3, 3, generator=g) * math.sqrt(2.0 / (cout * 9))
-            sd[f"features.{idx}.bias"] = torch.zeros(cout)
+    sd = CB.random_conv_state(CB.conv_shapes(_layers(net)), g, kaiming=_net(net) != "alex")
     for k, c in enumerate(_tap_widths(net)):
         sd[f"lin{k}"] = torch.rand(c, generator=g)
-    return sd
-
-
-def _torch_load(path: str) -> Dict[str, torch.Tensor]:
-    sd = torch.load(path, map_location="cpu")
-    sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
-    if not isinstance(sd, dict):
-        raise ValueError(f"{path}: not a state_dict")
     return sd
 
 
@@ -173,12 +135,13 @@ def load_lpips_state(backbone_path: str, lin_path: Optional[str] = None, net: st
     net='alex': the same three with torchvision's alexnet-owt-7be5be79.pth (`features.{0,3,6,8,10}.*`, 5 convolutions), the package's
     weights/v0.1/alex.pth and lpips.LPIPS(net='alex').state_dict() (`net.slice{1..5}.{0,3,6,8,10}.*`).                     [recalled]
     KeyError / ValueError name the key that is missing / mis-shaped; the other backbone's file fails so on its first key."""
-    sd = dict(_torch_load(backbone_path))
-    lin_sd = _torch_load(lin_path) if lin_path else {}
+    sd = dict(CB.load_features_state(backbone_path))
+    lin_sd = CB.load_features_state(lin_path) if lin_path else {}
     out = {}
-    for idx, wshape in _conv_table(net):
+    for conv, wshape in CB.conv_shapes(_layers(net)):
+        idx = conv[len("features."):]
         for leaf, shape in (("weight", wshape), ("bias", wshape[:1])):
-            key = f"features.{idx}.{leaf}"
+            key = f"{conv}.{leaf}"
             cands = [key] + [f"net.slice{s}.{idx}.{leaf}" for s in range(1, 6)]
             src = next((c for c in cands if c in sd), None)
             if src is None:
@@ -215,27 +178,16 @@ def lpips_scaled_input(img_u8: torch.Tensor, bgr: bool = True, normalize: bool =
     return ((x - shift) / scale).permute(0, 3, 1, 2).contiguous()
 
 
-def vgg16_tap_features(x: torch.Tensor, state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+def tap_features(x: torch.Tensor, state: Dict[str, torch.Tensor], net: str = "vgg") -> Dict[str, torch.Tensor]:
     """the five post-ReLU taps of an NCHW input"""
     feats = {}
-    for name, idx, _, _, pooled_before in vgg16_layers():
-        if pooled_before:
-            x = F.max_pool2d(x, 2, 2)
-        x = F.relu(F.conv2d(x, state[f"features.{idx}.weight"].to(x.dtype), state[f"features.{idx}.bias"].to(x.dtype), padding=1))
-        if name in LPIPS_TAPS:
-            feats[name] = x
-    return feats
-
-
-def alexnet_tap_features(x: torch.Tensor, state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """the five post-ReLU taps of an NCHW input, AlexNet backbone"""
-    feats = {}
-    for name, idx, _, _, _, stride, pad, pooled_before in ALEXNET_LAYERS:
-        if pooled_before:
-            x = F.max_pool2d(x, 3, 2)
-        x = F.relu(F.conv2d(x, state[f"features.{idx}.weight"].to(x.dtype), state[f"features.{idx}.bias"].to(x.dtype), stride=stride,
-                            padding=pad))
-        feats[name] = x
+    for l in _layers(net):
+        if l.pool:
+            x = F.max_pool2d(x, l.pool, 2)
+        x = F.relu(F.conv2d(x, state[f"features.{l.idx}.weight"].to(x.dtype), state[f"features.{l.idx}.bias"].to(x.dtype), stride=l.stride,
+                            padding=l.pad))
+        if l.name in _tap_names(net):
+            feats[l.name] = x
     return feats
 
 
@@ -254,10 +206,9 @@ def lpips_from_features(feats0: Dict[str, torch.Tensor], feats1: Dict[str, torch
 def lpips_reference(a_u8, b_u8, state: Dict[str, torch.Tensor], bgr: bool = True, normalize: bool = False,
                     dtype=torch.float64, net: str = "vgg") -> torch.Tensor:
     """LPIPS(net='vgg' | 'alex', version='0.1') of uint8 [N, H, W, 3] RGB image pairs as the reference feeds it (module docstring) -> [N]"""
-    taps = alexnet_tap_features if _net(net) == "alex" else vgg16_tap_features
     with torch.no_grad():
-        f0 = taps(lpips_scaled_input(a_u8, bgr, normalize, dtype), state)
-        f1 = taps(lpips_scaled_input(b_u8, bgr, normalize, dtype), state)
+        f0 = tap_features(lpips_scaled_input(a_u8, bgr, normalize, dtype), state, net)
+        f1 = tap_features(lpips_scaled_input(b_u8, bgr, normalize, dtype), state, net)
         return lpips_from_features(f0, f1, {t: state[f"lin{k}"] for k, t in enumerate(_tap_names(net))})
 
 
@@ -266,29 +217,31 @@ class LPIPSPlan:
     """One static launch list for N image pairs of H x W: ssr_lpips_input for both images (one batch of 2N), the 13 convolutions
     with the ReLU epilogue (the tapped ones stored before their ReLU), ssr_relu_maxpool2_fwd behind taps 1-4, five ssr_lpips_layer.
     The ParamStore is the exact fp32 mode's; `store` shares one (already loaded and packed) between the plans of a LPIPSModel.
-    net='alex': the AlexNet launch list (_init_alex), any H, W >= 31."""
+    net='alex', any H, W >= 31: conv1 and conv2 through ssr_conv_direct, ssr_maxpool3s2_fwd in front of conv2 and conv3, conv3..5
+    through ssr_conv2d, every tap stored AFTER its ReLU, five ssr_lpips_layer with relu = 0.  `direct`: {layer name: (weights
+    [K*K][Cin][Cout], bias)} on the device (cnn_backbone.append_forward), empty for VGG."""
 
     def __init__(self, N: int, H: int, W: int, state: Optional[Dict[str, torch.Tensor]], device="cuda", bgr: bool = True,
                  normalize: bool = False, store=None, lins: Optional[torch.Tensor] = None, net: str = "vgg", direct=None):
-        from . import engine, hip
-        from .hip import view
         self.net = _net(net)
-        if self.net == "alex":
-            self._init_alex(N, H, W, state, device, bgr, normalize, store, lins, direct)
-            return
-        if N <= 0 or H <= 0 or W <= 0 or H % 16 or W % 16:
+        alex = self.net == "alex"
+        if alex and N <= 0:
+            raise ValueError(f"LPIPS needs at least one image pair, got N = {N}")
+        if alex:
+            alexnet_tap_sizes(H, W)                      # ValueError below 31
+        elif N <= 0 or H <= 0 or W <= 0 or H % 16 or W % 16:
             raise ValueError(f"LPIPS (VGG16, four poolings) needs H and W divisible by 16, got {N} x {H} x {W}")
         dev = torch.device(device)
         self.N, self.H, self.W = N, H, W
         if store is None:
-            store, lins = _device_weights(state, dev)
-        self.store, self.lins = store, lins
+            store, lins, direct = _device_weights(state, dev, self.net)
+        self.store, self.lins, self.direct = store, lins, direct or {}
         lib = hip.lib()
         B = 2 * N
-        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)      # noqa: E731
+        z = lambda *s: torch.zeros(B, *s, dtype=torch.float32, device=dev)      # noqa: E731
         self.a_u8 = torch.zeros(N, H, W, 3, dtype=torch.uint8, device=dev)
         self.b_u8 = torch.zeros(N, H, W, 3, dtype=torch.uint8, device=dev)
-        self.xn = z(B, H, W, 8)
+        self.xn = z(H, W, 8)
         self._shift = (C.c_float * 3)(*LPIPS_SHIFT)
         self._scale = (C.c_float * 3)(*LPIPS_SCALE)
         self._perm = (C.c_int32 * 3)(*((2, 1, 0) if bgr else (0, 1, 2)))
@@ -300,29 +253,15 @@ class LPIPSPlan:
               1 if normalize else 0, what="lpips input (image 1)")
         L.add(lib.ssr_lpips_input, self.b_u8.data_ptr(), view(self.xn[N:]), hip.F32, npix, self._shift, self._scale, self._perm,
               1 if normalize else 0, what="lpips input (image 2)")
-        layers = vgg16_layers()
-        self.acts, self.pooled, taps = {}, {}, []
-        src, h, w = self.xn, H, W
-        for name, idx, cin, cout, pooled_before in layers:
-            if pooled_before:
-                h, w = h // 2, w // 2
-            dst = self.acts[name] = z(B, h, w, cout)
-            tapped = name in LPIPS_TAPS
-            cb.conv(L, f"features.{idx}", view(src), h, w, view(dst), act=hip.ACT_NONE if tapped else hip.ACT_RELU)
-            src = dst
-            if tapped:
-                taps.append((name, h * w, cout))
-                if name != LPIPS_TAPS[-1]:
-                    self.pooled[name] = z(B, h // 2, w // 2, cout)
-                    L.add(lib.ssr_relu_maxpool2_fwd, view(dst), view(self.pooled[name]), hip.F32, B, h, w, cout, what=f"relu+pool {name}")
-                    src = self.pooled[name]
-        self._add_taps(L, taps, relu=1)
+        layers, tapped = _layers(self.net), _tap_names(self.net)
+        self.acts, self.pooled = CB.forward_buffers(layers, H, W, z, tapped, not alex)
+        _, taps = CB.append_forward(L, cb, lib, layers, self.xn, H, W, B, hip.F32, tapped, self.acts.__getitem__, self.pooled, not alex,
+                                    self.direct)
+        self._add_taps(L, taps, relu=0 if alex else 1)
         self.launcher = L
 
     def _add_taps(self, L, taps, relu: int):
         """the five ssr_lpips_layer launches over self.acts; partials: per tap [N][nblk] doubles, one buffer, one download"""
-        from . import hip
-        from .hip import view
         lib, N = hip.lib(), self.N
         self.slices, off, woff = [], 0, 0
         for name, hw, c in taps:
@@ -337,65 +276,6 @@ class LPIPSPlan:
                   self.partial.data_ptr() + 8 * poff, what=f"lpips layer {name}")
             woff += c
 
-    def _init_alex(self, N, H, W, state, device, bgr, normalize, store, lins, direct):
-        """AlexNet: ssr_lpips_input for both images (one batch of 2N), conv1 and conv2 through ssr_conv_direct, ssr_maxpool3s2_fwd
-        behind taps 1 and 2, conv3..5 through ssr_conv2d in exact fp32 (ssr_conv_direct where ssr_conv2d answers SSR_EUNSUP for the
-        grid: asked once here through ssr_conv2d_variant, a question of the shape and never of the batch), every tap stored AFTER its
-        ReLU, five ssr_lpips_layer with relu = 0.  `direct`: {layer name: (weights [K*K][Cin][Cout], bias)} on the device."""
-        from . import engine, hip
-        from .hip import view
-        if N <= 0:
-            raise ValueError(f"LPIPS needs at least one image pair, got N = {N}")
-        sizes = alexnet_tap_sizes(H, W)                  # ValueError below 31
-        dev = torch.device(device)
-        self.N, self.H, self.W = N, H, W
-        if store is None:
-            store, lins, direct = _device_weights(state, dev, "alex")
-        self.store, self.lins, self.direct = store, lins, direct
-        lib = hip.lib()
-        B = 2 * N
-        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)      # noqa: E731
-        self.a_u8 = torch.zeros(N, H, W, 3, dtype=torch.uint8, device=dev)
-        self.b_u8 = torch.zeros(N, H, W, 3, dtype=torch.uint8, device=dev)
-        self.xn = z(B, H, W, 8)
-        self._shift = (C.c_float * 3)(*LPIPS_SHIFT)
-        self._scale = (C.c_float * 3)(*LPIPS_SCALE)
-        self._perm = (C.c_int32 * 3)(*((2, 1, 0) if bgr else (0, 1, 2)))
-        cb = engine._ConvBuilder(store, B)
-        self._cb = cb
-        L = engine.Launcher()
-        npix = N * H * W
-        L.add(lib.ssr_lpips_input, self.a_u8.data_ptr(), view(self.xn[:N]), hip.F32, npix, self._shift, self._scale, self._perm,
-              1 if normalize else 0, what="lpips input (image 1)")
-        L.add(lib.ssr_lpips_input, self.b_u8.data_ptr(), view(self.xn[N:]), hip.F32, npix, self._shift, self._scale, self._perm,
-              1 if normalize else 0, what="lpips input (image 2)")
-        self.acts, self.pooled, taps = {}, {}, []
-        src, h, w = self.xn, H, W
-        for (name, idx, cin, cout, k, stride, pad, pooled_before), (ho, wo) in zip(ALEXNET_LAYERS, sizes):
-            if pooled_before:
-                ph, pw = (h - 3) // 2 + 1, (w - 3) // 2 + 1
-                p = self.pooled[name] = z(B, ph, pw, src.shape[-1])
-                L.add(lib.ssr_maxpool3s2_fwd, view(src), view(p), hip.F32, B, h, w, src.shape[-1], 0, what=f"pool in front of {name}")
-                src, h, w = p, ph, pw
-            dst = self.acts[name] = z(B, ho, wo, cout)
-            use_direct = k != 3
-            if not use_direct:
-                cb.conv(L, f"features.{idx}", view(src), h, w, view(dst), act=hip.ACT_RELU)
-                rc = lib.ssr_conv2d_variant(C.byref(cb.keep[-1]))
-                if rc == -2:                              # SSR_EUNSUP for this grid: the generic kernel
-                    L.calls.pop()
-                    use_direct = True
-                elif rc < 0:
-                    hip.check(rc, f"ssr_conv2d_variant {name}")
-            if use_direct:
-                wd, bd = self.direct[name]
-                L.add(lib.ssr_conv_direct, view(src), view(dst), wd.data_ptr(), bd.data_ptr(), hip.F32, B, h, w, wd.shape[1], cout, k,
-                      stride, pad, 1, what=f"conv direct {name}")
-            taps.append((name, ho * wo, cout))
-            src, h, w = dst, ho, wo
-        self._add_taps(L, taps, relu=0)
-        self.launcher = L
-
     def run(self, a_u8: torch.Tensor, b_u8: torch.Tensor) -> torch.Tensor:
         """-> float64 [N] on the host (one download: the partials, added in index order per tap, taps in order)"""
         self.a_u8.copy_(a_u8)
@@ -409,11 +289,10 @@ class LPIPSPlan:
 
 
 def _device_weights(state: Dict[str, torch.Tensor], dev, net: str = "vgg"):
-    """VGG: (ParamStore of the VGG16 convolutions in the exact fp32 mode, loaded and packed; the five lin vectors as one fp32 tensor).
-    AlexNet: (ParamStore of its three 3x3 layers, the same; the lin vectors; {layer: (weights [K*K][CinPad][Cout], bias)} in
-    ssr_conv_direct's layout for all five layers, permuted here in torch: conv1's 3 input channels padded with zero weights to the 8
-    channels ssr_lpips_input writes)."""
-    from . import engine, hip
+    """-> (ParamStore of the backbone's 3x3 convolutions in the exact fp32 mode, loaded and packed; the five lin vectors as one fp32
+    tensor; `direct`).  `direct` is empty for VGG; AlexNet: {layer: (weights [K*K][CinPad][Cout], bias)} in ssr_conv_direct's layout
+    for all five layers, permuted here in torch: conv1's 3 input channels padded with zero weights to the 8 channels ssr_lpips_input
+    writes."""
     net = _net(net)
     widths = _tap_widths(net)
     for k, c in enumerate(widths):
@@ -422,22 +301,21 @@ def _device_weights(state: Dict[str, torch.Tensor], dev, net: str = "vgg"):
         if tuple(state[f"lin{k}"].shape) != (c,):
             raise ValueError(f"lin{k}: shape {tuple(state[f'lin{k}'].shape)}, expected ({c},)")
     direct = {}
-    if net == "alex":
-        for name, idx, cin, cout, k, _, _, _ in ALEXNET_LAYERS:
-            for leaf, shape in (("weight", (cout, cin, k, k)), ("bias", (cout,))):
-                key = f"features.{idx}.{leaf}"
-                if key not in state:
-                    raise KeyError(key)
-                if tuple(state[key].shape) != shape:
-                    raise ValueError(f"{key}: shape {tuple(state[key].shape)}, expected {shape}")
-            wd = torch.zeros(k * k, -(-cin // 8) * 8, cout, dtype=torch.float32)
-            wd[:, :cin] = state[f"features.{idx}.weight"].detach().to(torch.float32).permute(2, 3, 1, 0).reshape(k * k, cin, cout)
-            direct[name] = (wd.to(dev), state[f"features.{idx}.bias"].detach().to(torch.float32).contiguous().to(dev))
-    store = engine.ParamStore(alexnet_specs() if net == "alex" else vgg16_specs(), hip.F32, device=dev)
+    for l in ALEXNET_LAYERS if net == "alex" else ():
+        cout, cin, k, conv = l.cout, l.cin, l.k, f"features.{l.idx}"
+        for key, shape in ((conv + ".weight", (cout, cin, k, k)), (conv + ".bias", (cout,))):
+            if key not in state:
+                raise KeyError(key)
+            if tuple(state[key].shape) != shape:
+                raise ValueError(f"{key}: shape {tuple(state[key].shape)}, expected {shape}")
+        wd = torch.zeros(k * k, -(-cin // 8) * 8, cout, dtype=torch.float32)
+        wd[:, :cin] = state[conv + ".weight"].detach().to(torch.float32).permute(2, 3, 1, 0).reshape(k * k, cin, cout)
+        direct[l.name] = (wd.to(dev), state[conv + ".bias"].detach().to(torch.float32).contiguous().to(dev))
+    store = engine.ParamStore(CB.conv_specs(_layers(net), dgrad_packed=False), hip.F32, device=dev)
     store.load_state_dict(state)
     store.pack()
     lins = torch.cat([state[f"lin{k}"].to(torch.float32) for k in range(len(widths))]).to(dev)
-    return (store, lins, direct) if net == "alex" else (store, lins)
+    return store, lins, direct
 
 
 class LPIPSModel:
@@ -446,11 +324,7 @@ class LPIPSModel:
     def __init__(self, state: Dict[str, torch.Tensor], device="cuda", net: str = "vgg"):
         self.device = torch.device(device)
         self.net = _net(net)
-        self.direct = None
-        if self.net == "alex":
-            self.store, self.lins, self.direct = _device_weights(state, self.device, "alex")
-        else:
-            self.store, self.lins = _device_weights(state, self.device)
+        self.store, self.lins, self.direct = _device_weights(state, self.device, self.net)
         self.plans: Dict[Tuple, LPIPSPlan] = {}
 
     def plan(self, N: int, H: int, W: int, bgr: bool = True, normalize: bool = False) -> LPIPSPlan:

@@ -7,6 +7,8 @@ VGG19 (torchvision `features`, frozen): 16 3x3 convolutions + ReLU, 2x2 max-pool
 loss reads the conv outputs BEFORE the ReLU.  The convolutions and their dgrads run on the conv kernels through the C ABI
 (SSR_ACT_RELU epilogue, ReLU' masks); the tapped layers are exactly the ones in front of a pooling, so "ReLU + max-pool" is one
 pass over the stored pre-ReLU feature (csrc/vgg.hip).  Only dgrads are needed (the extractor's parameters are frozen).
+The layer table, the specs, the random weights and the forward's launches are cnn_backbone.py, shared with the LPIPS metric's VGG16
+and AlexNet; what is here is the loss's own: option checks, normalisation, the Gram and L1 launches and the dgrad chain.
 The gradient w.r.t. the generator output is ADDED to the L1-gradient buffer that the discriminator's input-gradient kernel
 already folds in (train_step._phase_g), so no extra pass over the 128x128 output exists.
 
@@ -21,56 +23,35 @@ accepted too).  There is no network access here, so benchmarks and tests use ran
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 from typing import Dict, List, Optional
 
 import torch
 
-from . import engine, hip
+from . import cnn_backbone as CB, engine, hip
 from .hip import view
 
 VGG_PRETRAIN_PATH = "experiments/pretrained_models/vgg19-dcbb9e9d.pth"    # basicsr/archs/vgg_arch.py
 VGG_MEAN = (0.485, 0.456, 0.406)
 VGG_STD = (0.229, 0.224, 0.225)
-# (block, convs in the block, width)
-VGG19_BLOCKS = ((1, 2, 64), (2, 2, 128), (3, 4, 256), (4, 4, 512), (5, 4, 512))
 
 
 def vgg19_layers():
     """[(name 'convB_J', torchvision features index, cin, cout, pooled_before)]"""
-    out, idx, cin = [], 0, 3
-    for b, n, width in VGG19_BLOCKS:
-        for j in range(1, n + 1):
-            out.append((f"conv{b}_{j}", idx, cin, width, j == 1 and b > 1))
-            idx += 2                    # conv, relu
-            cin = width
-        idx += 1                        # pool
-    return out
+    return [(l.name, l.idx, l.cin, l.cout, bool(l.pool)) for l in CB.vgg_layers(CB.VGG19_BLOCKS)]
 
 
 def vgg19_specs(last: str) -> List[engine.ConvSpec]:
-    specs = []
-    for name, idx, cin, cout, _ in vgg19_layers():
-        specs.append(engine.ConvSpec(f"features.{idx}", cout, cin, 3, 1, True, False))
-        if name == last:
-            break
-    return specs
+    return CB.conv_specs(CB.vgg_layers(CB.VGG19_BLOCKS), last)
 
 
 def vgg19_random_state(specs, seed: int = 0):
     """torchvision VGG._initialize_weights: kaiming_normal_(fan_out, relu), zero bias."""
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for s in specs:
-        sd[s.name + ".weight"] = torch.randn(s.cout, s.cin, 3, 3, generator=g) * math.sqrt(2.0 / (s.cout * 9))
-        sd[s.name + ".bias"] = torch.zeros(s.cout)
-    return sd
+    return CB.random_conv_state([(s.name, (s.cout, s.cin, s.k, s.k)) for s in specs], torch.Generator().manual_seed(seed))
 
 
 def load_vgg19_state(path: str) -> Dict[str, torch.Tensor]:
-    sd = torch.load(path, map_location="cpu")
-    sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+    sd = CB.load_features_state(path)
     return {k[len("vgg_net."):] if k.startswith("vgg_net.") else k: v for k, v in sd.items() if "features." in k}
 
 
@@ -103,23 +84,23 @@ class PerceptualPlan:
         self.feature = self.pw > 0.0 or not self.style
         if self.style and not style_loss_ptr:
             raise ValueError("PerceptualPlan: style_weight > 0 needs style_loss_ptr (the l_g_style slot)")
-        names = [n for n, *_ in vgg19_layers()]
+        net = CB.vgg_layers(CB.VGG19_BLOCKS)
+        names = [l.name for l in net]
         for k in self.layer_weights:
             if k not in names:
                 raise NotImplementedError(f"perceptual layer {k!r}: features are supported at conv outputs (before the ReLU)")
-        layers = vgg19_layers()
         last = max(self.layer_weights, key=names.index)
-        layers = layers[:names.index(last) + 1]
-        for (n, *_), nxt in zip(layers, layers[1:]):
+        net = net[:names.index(last) + 1]
+        for l, nxt in zip(net, net[1:]):
             # a tapped layer is stored before its ReLU; the fused ReLU+pool pass needs a pooling behind it
-            if n in self.layer_weights and not nxt[4]:
-                raise NotImplementedError(f"perceptual layer {n!r}: taps are supported in front of a pooling layer (and at the last layer)")
+            if l.name in self.layer_weights and not nxt.pool:
+                raise NotImplementedError(f"perceptual layer {l.name!r}: taps are supported in front of a pooling layer (and at the last layer)")
         mode = dtype                          # (hip.F32F: the VGG forward in exact fp32 too - its ReLU decisions shape the image gradient)
         dtype = hip.storage_code(mode)
         self.dt, self.B, self.H, self.W = dtype, B, H, W
         tdt = hip.torch_dtype(dtype)
         dev = x_buf.device
-        self.store = engine.ParamStore(vgg19_specs(last), mode, device=dev)
+        self.store = engine.ParamStore(CB.conv_specs(net), mode, device=dev)
         sd = state
         self.random_weights = False
         if sd is None:
@@ -137,7 +118,7 @@ class PerceptualPlan:
                     f"perceptual_opt needs the VGG19 weights: put torchvision's vgg19-dcbb9e9d.pth at {VGG_PRETRAIN_PATH} (BasicSR's "
                     "location), or set SSR_VGG19_WEIGHTS=<file>; SSR_VGG19_RANDOM=1 runs with random weights (throughput only)")
         self.store.load_state_dict(sd)
-        z = lambda *s: torch.zeros(*s, dtype=tdt, device=dev)
+        z = lambda *s: torch.zeros(B, *s, dtype=tdt, device=dev)
         use_norm, range_norm = bool(opt.get("use_input_norm", True)), bool(opt.get("range_norm", False))
         # y = ((x + 1)/2 if range_norm else x - mean)/std ...   as one per-channel affine map
         a = 0.5 if range_norm else 1.0
@@ -146,42 +127,25 @@ class PerceptualPlan:
         self._scale = (C.c_float * 8)(*[a / s for s in std], *([0.0] * 5))
         self._shift = (C.c_float * 8)(*[(b - m) / s for m, s in zip(mean, std)], *([0.0] * 5))
         self._zero = (C.c_float * 8)(*([0.0] * 8))
-        self.xn = z(B, H, W, 8)          # normalised image (3 of 8 channels)
-        self.g_xn = z(B, H, W, 8)
+        self.xn = z(H, W, 8)             # normalised image (3 of 8 channels)
+        self.g_xn = z(H, W, 8)
         cb = engine._ConvBuilder(self.store, B)
         self._cb = cb
         lib = hip.lib()
         # activations: per conv either the post-ReLU output (plain layers) or the pre-ReLU feature (tapped layers) + its pooled twin
-        acts, feats_t, pooled, g_acts, g_pooled = {}, {}, {}, {}, {}
-        h, w = H, W
-        dims = {}
-        for name, idx, cin, cout, pooled_before in layers:
-            if pooled_before:
-                h, w = h // 2, w // 2
-            dims[name] = (h, w)
-            acts[name] = z(B, h, w, cout)
-            g_acts[name] = z(B, h, w, cout)
-            if name in self.layer_weights:
-                feats_t[name] = z(B, h, w, cout)
-                if name != last:
-                    pooled[name] = z(B, h // 2, w // 2, cout)
-                    g_pooled[name] = z(B, h // 2, w // 2, cout)
+        acts, pooled = CB.forward_buffers(net, H, W, z, self.layer_weights, True)
+        g_acts, g_pooled = CB.forward_buffers(net, H, W, z, self.layer_weights, True)
+        feats_t = {name: torch.zeros_like(acts[name]) for name in acts if name in self.layer_weights}
+        dims = dict(zip(names, CB.tap_sizes(net, H, W)))
+        layers = vgg19_layers()[:len(net)]           # as `layers` exposes them: (name, index, cin, cout, pooled_before)
         self.acts, self.feats_t, self.g_acts = acts, feats_t, g_acts
         npix = B * H * W
 
         def forward(img: torch.Tensor, outs: Dict[str, torch.Tensor]) -> engine.Launcher:
             L = engine.Launcher()
             L.add(lib.ssr_channel_affine, view(img), view(self.xn), dtype, npix, 3, self._scale, self._shift, 0, what="vgg normalise")
-            src = self.xn
-            for name, idx, cin, cout, pooled_before in layers:
-                hh, ww = dims[name]
-                tapped = name in self.layer_weights
-                dst = outs[name] if tapped else acts[name]
-                cb.conv(L, f"features.{idx}", view(src), hh, ww, view(dst), act=hip.ACT_NONE if tapped else hip.ACT_RELU)
-                src = dst
-                if tapped and name != last:
-                    L.add(lib.ssr_relu_maxpool2_fwd, view(dst), view(pooled[name]), dtype, B, hh, ww, cout, what=f"relu+pool {name}")
-                    src = pooled[name]
+            CB.append_forward(L, cb, lib, net, self.xn, H, W, B, dtype, self.layer_weights,
+                              lambda name: outs[name] if name in self.layer_weights else acts[name], pooled, True)
             return L
 
         self.fwd_target = forward(tgt_buf, feats_t)
@@ -197,7 +161,7 @@ class PerceptualPlan:
                 hip.check(min(splits[name], 0), f"ssr_gram_splits {name}")
                 self.gram_x[name] = torch.zeros(B, cout, cout, dtype=torch.float32, device=dev)
                 self.gram_t[name] = torch.zeros(B, cout, cout, dtype=torch.float32, device=dev)
-                self.gram_s[name] = z(B, cout, cout)            # sign(D) in the feature dtype (+-1 / 0: exact)
+                self.gram_s[name] = z(cout, cout)          # sign(D) in the feature dtype (+-1 / 0: exact)
             # one split-partial workspace for every Gram launch (they run in order on one stream)
             ws_n = max([splits[k] * B * acts[k].shape[-1] ** 2 for k in splits if splits[k] > 1] or [1])
             self.gram_ws = torch.zeros(ws_n, dtype=torch.float32, device=dev)
@@ -226,14 +190,14 @@ class PerceptualPlan:
                 coef = self.sw * wgt / (B * cout * cout) * 2.0 / (cout * hh * ww)
                 Bk.add(lib.ssr_gram_bwd, view(acts[name]), self.gram_s[name].data_ptr(), view(g_acts[name]), dtype, B, hh * ww, cout, coef,
                        1 if self.feature else 0, what=f"gram bwd {name}")
-        for li in reversed(range(len(layers))):
-            name, idx, cin, cout, pooled_before = layers[li]
+        for li in reversed(range(len(net))):
+            name, idx, cout = net[li].name, net[li].idx, net[li].cout
             hh, ww = dims[name]
             if li == 0:      # conv1_1: gradient w.r.t. the normalised image (3 channels), no mask
                 cb.dgrad(Bk, f"features.{idx}", view(g_acts[name]), hh, ww, view(self.g_xn), cout=8, cin_dy=cout)
                 break
-            pname = layers[li - 1][0]
-            if pooled_before:
+            pname = net[li - 1].name
+            if net[li].pool:
                 # input is pooled[pname]: plain dgrad into its gradient, then route through ReLU + pooling into the tapped feature
                 cb.dgrad(Bk, f"features.{idx}", view(g_acts[name]), hh, ww, view(g_pooled[pname]))
                 ph, pw_ = dims[pname]

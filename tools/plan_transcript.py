@@ -30,6 +30,19 @@ size (packing is a kernel); their addresses are canonical either way.
   python tools/plan_transcript.py --show loss/split/mfma/d72
 
 tests/test_tower_plans_host.py and tests/test_gpu_tower_plans.py hold vit_tower.py, clipscore_metric.py and clip_loss.py to that file.
+
+The CNN feature backbones have the third table, BACKBONE_CONFIGS: the LPIPS metric plan (VGG16 under both feeds; AlexNet at its three
+test sizes, under both feeds, and once with its 3 x 3 layers refused by ssr_conv2d) at N = 2 and the perceptual loss plan (fwd_target,
+fwd, bwd; the shipped taps in every arithmetic mode, and in fp32 a truncated tap set, the style term with and without the feature term,
+both normalisation switches and the deterministic loss flag) at B = 2, 16 x 32.  Per configuration the text lists every launcher, the
+plan's ParamStore with a sha256 over its fp32 arena, every other device weight (key, shape, dtype, one sha256 over the bytes) and the
+element count of every buffer the plan owns by attribute name; the file also holds the sha256 of three random states.  On the CPU
+ParamStore.pack() (a kernel) is a no-op.
+
+  python tools/plan_transcript.py --backbone-golden tests/golden/backbone_plans.json
+  python tools/plan_transcript.py --show lpips/alex/64x64
+
+tests/test_backbone_plans_host.py and tests/test_gpu_backbone_plans.py hold cnn_backbone.py, lpips_metric.py and perceptual.py to that file.
 """
 import argparse
 import bisect
@@ -555,10 +568,170 @@ def tower_golden(runs):
             "full_text": {k: runs[k][0].splitlines() for k in TOWER_FULL_TEXT}}
 
 
+# ---------------------------------------------------------------------------------------------------- the CNN feature backbones
+# The LPIPS metric plan (VGG16, AlexNet) and the perceptual loss plan (VGG19): cnn_backbone.py, lpips_metric.py, perceptual.py, recorded in
+# tests/golden/backbone_plans.json.  The smallest shapes at which each branch is still taken.  AlexNet's three 3 x 3 layers go to
+# ssr_conv2d at all three of the project's test sizes (grids of 1 x 1, 1 x 2 and 3 x 3), and at every other size: the pipelined family
+# of csrc/conv.hip takes any grid of a 3 x 3 stride-1 layer in exact fp32 (pipe_shape_ok), so no image size makes ssr_conv2d_variant
+# answer SSR_EUNSUP there (31 ... 299 a side were tried).  The plan's fallback to ssr_conv_direct is therefore recorded by the
+# configuration lpips/alex/31x31/refused, in which the tool answers the plan's question with SSR_EUNSUP itself (_conv2d_refuses).
+BACKBONE_N = 2
+VGG_HW = (16, 32)                    # the smallest sides four poolings allow, and not square
+SHIPPED_LAYER_WEIGHTS = {"conv1_2": 0.1, "conv2_2": 0.1, "conv3_4": 1, "conv4_4": 1, "conv5_4": 1}        # options/*.yml
+BACKBONE_FULL_TEXT = ("lpips/alex/64x64", "perceptual/fp32/style")
+BACKBONE_CONFIGS = {}                # name -> (builder, keyword arguments)
+
+
+class _no_pack:
+    """on the CPU, ParamStore.pack() (which launches ssr_pack_weights) does nothing"""
+
+    def __init__(self, dev):
+        self.cpu = _on_cpu(dev)
+
+    def __enter__(self):
+        from satlas_super_resolution_amd import engine
+        self.real = engine.ParamStore.pack
+        if self.cpu:
+            engine.ParamStore.pack = lambda store: None
+
+    def __exit__(self, *exc):
+        from satlas_super_resolution_amd import engine
+        engine.ParamStore.pack = self.real
+
+
+class _conv2d_refuses:
+    """ssr_conv2d_variant answers SSR_EUNSUP (-2) for every descriptor, as if no kernel family took the grid"""
+
+    def __init__(self, on):
+        self.on = on
+
+    def __enter__(self):
+        from satlas_super_resolution_amd import hip
+        self.real = hip.lib().ssr_conv2d_variant
+        if self.on:
+            hip.lib().ssr_conv2d_variant = lambda desc: -2
+
+    def __exit__(self, *exc):
+        from satlas_super_resolution_amd import hip
+        hip.lib().ssr_conv2d_variant = self.real
+
+
+def _lpips_backbone(dev, net, H, W, bgr=True, normalize=False, refused=False):
+    from satlas_super_resolution_amd import lpips_metric as LM
+    with _no_pack(dev):
+        model = LM.LPIPSModel(LM.lpips_random_state(17, net), dev, net=net)
+    with _conv2d_refuses(refused):
+        plan = model.plan(BACKBONE_N, H, W, bgr=bgr, normalize=normalize)
+    weights = [("lins", model.lins)]
+    for name, (w, b) in (getattr(model, "direct", None) or {}).items():
+        weights += [("direct.%s.weight" % name, w), ("direct.%s.bias" % name, b)]
+    return plan, [("launcher", plan.launcher)], weights, []
+
+
+def _perceptual_backbone(dev, mode, layer_weights=SHIPPED_LAYER_WEIGHTS, loss_flags=0, **opt):
+    """generated image, target and gradient buffers of 8 channels; l_g_percep into the first half of a two-slot loss buffer, l_g_style into
+    the second"""
+    import torch
+    from satlas_super_resolution_amd import hip, perceptual as P
+    (H, W), code = VGG_HW, hip.dtype_code(mode)
+    x, tgt, grad = (torch.zeros(BACKBONE_N, H, W, 8, dtype=hip.torch_dtype(hip.storage_code(code)), device=dev) for _ in range(3))
+    loss = torch.zeros(2 * hip.LOSS_SLOTS, device=dev)
+    opt = dict({"type": "PerceptualLoss", "layer_weights": dict(layer_weights), "vgg_type": "vgg19", "use_input_norm": True,
+                "perceptual_weight": 1.0, "style_weight": 0, "range_norm": False, "criterion": "l1"}, **opt)
+    state = P.vgg19_random_state(P.vgg19_specs(list(layer_weights)[-1]), 3)
+    plan = P.PerceptualPlan(opt, BACKBONE_N, H, W, code, x, tgt, grad, loss.data_ptr(), state=state, loss_flags=loss_flags,
+                            style_loss_ptr=loss.data_ptr() + 4 * hip.LOSS_SLOTS)
+    if not _on_cpu(dev):
+        plan.pack()
+    return plan, [(n, getattr(plan, n)) for n in ("fwd_target", "fwd", "bwd")], [], [x, tgt, grad, loss]
+
+
+def _backbone_configs():
+    from satlas_super_resolution_amd import hip
+    cfg = BACKBONE_CONFIGS
+    cfg["lpips/vgg/bgr"] = (_lpips_backbone, dict(net="vgg", H=VGG_HW[0], W=VGG_HW[1]))                 # the reference's feed
+    cfg["lpips/vgg/rgb+normalize"] = (_lpips_backbone, dict(net="vgg", H=VGG_HW[0], W=VGG_HW[1], bgr=False, normalize=True))
+    for H, W in ((31, 31), (35, 47), (64, 64)):                   # 31: ALEXNET_MIN_SIDE, taps of 7, 3, 1, 1, 1
+        cfg["lpips/alex/%dx%d" % (H, W)] = (_lpips_backbone, dict(net="alex", H=H, W=W))
+    cfg["lpips/alex/31x31/refused"] = (_lpips_backbone, dict(net="alex", H=31, W=31, refused=True))
+    cfg["lpips/alex/64x64/rgb+normalize"] = (_lpips_backbone, dict(net="alex", H=64, W=64, bgr=False, normalize=True))
+    for mode in MODES:
+        cfg["perceptual/%s" % mode] = (_perceptual_backbone, dict(mode=mode))
+    for name, kw in (("conv3_4", dict(layer_weights={"conv1_2": 0.1, "conv2_2": 0.1, "conv3_4": 1})),
+                     ("style", dict(style_weight=0.5)), ("style_only", dict(style_weight=0.5, perceptual_weight=0)),
+                     ("no_input_norm", dict(use_input_norm=False)), ("range_norm", dict(range_norm=True)),
+                     ("deterministic", dict(loss_flags=hip.DETERMINISTIC))):
+        cfg["perceptual/fp32/%s" % name] = (_perceptual_backbone, dict(mode="fp32", **kw))
+
+
+_backbone_configs()
+
+
+def _sha_tensors(pairs):
+    h = hashlib.sha256()
+    for k, t in pairs:
+        h.update(k.encode())
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+def backbone_transcript(plan, launchers, weights, extra):
+    """-> (text, number of C-ABI calls): every launcher, the plan's ParamStore (and a sha256 over its fp32 arena), the (key, shape, dtype)
+    of every other device weight with one sha256 over the keys and bytes, the element count of every buffer the plan owns by attribute"""
+    import torch
+    canon = Canon([plan] + list(extra))
+    out, calls = [], 0
+    for name, L in launchers:
+        out.append("launcher %s" % name)
+        calls += fmt_launcher(canon, L, out, "  ")
+    fmt_store(canon, plan.store, out)
+    out.append("store data sha256 %s" % _sha_tensors([("data", plan.store.data)]))
+    for k, t in weights:
+        out.append("weight %s %s %s" % (k, list(t.shape), str(t.dtype).replace("torch.", "")))
+    if weights:
+        out.append("weights sha256 %s" % _sha_tensors(weights))
+    for attr in sorted(vars(plan)):
+        v = getattr(plan, attr)
+        if isinstance(v, torch.Tensor) and attr != "lins":
+            out.append("buffer %s numel %d" % (attr, v.numel()))
+        elif isinstance(v, dict) and v and all(isinstance(t, torch.Tensor) for t in v.values()):
+            out += ["buffer %s.%s numel %d" % (attr, k, v[k].numel()) for k in sorted(v)]
+    return "\n".join(out) + "\n", calls
+
+
+def backbone_objects(name, dev="cpu"):
+    fn, kw = BACKBONE_CONFIGS[name]
+    return fn(dev, **kw)
+
+
+def build_backbone(name, dev="cpu"):
+    """(text, calls) of one backbone configuration"""
+    return backbone_transcript(*backbone_objects(name, dev))
+
+
+def backbone_sweep(dev="cpu"):
+    return {name: build_backbone(name, dev) for name in BACKBONE_CONFIGS}
+
+
+def random_state_hashes():
+    """the generator draw order of the three random states (committed fixtures and recorded figures were made with it): keys plus bytes"""
+    from satlas_super_resolution_amd import lpips_metric as LM, perceptual as P
+    return {"lpips_random_state(17, 'vgg')": _sha_tensors(LM.lpips_random_state(17, "vgg").items()),
+            "lpips_random_state(17, 'alex')": _sha_tensors(LM.lpips_random_state(17, "alex").items()),
+            "vgg19_random_state(vgg19_specs('conv5_4'), 3)": _sha_tensors(P.vgg19_random_state(P.vgg19_specs("conv5_4"), 3).items())}
+
+
+def backbone_golden(runs):
+    return {"configs": {k: {"calls": c, "sha256": digest(t)} for k, (t, c) in runs.items()},
+            "random_states": random_state_hashes(),
+            "full_text": {k: runs[k][0].splitlines() for k in BACKBONE_FULL_TEXT}}
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--golden")
     ap.add_argument("--tower-golden")
+    ap.add_argument("--backbone-golden")
     ap.add_argument("--one", action="store_true")
     ap.add_argument("--setting", default="")
     ap.add_argument("--show")
@@ -572,8 +745,16 @@ if __name__ == "__main__":
             json.dump(doc, f, indent=0)
             f.write("\n")
         print("%d tower transcripts -> %s (%d bytes)" % (len(doc["configs"]), a.tower_golden, os.path.getsize(a.tower_golden)))
+    elif a.backbone_golden:
+        doc = backbone_golden(backbone_sweep(a.device))
+        with open(a.backbone_golden, "w") as f:
+            json.dump(doc, f, indent=0)
+            f.write("\n")
+        print("%d backbone transcripts -> %s (%d bytes)" % (len(doc["configs"]), a.backbone_golden, os.path.getsize(a.backbone_golden)))
     elif a.show in TOWER_CONFIGS:
         sys.stdout.write(build_tower(a.show, a.device)[0])
+    elif a.show in BACKBONE_CONFIGS:
+        sys.stdout.write(build_backbone(a.show, a.device)[0])
     elif a.show:
         name, mode = a.show.split("/")
         sys.stdout.write(build(name, mode, a.device)[0])
